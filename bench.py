@@ -16,6 +16,11 @@ limited to exactly K iterations from the initial guess (tolerance 0: nothing con
 counts, hence the time per step, grow along the Krylov space, so K is part of the metric label), inputs resident in HBM;
 the preconditioner set-up (diag, SpGEMM, 2x ILU(0)) is reported separately.
 
+A plain run sets up, warms up, times the K steps and prints the result line (headline, `config`, `phases`).  `--full`
+adds what the headline does not need: HIP events around the launches of the sampled kernel classes inside the timed
+solve (`kernel_classes`, `roofline`), the CPU baseline with its like-for-like GPU pairs, and the `--converge` solve.
+`--dump-outputs DIR` writes what the timed solve computed in its last step to DIR/<name>.npy (see dump_outputs).
+
 One process per GPU: `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...`.
 """
 from __future__ import annotations
@@ -37,6 +42,8 @@ BYTES_PER_DOF = 3.9e3          # measured working set of FGMRES + aSIMPLE at 120
 N_DOFS_NORTH_STAR = 167_545_276  # 4800x1600
 NAMES_S = ["GMRES", "FGMRES", "Bicgstab"]
 NAMES_P = ["blockDiagonal", "blockTriangular", "aSIMPLE"]
+DUMP_VALUES = 6_000_000        # solution entries --dump-outputs writes at most, over all ranks (48 MB of float64)
+DUMP_SEED = 2024
 
 
 _T0 = time.time()
@@ -90,7 +97,12 @@ def parse():
                     help="NSK_OPT_SCHUR_SIGN of the --converge solve ONLY: -1 negates aSIMPLE's S (labelled deviation from the "
                          "reference, off by default; the timed region always runs the reference's +1)")
     ap.add_argument("--blas1-pairs", type=int, default=-1, help="NSK_OPT_BLAS1_PAIRS: -1 by variant (default), 0, 1")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the figures beside the headline: sampled kernel classes and roofline (HIP events inside the "
+                         "timed solve), the CPU baseline (--cpu-*) with its GPU pairs, the --converge solve")
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                    help="after the timed steps, write what they computed to DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-mesh", type=str, default="",
                     help="mesh of the CPU baseline's first sample; default: the bench mesh itself (1200,400 at N = 1)")
     ap.add_argument("--cpu-steps", type=int, default=1,
@@ -99,11 +111,14 @@ def parse():
     ap.add_argument("--cpu-mesh2", type=str, default="300,100", help="second, smaller CPU sample ('' = none)")
     ap.add_argument("--cpu-steps2", type=int, default=12)
     ap.add_argument("--cpu-threads", type=int, default=0, help="0 = all host cores")
-    ap.add_argument("--converge", type=float, default=0.0, help="if > 0: also one full solve to this tolerance (see --converge-*)")
+    ap.add_argument("--converge", type=float, default=0.0, help="if > 0 (with --full): also one full solve to this tolerance (see --converge-*)")
     ap.add_argument("--converge-mesh", type=str, default="300,100")
     ap.add_argument("--converge-preconditioner", type=int, default=0, help="default: BASELINE configs[1], FGMRES + blockDiagonal")
     ap.add_argument("--converge-budget", type=float, default=600.0, help="seconds after which the solve is cancelled")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.converge > 0 and not args.full:
+        ap.error("--converge is part of --full")
+    return args
 
 
 def choose_workload(world, scaling="auto", mesh="", reynolds=0.0):
@@ -272,6 +287,28 @@ def converged_solve(S, PT, P, dist, args, world, rank, local_rank, sync):
     return out
 
 
+def dump_outputs(ls, res, out_dir, rank, world):
+    """What the timed solve hands its caller, as float64 arrays in DIR/<name>.npy: the solution after the K timed outer
+    iterations (`solution_u`, `solution_p`; `_rank<r>` appended on more than one rank), the final residual and the residual
+    history of the outer solver (rank 0).  A solution above DUMP_VALUES entries is written as a fixed sample: the sorted
+    indices np.random.default_rng([DUMP_SEED, 0 (u) / 1 (p)]).choice(n, m, replace=False), the same for the same sizes."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    xu, xp = ls.download_solution()
+    budget = DUMP_VALUES // world
+    n = xu.size + xp.size
+    tag = f"_rank{rank}" if world > 1 else ""
+    for k, (name, x) in enumerate((("solution_u", xu), ("solution_p", xp))):
+        if n > budget:
+            m = budget * x.size // n
+            idx = np.sort(np.random.default_rng([DUMP_SEED, k]).choice(x.size, m, replace=False, shuffle=False))
+            x = x[idx]
+        np.save(os.path.join(out_dir, name + tag + ".npy"), np.ascontiguousarray(x, dtype=np.float64))
+    if rank == 0:
+        np.save(os.path.join(out_dir, "final_residual.npy"), np.array([res], dtype=np.float64))
+        np.save(os.path.join(out_dir, "residual_history.npy"), np.asarray(ls.history(), dtype=np.float64))
+
+
 def main():
     args = parse()
     rank = int(os.environ.get("RANK", "0"))
@@ -326,15 +363,15 @@ def main():
 
     aS = args.preconditioner == 2
     ops = (20, 0, 21) + ((5,) if aS else (3,))
-    # warm-up + timed region; HIP events around every launch of the sampled ops inside the timed solve
-    ls.setup_preconditioner(args.preconditioner, args.variant, 0.5)
+    # warm-up + timed region; with --full, HIP events around every launch of the sampled ops inside the timed solve
     ls.upload_system(pr.rhs_u, pr.rhs_p, pr.x0_u, pr.x0_p)
     ls.solve_resident(args.solver, 0.0, max(1, args.warmup))   # (falls back to per-colour launches by itself if needed)
     ls.setup_preconditioner(args.preconditioner, args.variant, 0.5)
     ls.upload_system(pr.rhs_u, pr.rhs_p, pr.x0_u, pr.x0_p)
     ls.reset_stats()
-    for op in ops:
-        ls.profile_begin(op, 1024)
+    if args.full:
+        for op in ops:
+            ls.profile_begin(op, 1024)
     say(f"timed region: {args.steps} outer iterations")
     barrier()
     sync()
@@ -344,8 +381,10 @@ def main():
     barrier()
     dt = time.perf_counter() - t0
     say(f"timed region done: {dt:.2f} s")
-    prof = {op: ls.profile_read(op) for op in ops}
-    ls.profile_end()
+    prof = {}
+    if args.full:
+        prof = {op: ls.profile_read(op) for op in ops}
+        ls.profile_end()
     if world > 1:
         tt = torch.tensor([dt], dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -354,6 +393,9 @@ def main():
     free_b, total_b = torch.cuda.mem_get_info()       # everything of this solve is still resident
     dev_bytes = int(total_b - free_b)
     assert its == args.steps, (its, args.steps)
+    if args.dump_outputs:
+        dump_outputs(ls, res, args.dump_outputs, rank, world)
+        say(f"outputs of the timed region written to {args.dump_outputs}")
     n_u_local, n_p_local, nnz_F_local = pr.n_u, pr.n_p, pr.F.nnz
 
     # ---- like-for-like pairs of the CPU baseline: the same K iterations on the CPU samples' meshes, on the GPU
@@ -368,7 +410,8 @@ def main():
                 "ordering": ["natural", "multicolour"][args.ordering], "shards": args.subdomains}
 
     cpu_samples = []     # (mesh string, K, GPU pair)
-    if world == 1 and not args.no_cpu_baseline:
+    with_cpu = args.full and world == 1 and not args.no_cpu_baseline
+    if with_cpu:
         m1 = args.cpu_mesh or f"{nx},{ny}"
         for mesh_s, K in ((m1, args.cpu_steps), (args.cpu_mesh2, args.cpu_steps2)):
             if not mesh_s or K <= 0 or any(mesh_s == c[0] for c in cpu_samples):
@@ -379,7 +422,7 @@ def main():
                 cpu_samples.append((mesh_s, K, gpu_pair(ls, pr, cx, cy, K)))
     ls.close()
     del pr
-    if world == 1 and not args.no_cpu_baseline:
+    if with_cpu:
         for mesh_s, K in ((m1, args.cpu_steps), (args.cpu_mesh2, args.cpu_steps2)):
             if not mesh_s or K <= 0 or any(mesh_s == c[0] for c in cpu_samples):
                 continue
@@ -390,53 +433,66 @@ def main():
             del pr2
 
     conv = None
-    if args.converge > 0:
+    if args.full and args.converge > 0:
         conv = converged_solve(S, PT, P, dist, args, world, rank, local_rank, sync)
 
     if rank == 0:
         value = n_global * args.steps / dt
-        lu, lp = st["n_colors_u"] or st["n_levels_u"], st["n_colors_p"] or st["n_levels_p"]
-        names = {0: "spmv_blk_kernel<2,2>: SpMV with F (inner FGMRES), 2x2 node blocks",
-                 3: "spmv_stream_kernel<3,0>: SpMV with Mp (inner CG), pairs of entries per lane", 5: "spmv_stream_kernel<3,0>: SpMV with S (inner CG), pairs of entries per lane",
-                 20: (f"tri_blk_kernel: ILU(0)/SGS apply on F ({lu}+{lu} node-colour level launches "
-                      "of one apply)" if args.sync_free != 2 else
-                      "tri_blk_sf_kernel: ILU(0)/SGS apply on F (one launch per half, in-kernel hand-off)"),
-                 21: ("tri_ring_kernel: natural-order ILU(0)/SGS apply on the pressure mass matrix (gather + one one-workgroup launch "
-                      "per half through an LDS ring; what bounds it is the chain of dependent levels on ONE CU, not HBM)"
-                      if st.get("ring_applies", 0) > 0 else
-                      "tri_stream_sf_kernel: ILU(0)/SGS apply on the pressure block (one launch per half, in-kernel hand-off)"
-                      if args.sync_free >= 1 else
-                      f"tri_stream_kernel: ILU(0)/SGS apply on the pressure block ({lp}+{lp} level "
-                      "launches of one apply)")}
-        klass = {}
-        for op, (ms, cnt, by, ncalls, byf) in prof.items():
-            ach = (by / 1e9) / (ms / 1e3) if ms > 0 else 0.0
-            achf = (byf / 1e9) / (ms / 1e3) if ms > 0 else 0.0
-            klass[op] = dict(kernel=names[op], avg_ms=ms, launches_sampled=cnt, calls=ncalls,
-                             bytes_csr_algorithmic=by, bytes_format=byf,
-                             achieved_algorithmic=ach, achieved_format=achf,
-                             # fraction of the HBM peak from the bytes the storage format really streams: cannot exceed 1
-                             frac=achf / HBM_PEAK_GBS, frac_algorithmic=ach / HBM_PEAK_GBS,
-                             time_share=ncalls * ms / 1e3 / dt)   # share of the timed solve spent in this class
-        dom = max(klass, key=lambda o: klass[o]["time_share"])
-        D = klass[dom]
-        # HBM traffic of the dominant class from the committed PMC passes (rocprofv3 --pmc cannot run inside
-        # this process); only quoted when it was measured on this very workload
-        traffic, traffic_src, traffic_stale = None, None, None
-        import hashlib
-        ksrc = [os.path.join(ROOT, "navier_stokes_solver_amd", "csrc", f) for f in ("nsk_kernels.hip", "nsk_tri.cpp")]
-        sha_now = hashlib.sha256(b"".join(open(f, "rb").read() for f in ksrc)).hexdigest()
-        for pmc_name in ("r04_pmc_traffic_1200x400.json", "r03_pmc_traffic_1200x400.json", "r02_pmc_traffic_1200x400.json"):
-            pmc = os.path.join(ROOT, "profiles", pmc_name)
-            if (nx, ny, world, args.lx) == (1200, 400, 1, 2.2) and os.path.exists(pmc):
-                rec = json.load(open(pmc))
-                kk = rec.get("by_op", {})
-                if str(dom) in kk:
-                    traffic = kk[str(dom)]["traffic_bytes_corrected"]
-                    traffic_src = f"profiles/{pmc_name} (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes)"
-                    # the counters belong to the kernel sources they were taken from (sha recorded by scripts/pmc_traffic.py)
-                    traffic_stale = rec.get("kernel_sources_sha256") != sha_now
-                    break
+        full = {}         # the sampled kernel classes and the roofline of the dominant one (--full)
+        if args.full:
+            lu, lp = st["n_colors_u"] or st["n_levels_u"], st["n_colors_p"] or st["n_levels_p"]
+            names = {0: "spmv_blk_kernel<2,2>: SpMV with F (inner FGMRES), 2x2 node blocks",
+                     3: "spmv_stream_kernel<3,0>: SpMV with Mp (inner CG), pairs of entries per lane", 5: "spmv_stream_kernel<3,0>: SpMV with S (inner CG), pairs of entries per lane",
+                     20: (f"tri_blk_kernel: ILU(0)/SGS apply on F ({lu}+{lu} node-colour level launches "
+                          "of one apply)" if args.sync_free != 2 else
+                          "tri_blk_sf_kernel: ILU(0)/SGS apply on F (one launch per half, in-kernel hand-off)"),
+                     21: ("tri_ring_kernel: natural-order ILU(0)/SGS apply on the pressure mass matrix (gather + one one-workgroup launch "
+                          "per half through an LDS ring; what bounds it is the chain of dependent levels on ONE CU, not HBM)"
+                          if st.get("ring_applies", 0) > 0 else
+                          "tri_stream_sf_kernel: ILU(0)/SGS apply on the pressure block (one launch per half, in-kernel hand-off)"
+                          if args.sync_free >= 1 else
+                          f"tri_stream_kernel: ILU(0)/SGS apply on the pressure block ({lp}+{lp} level "
+                          "launches of one apply)")}
+            klass = {}
+            for op, (ms, cnt, by, ncalls, byf) in prof.items():
+                ach = (by / 1e9) / (ms / 1e3) if ms > 0 else 0.0
+                achf = (byf / 1e9) / (ms / 1e3) if ms > 0 else 0.0
+                klass[op] = dict(kernel=names[op], avg_ms=ms, launches_sampled=cnt, calls=ncalls,
+                                 bytes_csr_algorithmic=by, bytes_format=byf,
+                                 achieved_algorithmic=ach, achieved_format=achf,
+                                 # fraction of the HBM peak from the bytes the storage format really streams: cannot exceed 1
+                                 frac=achf / HBM_PEAK_GBS, frac_algorithmic=ach / HBM_PEAK_GBS,
+                                 time_share=ncalls * ms / 1e3 / dt)   # share of the timed solve spent in this class
+            dom = max(klass, key=lambda o: klass[o]["time_share"])
+            D = klass[dom]
+            # HBM traffic of the dominant class from the committed PMC passes (rocprofv3 --pmc cannot run inside
+            # this process); only quoted when it was measured on this very workload
+            traffic, traffic_src, traffic_stale = None, None, None
+            import hashlib
+            ksrc = [os.path.join(ROOT, "navier_stokes_solver_amd", "csrc", f) for f in ("nsk_kernels.hip", "nsk_tri.cpp")]
+            sha_now = hashlib.sha256(b"".join(open(f, "rb").read() for f in ksrc)).hexdigest()
+            for pmc_name in ("r04_pmc_traffic_1200x400.json", "r03_pmc_traffic_1200x400.json", "r02_pmc_traffic_1200x400.json"):
+                pmc = os.path.join(ROOT, "profiles", pmc_name)
+                if (nx, ny, world, args.lx) == (1200, 400, 1, 2.2) and os.path.exists(pmc):
+                    rec = json.load(open(pmc))
+                    kk = rec.get("by_op", {})
+                    if str(dom) in kk:
+                        traffic = kk[str(dom)]["traffic_bytes_corrected"]
+                        traffic_src = f"profiles/{pmc_name} (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes)"
+                        # the counters belong to the kernel sources they were taken from (sha recorded by scripts/pmc_traffic.py)
+                        traffic_stale = rec.get("kernel_sources_sha256") != sha_now
+                        break
+            full = {
+                "roofline": {
+                    "bound": "hbm", "kernel": D["kernel"], "time_share": D["time_share"],
+                    "achieved": D["achieved_algorithmic"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": D["achieved_algorithmic"] / HBM_PEAK_GBS, "traffic": traffic, "traffic_unit": "bytes per launch",
+                    "traffic_source": traffic_src, "traffic_stale": traffic_stale,
+                    "bytes_per_launch": D["bytes_csr_algorithmic"], "bytes_format": D["bytes_format"],
+                    "frac_format": D["frac"], "avg_ms": D["avg_ms"], "launches_sampled": D["launches_sampled"],
+                },
+                "kernel_classes": [klass[o] for o in sorted(klass)],
+            }
         label = f"{NAMES_S[args.solver]}+{NAMES_P[args.preconditioner]}, Re={args.reynolds:g}"
         out = {
             "metric": f"DoF*iters/s ({label}; first K={args.steps} outer iterations)",
@@ -465,15 +521,7 @@ def main():
                 "blas1_reductions": "16-byte loads (pairs)" if (args.blas1_pairs if args.blas1_pairs >= 0 else int(args.variant == 0))
                                     else "8-byte loads",
             },
-            "roofline": {
-                "bound": "hbm", "kernel": D["kernel"], "time_share": D["time_share"],
-                "achieved": D["achieved_algorithmic"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": D["achieved_algorithmic"] / HBM_PEAK_GBS, "traffic": traffic, "traffic_unit": "bytes per launch",
-                "traffic_source": traffic_src, "traffic_stale": traffic_stale,
-                "bytes_per_launch": D["bytes_csr_algorithmic"], "bytes_format": D["bytes_format"],
-                "frac_format": D["frac"], "avg_ms": D["avg_ms"], "launches_sampled": D["launches_sampled"],
-            },
-            "kernel_classes": [klass[o] for o in sorted(klass)],
+            **full,
             "phases": {
                 "generate_s": t_gen, "upload_s": t_upload, "setup_first_s": t_setup_first, "setup_numeric_s": t_setup,
                 "solve_s": dt, "spmv_GB": st["spmv_bytes"] / 1e9, "tri_GB": st["tri_bytes"] / 1e9,
@@ -489,7 +537,7 @@ def main():
         }
         if conv:
             out["converged_solve"] = conv
-        if world == 1 and not args.no_cpu_baseline:
+        if with_cpu:
             # first sample: the bench mesh itself (a few outer iterations: the oracle needs tens of seconds for one at
             # 1200x400); second sample: a mesh the oracle does a dozen iterations on
             cbs = []

@@ -8,9 +8,9 @@ repo=${GRAFT_REPO_ROOT:-$(pwd)}
 out=gpurun_out/prof_$tag
 mkdir -p $repo/$out
 cd $repo
-timeout -k 10 500 python3 bench.py --steps 20 --warmup 5 > $out/bench_line_K20.json 2> $out/bench_line_K20.err || echo "bench K20 failed"
+timeout -k 10 500 python3 bench.py --full --steps 20 --warmup 5 > $out/bench_line_K20.json 2> $out/bench_line_K20.err || echo "bench K20 failed"
 echo "bench K20 done"
-timeout -k 10 500 python3 bench.py --no-cpu-baseline > $out/bench_line_default_K58.json 2> $out/bench_line_default_K58.err || echo "bench K58 failed"
+timeout -k 10 500 python3 bench.py --full --no-cpu-baseline > $out/bench_line_default_K58.json 2> $out/bench_line_default_K58.err || echo "bench K58 failed"
 echo "bench K58 done"
 (cd /tmp && export TMPDIR=/tmp && timeout -k 10 500 rocprofv3 --kernel-trace --stats -d $repo/$out/kt --output-format csv -- python3 $repo/bench.py --steps 20 --warmup 5 --no-cpu-baseline > $repo/$out/bench_line_under_rocprof_K20.json 2> $repo/$out/rocprof_kt.err) || echo "kernel trace failed"
 rm -f $out/kt/*/*_kernel_trace.csv   # (70 MB; the statistics file is what is kept)

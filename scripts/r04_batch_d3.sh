@@ -5,7 +5,7 @@ O=gpurun_out/r04_d
 mkdir -p $O
 echo "== A/B: skewed vector allocations (channel phases of the nine Gram-Schmidt streams), K = 8"
 for w in 0 1; do
-  NSK_VEC_SKEW=$w timeout -k 10 500 python bench.py --steps 8 --warmup 3 --no-cpu-baseline > $O/ab_vec_skew_$w.json 2> /dev/null
+  NSK_VEC_SKEW=$w timeout -k 10 500 python bench.py --full --steps 8 --warmup 3 --no-cpu-baseline > $O/ab_vec_skew_$w.json 2> /dev/null
   python -c "
 import json; d = json.load(open('$O/ab_vec_skew_$w.json')); print('NSK_VEC_SKEW=$w ms_per_step', round(d['ms_per_step'], 1), 'blas1 GB', round(d['phases']['blas1_GB'],1))"
 done

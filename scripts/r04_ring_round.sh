@@ -11,8 +11,8 @@ echo "== tests"
 python -m pytest tests/test_partition.py -q -m gpu -k "failing_rank" 2>&1 | tail -4
 python -m pytest tests/test_gpu_parity.py -q -m gpu -k "vector_ops or dot_norm or one_launch or lds_ring or first_restart" 2>&1 | tail -4
 echo "== bench config 5, 8-byte BLAS-1 (round-3 arithmetic) and 16-byte BLAS-1"
-NSK_BLAS1_PAIRS=0 python bench.py --mesh 600,200 --variant 1 --preconditioner 0 --steps 40 --warmup 10 --no-cpu-baseline > $O/bench_config5_K40_blas1_scalar.json 2> $O/bench_config5_K40_blas1_scalar.err
-python bench.py --mesh 600,200 --variant 1 --preconditioner 0 --steps 40 --warmup 10 --no-cpu-baseline > $O/bench_config5_K40.json 2> $O/bench_config5_K40.err
+NSK_BLAS1_PAIRS=0 python bench.py --full --mesh 600,200 --variant 1 --preconditioner 0 --steps 40 --warmup 10 --no-cpu-baseline > $O/bench_config5_K40_blas1_scalar.json 2> $O/bench_config5_K40_blas1_scalar.err
+python bench.py --full --mesh 600,200 --variant 1 --preconditioner 0 --steps 40 --warmup 10 --no-cpu-baseline > $O/bench_config5_K40.json 2> $O/bench_config5_K40.err
 python - <<'PY'
 import json
 for f in ("bench_config5_K40_blas1_scalar", "bench_config5_K40"):
