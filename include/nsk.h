@@ -114,7 +114,7 @@ enum {
                                  (pressure), and restarted FGMRES(30) crawls on the indefinite spectrum (3 062
                                  against 580 outer iterations to 1e-10 at 60x20 in the CPU restatement).  Every parity test,
                                  the drivers and the bench headline keep +1 */
-  NSK_OPT_BLAS1_PAIRS = 15     /* dot products / norms / fused Gram-Schmidt sums read PAIRS of entries through 16-byte loads
+  NSK_OPT_BLAS1_PAIRS = 15,    /* dot products / norms / fused Gram-Schmidt sums read PAIRS of entries through 16-byte loads
                                  (6.3+ TB/s instead of 4.0-5.4 with 8 bytes per lane): 1 on, 0 off, -1 (default) on in the
                                  STATIONARY preconditioner variant, off in the unsteady one.  Another lane decomposition is
                                  another summation order, i.e. other last bits in every Krylov coefficient — harmless where
@@ -122,6 +122,18 @@ enum {
                                  restarted FGMRES sits on an edge: BASELINE config 5's first time step at 600x200 (-p 0) takes
                                  1 061 / 865 / 1 363 outer iterations with the 8-byte sums and 1 162 / no convergence in 100 000
                                  with the 16-byte ones (profiles/r04_cli_first_level_*) */
+  NSK_OPT_FACTOR_PRECISION = 16 /* storage precision of the ILU(0) / SGS factors' OFF-DIAGONAL values in the split halves the
+                                 multicolour kernels stream: 64 (default) double, as today; 32: rounded to float once per
+                                 set-up (the gather behind the numeric factorisation), and the double copies of those halves
+                                 are not kept.  What stays double: the numeric ILU(0) itself (it runs on the double
+                                 combined factor), the diagonal data (1/d, the 2x2 node diagonals), every vector and all
+                                 arithmetic (values are widened as they are loaded).  Applies to the velocity factor (2x2
+                                 node blocks) and the S / Mp factors; factors that take the natural-order ring, the level
+                                 walker, the single-workgroup path for tiny factors or the velocity AMG keep double —
+                                 nsk_tri_get_value_bytes reports what each holds.  A LABELLED DEVIATION from the reference,
+                                 whose Ifpack factors are double: the outer FGMRES stays double and checks the true residual,
+                                 the preconditioner alone is perturbed.  Other values: -61.  NSK_FACTOR_PRECISION=32 / 64 in
+                                 the environment overrides the option for every handle (A/B runs; other values ignored) */
 };
 
 typedef struct {
@@ -212,6 +224,10 @@ int nsk_tri_apply(nsk_handle h, int which, const double *b, double *x);
 int nsk_amg_info(nsk_handle h, int shard, int level, int64_t *rows, int64_t *nnz, double *lambda_max);
 /* ordering used by that triangular preconditioner: perm[new] = old (identity when natural) */
 int nsk_tri_get_perm(nsk_handle h, int which, int32_t *perm);
+/* bytes per stored off-diagonal value of that triangular preconditioner as its applies read them in the current set-up:
+ * 4 (NSK_OPT_FACTOR_PRECISION = 32 and the factor runs through the split-half kernels), 8 (double), 0 when the slot is no
+ * triangular factor (the velocity AMG of the stationary blockTriangular preconditioner) */
+int nsk_tri_get_value_bytes(nsk_handle h, int which, int32_t *bytes);
 /* preconditioner.vmult(dst, src), applied `calls` times on the same object; dst is in/out */
 int nsk_precond_vmult(nsk_handle h, const double *src_u, const double *src_p, double *dst_u, double *dst_p,
                       int calls);

@@ -72,6 +72,7 @@ struct NewtonDriver {
   bool stokes_signs = true;
   long total_its = 0;
   int assemblies = 0;
+  bool precision_reported = false;
 
   double assemble(bool first, bool stokes, double nu) {  // assemble_system(global_first_iter, computing_stokes)
     if (nu != nu_mp) { check(h, nsk_scale_values(h, NSK_BLK_MP, nu_mp / nu), "nsk_scale_values"); nu_mp = nu; }
@@ -85,6 +86,16 @@ struct NewtonDriver {
   int solve_system() {
     check(h, nsk_setup_preconditioner(h, preconditioner, NSK_UNSTEADY ? NSK_VARIANT_UNSTEADY : NSK_VARIANT_STATIONARY, 0.5),
           "nsk_setup_preconditioner");
+    // NSK_FACTOR_PRECISION=32 (read by the library): a LABELLED DEVIATION from the reference.  (On a line of its own: the
+    // Newton line in front of this call is still open.)
+    if (!precision_reported) {
+      precision_reported = true;
+      int32_t bu = 0, bp = 0;
+      check(h, nsk_tri_get_value_bytes(h, NSK_TRI_VELOCITY, &bu), "nsk_tri_get_value_bytes");
+      check(h, nsk_tri_get_value_bytes(h, NSK_TRI_PRESSURE, &bp), "nsk_tri_get_value_bytes");
+      if (bu == 4 || bp == 4)
+        std::printf("\n[nsk] NSK_FACTOR_PRECISION=32: ILU/SGS factors stored in fp32 (deviation from the reference)\n");
+    }
     int iters = 0;
     double res = 0.0;
     const int rc = nsk_solve_resident(h, solver_type, tolerance, NSK_UNSTEADY ? 100000 : 20000, &iters, &res);

@@ -136,6 +136,7 @@ struct nsk_handle_s {
   int velocity_amg = 1;     // NSK_OPT_VELOCITY_AMG
   int schur_sign = 1;       // NSK_OPT_SCHUR_SIGN: +1 the reference's S = B D^-1 Bt, -1 the negated (SIMPLE's) one
   int blas1_pairs = -1;     // NSK_OPT_BLAS1_PAIRS: -1 by variant (stationary on, unsteady off), 0, 1
+  int factor_precision = 64;   // NSK_OPT_FACTOR_PRECISION: 64, or 32 (single-precision off-diagonal values of the split halves)
   // pressure_mass does not depend on the state: its values only change when the caller hands over new ones, and a
   // factor of the same values under the same analysis is the same factor — it is kept (the natural-order ILU(0) of M_p
   // at 600x200 takes 0.47 s per set-up, one workgroup walking 4 001 levels: 8.5 s of config 5's first time level)
@@ -461,6 +462,14 @@ void H::setup(int type, int variant_, double alpha_) {
   tF.sync_free = sync_free_mode == 2;
   tMp.sf_fault = tS.sf_fault = (fault_inject & 1) != 0;
   tF.sf_fault = (fault_inject & 2) != 0;
+  // storage precision of the factors' off-diagonal values; NSK_FACTOR_PRECISION=32 / 64 overrides the option (A/B
+  // measurements with unchanged callers), any other value is ignored.  numeric() reallocates the halves when it changes.
+  static const int env_precision = [] {
+    const char *e = std::getenv("NSK_FACTOR_PRECISION");
+    const int v = e ? std::atoi(e) : 0;
+    return v == 32 || v == 64 ? v : 0;
+  }();
+  tF.want_f32 = tS.want_f32 = tMp.want_f32 = (env_precision ? env_precision : factor_precision) == 32;
   // working-vector layout of the blocked velocity factor: colour-ordered whenever it runs single-launch (its
   // per-level kernels only know the caller's order).  The scalar factors always solve on colour-ordered vectors.
   const int f_layout = (x_layout_mode != 0 && sync_free_mode == 2) ? 1 : 0;
@@ -563,7 +572,7 @@ void H::setup(int type, int variant_, double alpha_) {
       mp_factored_version = -1;
     }
     tMp.kind = kindP;
-    if (mp_factored_version != mp_values_version || mp_factored_kind != kindP) {
+    if (mp_factored_version != mp_values_version || mp_factored_kind != kindP || tMp.storage_stale()) {
       Phase ph("factorise Mp (device)");
       tMp.numeric(Mp.val.p);
       mp_factored_version = mp_values_version;
@@ -1099,6 +1108,10 @@ int nsk_set_option(nsk_handle h, int opt, double v) {
     case NSK_OPT_SCHUR_SIGN:
       if (v != 1.0 && v != -1.0) throw Error(-61, "NSK_OPT_SCHUR_SIGN: +1 or -1");
       h->schur_sign = (int)v;
+      break;
+    case NSK_OPT_FACTOR_PRECISION:
+      if (v != 64.0 && v != 32.0) throw Error(-61, "NSK_OPT_FACTOR_PRECISION: 64 or 32");
+      h->factor_precision = (int)v;
       break;
     case NSK_IOPT_TRI_X_LAYOUT:
       h->x_layout_mode = v == 0.0 ? 0 : 2;
@@ -1666,6 +1679,15 @@ int nsk_amg_info(nsk_handle h, int shard, int level, int64_t *rows, int64_t *nnz
     if (lambda_max) *lambda_max = h->amgF.level_lambda(shard, level);
   }
   return nl;
+  NSK_CATCH(h)
+}
+
+int nsk_tri_get_value_bytes(nsk_handle h, int which, int32_t *bytes) {
+  NSK_TRY(h)
+  if (h->prec_type < 0) throw Error(-46, "call nsk_setup_preconditioner first");
+  if (which == NSK_TRI_VELOCITY && h->amg_active) *bytes = 0;   // no triangular factor in this setup
+  else *bytes = (which == NSK_TRI_VELOCITY ? &h->tF : h->tP)->value_bytes();
+  return 0;
   NSK_CATCH(h)
 }
 

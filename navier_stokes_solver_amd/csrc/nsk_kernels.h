@@ -125,6 +125,7 @@ void vec_cg_fused_update(hipStream_t s, int n, const double *sc7, const double *
                          double *x, double *r);
 void scalar_sqrt(hipStream_t s, const double *in, double *out);                         // out = sqrt(|in|)
 void vec_gather(hipStream_t s, int n, const int *idx, const double *x, double *y);      // y[i] = x[idx[i]]
+void vec_gather(hipStream_t s, int n, const int *idx, const double *x, float *y);       // y[i] = (float) x[idx[i]] (rounded to nearest)
 void extract_diag(hipStream_t s, const CsrView &A, double *d, double *dinv);
 
 // ---- level-scheduled sparse triangular solves on a permuted CSR factor ----
@@ -154,27 +155,39 @@ void tri_upper_serial(hipStream_t s, const TriView &T, int kind, const int *lvl_
 // (i = perm[r]):
 //   lower: x[i] = (rhs[i] - sum) * (kind ? dinv[r] : 1)
 //   upper: x[i] = kind ? x[i] - sum*dinv[r] : (x[i] - sum)*dinv[r]
-struct TriHalf {
+// V: the type the off-diagonal values are STORED in — double, or float for factors stored in single precision
+// (NSK_OPT_FACTOR_PRECISION = 32).  The kernels widen what they load to double; vectors and arithmetic stay double.
+template <class V>
+struct TriHalfT {
   const int *rowptr;
   const int *col;
-  const double *val;
+  const V *val;
   const int4 *desc;  // per workgroup: {first row, end row, first nnz, end nnz} — one load instead of a chain
 };
+using TriHalf = TriHalfT<double>;
+using TriHalf32 = TriHalfT<float>;
 // run_nnz: the non-zero cap the row runs in M.desc were built with (512, 1024 or 2048)
 void tri_stream_level(hipStream_t s, const TriHalf &M, int b0, int b1, int lower, int kind, int run_nnz,
+                      const double *dinv, const int *perm, const double *rhs, double *w);
+void tri_stream_level(hipStream_t s, const TriHalf32 &M, int b0, int b1, int lower, int kind, int run_nnz,
                       const double *dinv, const int *perm, const double *rhs, double *w);
 
 // 2x2 node-block streamed level of a triangular solve (velocity block): node rows (two adjacent DoF rows) in node-colour order,
 // 2x2 blocks towards other nodes, and per node row intra = {l10, u01, 1/d0, 1/d1} for its own diagonal block.
 //   lower ILU: y0 = b0 - s0 ; y1 = b1 - s1 - l10 y0            lower SGS: y0 = (b0 - s0)/d0 ; y1 = (b1 - s1 - l10 y0)/d1
 //   upper ILU: x1 = (y1 - s1)/d1 ; x0 = (y0 - s0 - u01 x1)/d0  upper SGS: x1 = y1 - s1/d1 ; x0 = y0 - (s0 + u01 x1)/d0
-struct TriBlk {
+template <class V>
+struct TriBlkT {
   const int *rowptr;   // per node row, in blocks
   const int *col;      // caller-order node id of the block column
-  const double *val;   // 4 per block
+  const V *val;        // 4 per block (row-major; float: one 16-byte load per block)
   const int4 *desc;    // per workgroup: {first node row, end node row, first block, end block}
 };
+using TriBlk = TriBlkT<double>;
+using TriBlk32 = TriBlkT<float>;
 void tri_blk_level(hipStream_t s, const TriBlk &M, int b0, int b1, int lower, int kind, const double *intra,
+                   const int *permn, const double *rhs, double *x);
+void tri_blk_level(hipStream_t s, const TriBlk32 &M, int b0, int b1, int lower, int kind, const double *intra,
                    const int *permn, const double *rhs, double *x);
 void invert_node_diagonals(hipStream_t s, int n_nodes, double *intra);
 
@@ -192,22 +205,33 @@ void vec_fill_sentinel(hipStream_t s, int n, double *y);
 // before it (lower half) / after it (upper half), nearest first — scalars, or 2x2 blocks (4 doubles) for the node-block
 // kernel.  gmax = 1 (chain, cpl null): no groups.
 constexpr int kTriGroupMax = 3;
-struct TriChain {
+template <class V>
+struct TriChainT {
   int gmax;
   const unsigned char *chain;
-  const double *cpl;
+  const V *cpl;   // (the same value type as the factor's halves)
 };
+using TriChain = TriChainT<double>;
+using TriChain32 = TriChainT<float>;
 void tri_stream_syncfree(hipStream_t s, const TriHalf &M, int n_blocks, int lower, int kind, int run_nnz,
                          int wrong_order /* test hook */, const double *dinv, const int *perm, const double *rhs,
                          const double *own, double *w, double *reset /* gets the sentinel at the rows' positions */,
                          int *err, long long *dbg = nullptr /* diagnostics: 16 int64 per workgroup */,
                          TriChain chain = TriChain{1, nullptr, nullptr});
+// single-precision halves: built for the pair-wise loads only (NSK_TRI_WIDE=0 is ignored for them)
+void tri_stream_syncfree(hipStream_t s, const TriHalf32 &M, int n_blocks, int lower, int kind, int run_nnz,
+                         int wrong_order, const double *dinv, const int *perm, const double *rhs, const double *own,
+                         double *w, double *reset, int *err, long long *dbg, TriChain32 chain);
 void tri_blk_syncfree(hipStream_t s, const TriBlk &M, int n_blocks, int lower, int kind, int permx,
                       int wrong_order /* test hook */, const double *intra, const int *permn, const double *rhs,
                       const double *own, double *w, double *out, double *reset, int *err,
                       TriChain chain = TriChain{1, nullptr, nullptr});
+void tri_blk_syncfree(hipStream_t s, const TriBlk32 &M, int n_blocks, int lower, int kind, int permx, int wrong_order,
+                      const double *intra, const int *permn, const double *rhs, const double *own, double *w,
+                      double *out, double *reset, int *err, TriChain32 chain);
 // y[i] = idx[i] >= 0 ? x[idx[i]] : 0
 void vec_gather_or_zero(hipStream_t s, long n, const int *idx, const double *x, double *y);
+void vec_gather_or_zero(hipStream_t s, long n, const int *idx, const double *x, float *y);   // (rounded to float)
 
 
 // ---- natural-order ("caller's order") triangular solve through an LDS ring ----

@@ -10,6 +10,7 @@
 #include "nsk_kernels.h"
 
 #include <algorithm>
+#include <type_traits>
 
 namespace nsk {
 
@@ -359,8 +360,8 @@ __global__ __launch_bounds__(BLK) void spmv_blk_fused_kernel(BlkView A, const do
 
 // Streamed level of a triangular solve on split CSR halves (scalar factors): rows of the level are contiguous in the
 // permuted (colour) order, the solution vector w and the column ids stay in the caller's numbering (i = perm[r]).
-template <int LOWER, int KIND, int NNZ>
-__global__ __launch_bounds__(BLK) void tri_stream_kernel(TriHalf M, int b0, int nb, const double *__restrict__ dinv,
+template <class V, int LOWER, int KIND, int NNZ>
+__global__ __launch_bounds__(BLK) void tri_stream_kernel(TriHalfT<V> M, int b0, int nb, const double *__restrict__ dinv,
                                                          const int *__restrict__ perm,
                                                          const double *__restrict__ rhs, double *__restrict__ w) {
   __shared__ double prod[NNZ];
@@ -394,7 +395,7 @@ __global__ __launch_bounds__(BLK) void tri_stream_kernel(TriHalf M, int b0, int 
       const int k = k0 + (int)threadIdx.x + u * BLK;
       const bool ok = k < k1;
       c[u] = ok ? __builtin_nontemporal_load(M.col + k) : 0;
-      v[u] = ok ? __builtin_nontemporal_load(M.val + k) : 0.0;
+      v[u] = ok ? (double)__builtin_nontemporal_load(M.val + k) : 0.0;   // (float halves: widened here)
     }
 #pragma unroll
     for (int u = 0; u < U; ++u) g[u] = w[c[u]];
@@ -414,8 +415,30 @@ __global__ __launch_bounds__(BLK) void tri_stream_kernel(TriHalf M, int b0, int 
   }
 }
 
-template <int LOWER, int KIND>
-__global__ __launch_bounds__(BLK) void tri_blk_kernel(TriBlk M, int b0, int nb, const double *__restrict__ intra,
+// One 2x2 block of a triangular half as loaded: rows (a00, a01), (a10, a11).  double: two 16-byte loads; float (factor
+// stored in single precision): ONE 16-byte load, kept in four registers and widened where the products are formed.
+template <class V>
+struct Blk4;
+template <>
+struct Blk4<double> {
+  double2 r0, r1;
+  __device__ __forceinline__ void load(const double *v) {
+    r0 = *reinterpret_cast<const double2 *>(v);
+    r1 = *reinterpret_cast<const double2 *>(v + 2);
+  }
+  __device__ __forceinline__ double2 row0() const { return r0; }
+  __device__ __forceinline__ double2 row1() const { return r1; }
+};
+template <>
+struct Blk4<float> {
+  float4 q;
+  __device__ __forceinline__ void load(const float *v) { q = *reinterpret_cast<const float4 *>(v); }
+  __device__ __forceinline__ double2 row0() const { return make_double2((double)q.x, (double)q.y); }
+  __device__ __forceinline__ double2 row1() const { return make_double2((double)q.z, (double)q.w); }
+};
+
+template <class V, int LOWER, int KIND>
+__global__ __launch_bounds__(BLK) void tri_blk_kernel(TriBlkT<V> M, int b0, int nb, const double *__restrict__ intra,
                                                       const int *__restrict__ permn, const double *__restrict__ rhs,
                                                       double *__restrict__ x) {
   __shared__ double p0[kBlkMax];
@@ -441,15 +464,14 @@ __global__ __launch_bounds__(BLK) void tri_blk_kernel(TriBlk M, int b0, int nb, 
   {
     constexpr int U = kBlkMax / BLK;  // staged: see stream_products
     int m[U];
-    double2 a0[U], a1[U], xv[U];
+    Blk4<V> a[U];
+    double2 xv[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int k = k0 + (int)threadIdx.x + u * BLK;
       const bool ok = k < k1;
       m[u] = ok ? __builtin_nontemporal_load(M.col + k) : 0;
-      const double *v = M.val + 4 * (size_t)(ok ? k : k0);
-      a0[u] = *reinterpret_cast<const double2 *>(v);
-      a1[u] = *reinterpret_cast<const double2 *>(v + 2);
+      a[u].load(M.val + 4 * (size_t)(ok ? k : k0));
     }
 #pragma unroll
     for (int u = 0; u < U; ++u) xv[u] = *reinterpret_cast<const double2 *>(x + 2 * (size_t)m[u]);
@@ -457,8 +479,9 @@ __global__ __launch_bounds__(BLK) void tri_blk_kernel(TriBlk M, int b0, int nb, 
     for (int u = 0; u < U; ++u) {
       const int k = k0 + (int)threadIdx.x + u * BLK;
       if (k < k1) {
-        p0[k - k0] = a0[u].x * xv[u].x + a0[u].y * xv[u].y;
-        p1[k - k0] = a1[u].x * xv[u].x + a1[u].y * xv[u].y;
+        const double2 a0 = a[u].row0(), a1 = a[u].row1();
+        p0[k - k0] = a0.x * xv[u].x + a0.y * xv[u].y;
+        p1[k - k0] = a1.x * xv[u].x + a1.y * xv[u].y;
       }
     }
   }
@@ -522,14 +545,16 @@ __device__ __forceinline__ double sf_wait(const double *p, unsigned long long fi
 // the products land in the same LDS words, the row sums read them in the same order: same bits.  Round 4 also measured a
 // thread taking its 8 entries CONSECUTIVELY (two 16-byte index + four 16-byte value loads): ILU(S) apply 0.459 -> 0.637 ms
 // at 1200x400, lanes 32 / 64 bytes apart touch four times the lines per instruction; removed again.
-template <int LOWER, int KIND, int NNZ, int GMAX, int WIDE>
-__global__ __launch_bounds__(BLK, 8) void tri_stream_sf_kernel(TriHalf M, const int4 *__restrict__ desc, int nb, int wrong_order,
+// V = float (factor stored in single precision): a pair is one 8-byte value load, still lane-contiguous; values are widened
+// to double as they land in registers.  Only WIDE = 2 is built for it.
+template <class V, int LOWER, int KIND, int NNZ, int GMAX, int WIDE>
+__global__ __launch_bounds__(BLK, 8) void tri_stream_sf_kernel(TriHalfT<V> M, const int4 *__restrict__ desc, int nb, int wrong_order,
                                                             const double *__restrict__ dinv,
                                                             const int *__restrict__ perm,
                                                             const double *__restrict__ rhs,
                                                             const double *ownv, double *w, double *reset, int *err,
                                                             long long *dbg, const unsigned char *__restrict__ chain,
-                                                            const double *__restrict__ cpl) {
+                                                            const V *__restrict__ cpl) {
   __shared__ double prod[NNZ];
   __shared__ double xs[GMAX > 1 ? kStreamRows : 1];   // results of this run's rows (line groups: the next member reads them)
   // diagnostics (dbg != null; nsk_internal.h: nsk_debug_tri_trace): time stamps of workgroup blockIdx.x
@@ -556,7 +581,7 @@ __global__ __launch_bounds__(BLK, 8) void tri_stream_sf_kernel(TriHalf M, const 
     const bool any = k0 < k1;   // (uniform) false: rows without entries; every lane then reads valid stand-in words
     const int kz = any ? k0 : 0;
     const int *colp = any ? M.col : M.rowptr;
-    const double *valp = any ? M.val : w;
+    const V *valp = any ? M.val : reinterpret_cast<const V *>(w);   // (stand-in of the value type: never used)
     unsigned o[U];   // byte offset of the gathered entry (32 bits on top of the uniform base)
     unsigned open = 0;   // bit u: entry u still shows the sentinel
     const char *wb = reinterpret_cast<const char *>(w);
@@ -569,9 +594,9 @@ __global__ __launch_bounds__(BLK, 8) void tri_stream_sf_kernel(TriHalf M, const 
       if (WIDE == 2) {
         // pairs of consecutive entries, lanes on consecutive pairs: U / 2 index loads of 8 bytes + U / 2 value loads of 16
         typedef int vi2 __attribute__((ext_vector_type(2)));
-        typedef double vd2 __attribute__((ext_vector_type(2)));
+        typedef V vd2 __attribute__((ext_vector_type(2)));
         typedef vi2 vi2u __attribute__((aligned(4)));
-        typedef vd2 vd2u __attribute__((aligned(8)));
+        typedef vd2 vd2u __attribute__((aligned(sizeof(V))));
 #pragma unroll
         for (int c = 0; c < U / 2; ++c) {
           const int k = k0 + 2 * (tb + c * BLK), kk = (any && k < k1) ? k : kz;   // (the arrays end with spare entries)
@@ -602,8 +627,8 @@ __global__ __launch_bounds__(BLK, 8) void tri_stream_sf_kernel(TriHalf M, const 
         if (GMAX > 1) {   // position in the line group, counted from the member that is solved first in this half
           const int ch = chain[r];
           cq = LOWER ? (ch & 15) : (ch >> 4) - 1 - (ch & 15);
-          c0 = cpl[(size_t)r * (kTriGroupMax - 1)];
-          c1 = cpl[(size_t)r * (kTriGroupMax - 1) + 1];
+          c0 = (double)cpl[(size_t)r * (kTriGroupMax - 1)];
+          c1 = (double)cpl[(size_t)r * (kTriGroupMax - 1) + 1];
         }
       }
 #pragma unroll
@@ -688,15 +713,15 @@ __global__ __launch_bounds__(BLK, 8) void tri_stream_sf_kernel(TriHalf M, const 
 #ifndef NSK_BLK_SF_WG
 #define NSK_BLK_SF_WG 1   // (study builds: 7 asks the compiler for seven workgroups per CU — the upper half sits at 73 VGPRs)
 #endif
-template <int LOWER, int KIND, int PERMX, int GMAX>
-__global__ __launch_bounds__(BLK, GMAX == 1 ? NSK_BLK_SF_WG : 1) void tri_blk_sf_kernel(TriBlk M, int nb, int wrong_order,
+template <class V, int LOWER, int KIND, int PERMX, int GMAX>
+__global__ __launch_bounds__(BLK, GMAX == 1 ? NSK_BLK_SF_WG : 1) void tri_blk_sf_kernel(TriBlkT<V> M, int nb, int wrong_order,
                                                          const double *__restrict__ intra,
                                                          const int *__restrict__ permn,
                                                          const double *__restrict__ rhs,
                                                          const double *ownv, double *x,
                                                          double *__restrict__ out, double *reset, int *err,
                                                          const unsigned char *__restrict__ chain,
-                                                         const double *__restrict__ cpl) {
+                                                         const V *__restrict__ cpl) {
   __shared__ double p0[kBlkMax];
   __shared__ double p1[kBlkMax];
   __shared__ double2 xs[GMAX > 1 ? kStreamRows : 1];   // results of this run's node rows (line groups)
@@ -725,24 +750,23 @@ __global__ __launch_bounds__(BLK, GMAX == 1 ? NSK_BLK_SF_WG : 1) void tri_blk_sf
     if (GMAX > 1 && lane == 0) {
       const int ch = chain[r];
       cq = LOWER ? (ch & 15) : (ch >> 4) - 1 - (ch & 15);
-      const double *c = cpl + (size_t)r * (4 * (kTriGroupMax - 1));
-      if (cq >= 1) { ca0 = *reinterpret_cast<const double2 *>(c); ca1 = *reinterpret_cast<const double2 *>(c + 2); }
-      if (cq >= 2) { cb0 = *reinterpret_cast<const double2 *>(c + 4); cb1 = *reinterpret_cast<const double2 *>(c + 6); }
+      const V *c = cpl + (size_t)r * (4 * (kTriGroupMax - 1));
+      Blk4<V> cb;
+      if (cq >= 1) { cb.load(c); ca0 = cb.row0(); ca1 = cb.row1(); }
+      if (cq >= 2) { cb.load(c + 4); cb0 = cb.row0(); cb1 = cb.row1(); }
     }
   }
   {
     constexpr int U = kBlkMax / BLK;
     int m[U];
-    double2 a0[U], a1[U];
+    Blk4<V> a[U];
     unsigned long long g0[U], g1[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int k = k0 + (int)threadIdx.x + u * BLK;
       const bool ok = k < k1;
       m[u] = ok ? __builtin_nontemporal_load(M.col + k) : -1;
-      const double *v = M.val + 4 * (size_t)(ok ? k : k0);
-      a0[u] = *reinterpret_cast<const double2 *>(v);
-      a1[u] = *reinterpret_cast<const double2 *>(v + 2);
+      a[u].load(M.val + 4 * (size_t)(ok ? k : k0));
     }
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -756,8 +780,9 @@ __global__ __launch_bounds__(BLK, GMAX == 1 ? NSK_BLK_SF_WG : 1) void tri_blk_sf
       const int k = k0 + (int)threadIdx.x + u * BLK;
       if (k < k1) {
         const double xa = sf_wait(x + 2 * (size_t)m[u], g0[u], err), xb = sf_wait(x + 2 * (size_t)m[u] + 1, g1[u], err);
-        p0[k - k0] = a0[u].x * xa + a0[u].y * xb;
-        p1[k - k0] = a1[u].x * xa + a1[u].y * xb;
+        const double2 a0 = a[u].row0(), a1 = a[u].row1();
+        p0[k - k0] = a0.x * xa + a0.y * xb;
+        p1[k - k0] = a1.x * xa + a1.y * xb;
       }
     }
   }
@@ -1398,15 +1423,24 @@ void spmv2_stream(hipStream_t s, const CsrView &A, const double *xao, const doub
   hipLaunchKernelGGL((spmv2_stream_kernel<2>), dim3(nblk), dim3(BLK), 0, s, A, xao, xag, B, xbo, xbg, rowblk, y);
 }
 
-void tri_blk_level(hipStream_t s, const TriBlk &M, int b0, int b1, int lower, int kind, const double *intra,
-                   const int *permn, const double *rhs, double *x) {
+template <class V>
+static void tri_blk_level_t(hipStream_t s, const TriBlkT<V> &M, int b0, int b1, int lower, int kind, const double *intra,
+                            const int *permn, const double *rhs, double *x) {
   const int nb = b1 - b0;
   if (nb <= 0) return;
   const int grid = ((nb + 7) / 8) * 8;
-#define NSK_TB(L, K) hipLaunchKernelGGL((tri_blk_kernel<L, K>), dim3(grid), dim3(BLK), 0, s, M, b0, nb, intra, permn, rhs, x)
+#define NSK_TB(L, K) hipLaunchKernelGGL((tri_blk_kernel<V, L, K>), dim3(grid), dim3(BLK), 0, s, M, b0, nb, intra, permn, rhs, x)
   if (lower) { if (kind == 0) NSK_TB(1, 0); else NSK_TB(1, 1); }
   else { if (kind == 0) NSK_TB(0, 0); else NSK_TB(0, 1); }
 #undef NSK_TB
+}
+void tri_blk_level(hipStream_t s, const TriBlk &M, int b0, int b1, int lower, int kind, const double *intra,
+                   const int *permn, const double *rhs, double *x) {
+  tri_blk_level_t(s, M, b0, b1, lower, kind, intra, permn, rhs, x);
+}
+void tri_blk_level(hipStream_t s, const TriBlk32 &M, int b0, int b1, int lower, int kind, const double *intra,
+                   const int *permn, const double *rhs, double *x) {
+  tri_blk_level_t(s, M, b0, b1, lower, kind, intra, permn, rhs, x);
 }
 
 void spmv_blk_stream(hipStream_t s, const BlkView &A, int R, int C, const int *rowblk, int nblk, const double *xo,
@@ -1430,12 +1464,13 @@ void spmv_blk_fused22_21(hipStream_t s, const BlkView &A, const double *xao, con
     hipLaunchKernelGGL(spmv_blk_fused_kernel, dim3(nblk), dim3(BLK), 0, s, A, xao, xag, B, xbo, xbg, rowblk, y);
 }
 
-void tri_stream_level(hipStream_t s, const TriHalf &M, int b0, int b1, int lower, int kind, int run_nnz,
-                      const double *dinv, const int *perm, const double *rhs, double *w) {
+template <class V>
+static void tri_stream_level_t(hipStream_t s, const TriHalfT<V> &M, int b0, int b1, int lower, int kind, int run_nnz,
+                               const double *dinv, const int *perm, const double *rhs, double *w) {
   const int nb = b1 - b0;
   if (nb <= 0) return;
   const int grid = ((nb + 7) / 8) * 8;
-#define NSK_TS(L, K, N) hipLaunchKernelGGL((tri_stream_kernel<L, K, N>), dim3(grid), dim3(BLK), 0, s, M, b0, nb, dinv, perm, rhs, w)
+#define NSK_TS(L, K, N) hipLaunchKernelGGL((tri_stream_kernel<V, L, K, N>), dim3(grid), dim3(BLK), 0, s, M, b0, nb, dinv, perm, rhs, w)
 #define NSK_TSN(L, K)                                            \
   do {                                                           \
     if (run_nnz <= 512) NSK_TS(L, K, 512);                       \
@@ -1446,6 +1481,14 @@ void tri_stream_level(hipStream_t s, const TriHalf &M, int b0, int b1, int lower
   else { if (kind == 0) NSK_TSN(0, 0); else NSK_TSN(0, 1); }
 #undef NSK_TSN
 #undef NSK_TS
+}
+void tri_stream_level(hipStream_t s, const TriHalf &M, int b0, int b1, int lower, int kind, int run_nnz,
+                      const double *dinv, const int *perm, const double *rhs, double *w) {
+  tri_stream_level_t(s, M, b0, b1, lower, kind, run_nnz, dinv, perm, rhs, w);
+}
+void tri_stream_level(hipStream_t s, const TriHalf32 &M, int b0, int b1, int lower, int kind, int run_nnz,
+                      const double *dinv, const int *perm, const double *rhs, double *w) {
+  tri_stream_level_t(s, M, b0, b1, lower, kind, run_nnz, dinv, perm, rhs, w);
 }
 
 #define NSK_EW(n, ...)                                                                       \
@@ -1524,17 +1567,21 @@ void vec_fill_sentinel(hipStream_t s, int n, double *y) {
   unsigned long long *p = reinterpret_cast<unsigned long long *>(y);
   NSK_EW(n, [=] __device__(int i) { p[i] = kSentinel; });
 }
-void tri_stream_syncfree(hipStream_t s, const TriHalf &M, int nb, int lower, int kind, int run_nnz, int wrong_order,
-                         const double *dinv, const int *perm, const double *rhs, const double *own, double *w,
-                         double *reset, int *err, long long *dbg, TriChain ch) {
+template <class V>
+static void tri_stream_syncfree_t(hipStream_t s, const TriHalfT<V> &M, int nb, int lower, int kind, int run_nnz,
+                                  int wrong_order, const double *dinv, const int *perm, const double *rhs, const double *own,
+                                  double *w, double *reset, int *err, long long *dbg, TriChainT<V> ch) {
   if (nb <= 0) return;
   // pairs of consecutive entries per lane (ILU(S) apply 0.449 -> 0.422 ms at 1200x400, same bits); NSK_TRI_WIDE=0: one 4- /
-  // 8-byte load per entry, the kernels of rounds 1-3 (A/B measurements)
+  // 8-byte load per entry, the kernels of rounds 1-3 (A/B measurements).  Single-precision halves exist for the pairs only
+  // (half the instantiations, half the build time): NSK_TRI_WIDE=0 takes WIDE = 2 for them
   static const int wide = [] { const char *e = getenv("NSK_TRI_WIDE"); return e ? atoi(e) : 2; }();
-#define NSK_SF(L, K, N, G)                                                                                                  \
-  do {                                                                                                                      \
-    if (wide == 2) hipLaunchKernelGGL((tri_stream_sf_kernel<L, K, N, G, 2>), dim3(nb), dim3(BLK), 0, s, M, M.desc, nb, wrong_order, dinv, perm, rhs, own, w, reset, err, dbg, ch.chain, ch.cpl); \
-    else hipLaunchKernelGGL((tri_stream_sf_kernel<L, K, N, G, 0>), dim3(nb), dim3(BLK), 0, s, M, M.desc, nb, wrong_order, dinv, perm, rhs, own, w, reset, err, dbg, ch.chain, ch.cpl);          \
+#define NSK_SF_LAUNCH(W, L, K, N, G) hipLaunchKernelGGL((tri_stream_sf_kernel<V, L, K, N, G, W>), dim3(nb), dim3(BLK), 0, s, M, M.desc, nb, wrong_order, dinv, perm, rhs, own, w, reset, err, dbg, ch.chain, ch.cpl)
+#define NSK_SF(L, K, N, G)                                   \
+  do {                                                       \
+    if constexpr (std::is_same<V, float>::value) NSK_SF_LAUNCH(2, L, K, N, G); \
+    else if (wide == 2) NSK_SF_LAUNCH(2, L, K, N, G);        \
+    else NSK_SF_LAUNCH(0, L, K, N, G);                       \
   } while (0)
 #define NSK_SFG(L, K, N)                                   \
   do {                                                     \
@@ -1553,12 +1600,24 @@ void tri_stream_syncfree(hipStream_t s, const TriHalf &M, int nb, int lower, int
 #undef NSK_SFN
 #undef NSK_SFG
 #undef NSK_SF
+#undef NSK_SF_LAUNCH
 }
-void tri_blk_syncfree(hipStream_t s, const TriBlk &M, int nb, int lower, int kind, int permx, int wrong_order,
-                      const double *intra, const int *permn, const double *rhs, const double *own, double *w, double *out,
-                      double *reset, int *err, TriChain ch) {
+void tri_stream_syncfree(hipStream_t s, const TriHalf &M, int nb, int lower, int kind, int run_nnz, int wrong_order,
+                         const double *dinv, const int *perm, const double *rhs, const double *own, double *w,
+                         double *reset, int *err, long long *dbg, TriChain ch) {
+  tri_stream_syncfree_t(s, M, nb, lower, kind, run_nnz, wrong_order, dinv, perm, rhs, own, w, reset, err, dbg, ch);
+}
+void tri_stream_syncfree(hipStream_t s, const TriHalf32 &M, int nb, int lower, int kind, int run_nnz, int wrong_order,
+                         const double *dinv, const int *perm, const double *rhs, const double *own, double *w,
+                         double *reset, int *err, long long *dbg, TriChain32 ch) {
+  tri_stream_syncfree_t(s, M, nb, lower, kind, run_nnz, wrong_order, dinv, perm, rhs, own, w, reset, err, dbg, ch);
+}
+template <class V>
+static void tri_blk_syncfree_t(hipStream_t s, const TriBlkT<V> &M, int nb, int lower, int kind, int permx, int wrong_order,
+                               const double *intra, const int *permn, const double *rhs, const double *own, double *w,
+                               double *out, double *reset, int *err, TriChainT<V> ch) {
   if (nb <= 0) return;
-#define NSK_SB(L, K, P, G) hipLaunchKernelGGL((tri_blk_sf_kernel<L, K, P, G>), dim3(nb), dim3(BLK), 0, s, M, nb, wrong_order, intra, permn, rhs, own, w, out, reset, err, ch.chain, ch.cpl)
+#define NSK_SB(L, K, P, G) hipLaunchKernelGGL((tri_blk_sf_kernel<V, L, K, P, G>), dim3(nb), dim3(BLK), 0, s, M, nb, wrong_order, intra, permn, rhs, own, w, out, reset, err, ch.chain, ch.cpl)
 #define NSK_SBG(L, K, P)                                   \
   do {                                                     \
     if (ch.gmax <= 1) NSK_SB(L, K, P, 1);                  \
@@ -1575,18 +1634,32 @@ void tri_blk_syncfree(hipStream_t s, const TriBlk &M, int nb, int lower, int kin
 #undef NSK_SBG
 #undef NSK_SB
 }
+void tri_blk_syncfree(hipStream_t s, const TriBlk &M, int nb, int lower, int kind, int permx, int wrong_order,
+                      const double *intra, const int *permn, const double *rhs, const double *own, double *w, double *out,
+                      double *reset, int *err, TriChain ch) {
+  tri_blk_syncfree_t(s, M, nb, lower, kind, permx, wrong_order, intra, permn, rhs, own, w, out, reset, err, ch);
+}
+void tri_blk_syncfree(hipStream_t s, const TriBlk32 &M, int nb, int lower, int kind, int permx, int wrong_order,
+                      const double *intra, const int *permn, const double *rhs, const double *own, double *w, double *out,
+                      double *reset, int *err, TriChain32 ch) {
+  tri_blk_syncfree_t(s, M, nb, lower, kind, permx, wrong_order, intra, permn, rhs, own, w, out, reset, err, ch);
+}
+template <class T>
 __global__ __launch_bounds__(BLK) void gather_or_zero_kernel(long n, const int *__restrict__ idx,
-                                                            const double *__restrict__ x, double *__restrict__ y) {
+                                                            const double *__restrict__ x, T *__restrict__ y) {
   for (long i = (long)blockIdx.x * BLK + threadIdx.x; i < n; i += (long)gridDim.x * BLK) {
     const int k = idx[i];
-    y[i] = k >= 0 ? x[k] : 0.0;
+    y[i] = k >= 0 ? (T)x[k] : (T)0;
   }
 }
-void vec_gather_or_zero(hipStream_t s, long n, const int *idx, const double *x, double *y) {
+template <class T>
+static void vec_gather_or_zero_t(hipStream_t s, long n, const int *idx, const double *x, T *y) {
   if (n <= 0) return;
   const int grid = (int)std::min<long>(65535 * 8, (n + BLK * 4 - 1) / (BLK * 4));
-  hipLaunchKernelGGL(gather_or_zero_kernel, dim3(grid), dim3(BLK), 0, s, n, idx, x, y);
+  hipLaunchKernelGGL(gather_or_zero_kernel<T>, dim3(grid), dim3(BLK), 0, s, n, idx, x, y);
 }
+void vec_gather_or_zero(hipStream_t s, long n, const int *idx, const double *x, double *y) { vec_gather_or_zero_t(s, n, idx, x, y); }
+void vec_gather_or_zero(hipStream_t s, long n, const int *idx, const double *x, float *y) { vec_gather_or_zero_t(s, n, idx, x, y); }
 void invert_node_diagonals(hipStream_t s, int n_nodes, double *intra) {
   const int n = n_nodes;
   NSK_EW(n, [=] __device__(int i) {
@@ -1596,6 +1669,9 @@ void invert_node_diagonals(hipStream_t s, int n_nodes, double *intra) {
 }
 void vec_gather(hipStream_t s, int n, const int *idx, const double *x, double *y) {
   NSK_EW(n, [=] __device__(int i) { y[i] = x[idx[i]]; });
+}
+void vec_gather(hipStream_t s, int n, const int *idx, const double *x, float *y) {
+  NSK_EW(n, [=] __device__(int i) { y[i] = (float)x[idx[i]]; });   // round to nearest even: the factor's one rounding
 }
 void halo_pack(hipStream_t s, int n, const int *idx, const double *x, double *buf) { vec_gather(s, n, idx, x, buf); }
 void local_sum(hipStream_t s, int count, const LocalSumArgs &A, double *out) {

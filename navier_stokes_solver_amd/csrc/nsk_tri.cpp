@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <numeric>
+#include <type_traits>
 
 namespace nsk {
 
@@ -662,16 +663,14 @@ void TriSolve::analyze(Ctx *c, const Csr &A, int kind_, int ordering_, const std
       }
       Ldesc.upload(ld, s); Lsf.upload(lsf, s);
       Udesc.upload(ud, s); Usf.upload(usf, s);
-      Lval.alloc((size_t)nnzL);
-      Uval.alloc((size_t)nnzU);
       intra.alloc((size_t)nn * 4);
       if (grouped) {
         chain.upload(hchain, s);
         Lcpl_src.upload(lcs, s); Ucpl_src.upload(ucs, s);
-        Lcpl.alloc(lcs.size()); Ucpl.alloc(ucs.size());
       }
-      ctx->sync();
       block2_ready = true;
+      alloc_halves();
+      ctx->sync();
     }
   }
   if (!perm.empty() && !block2) {
@@ -783,18 +782,14 @@ void TriSolve::analyze(Ctx *c, const Csr &A, int kind_, int ordering_, const std
       }
       Ldesc.upload(ld, s); Lsf.upload(lsf, s);
       Udesc.upload(ud, s); Usf.upload(usf, s);
-      Lval.alloc((size_t)nnzL + 8);
-      Uval.alloc((size_t)nnzU + 8);
-      NSK_HIP(hipMemsetAsync(Lval.p + nnzL, 0, 8 * sizeof(double), s));
-      NSK_HIP(hipMemsetAsync(Uval.p + nnzU, 0, 8 * sizeof(double), s));
       dinv.alloc((size_t)n);
       if (grouped) {
         chain.upload(hchain, s);
         Lcpl_src.upload(lcs, s); Ucpl_src.upload(ucs, s);
-        Lcpl.alloc(lcs.size()); Ucpl.alloc(ucs.size());
       }
-      ctx->sync();
       stream_ready = true;
+      alloc_halves();
+      ctx->sync();
     }
   }
   tick("split factors, runs, uploads");
@@ -970,16 +965,50 @@ void TriSolve::analyze(Ctx *c, const Csr &A, int kind_, int ordering_, const std
 }
 
 
+void TriSolve::alloc_halves() {
+  // (spare zero entries behind the value arrays — scalar halves: the wide loads of the single-launch kernels take a lane's
+  //  pair of consecutive entries at once and may read past the array's last one; blocked halves: one block, which a run
+  //  without blocks at the end of the array reads and discards)
+  const size_t spare = stream_ready ? 8 : 4;
+  auto alloc = [&](auto &buf, int64_t count) {
+    using T = std::remove_reference_t<decltype(*buf.p)>;
+    buf.alloc((size_t)count + spare);
+    if (spare) NSK_HIP(hipMemsetAsync(buf.p + count, 0, spare * sizeof(T), ctx->stream));
+  };
+  f32 = want_f32;
+  if (!stream_ready && !block2_ready) return;
+  if (f32) {
+    Lval.release(); Uval.release(); Lcpl.release(); Ucpl.release();
+    alloc(Lval32, nnzL);
+    alloc(Uval32, nnzU);
+    if (grouped) { Lcpl32.alloc(Lcpl_src.n); Ucpl32.alloc(Ucpl_src.n); }
+  } else {
+    Lval32.release(); Uval32.release(); Lcpl32.release(); Ucpl32.release();
+    alloc(Lval, nnzL);
+    alloc(Uval, nnzU);
+    if (grouped) { Lcpl.alloc(Lcpl_src.n); Ucpl.alloc(Ucpl_src.n); }
+  }
+}
+
+bool TriSolve::halves_in_use() const {   // (the decisions of apply(), in its order)
+  const bool tiny = (double)nnz * 12.0 < tiny_bytes && !schedL.empty();
+  if (!use_stream || tiny || !(stream_ready || block2_ready)) return false;
+  return sync_free || !grouped;
+}
+
 double TriSolve::format_bytes() const {
+  // (values: 8 bytes each, 4 when the halves in use are single precision)
+  const double vb = value_bytes();
   if (stream_ready)   // CSR halves + per run: descriptor; per row: rowptr x2, perm x2, rhs, dinv, y (store + load), x (fill + store)
-    return 12.0 * (double)(nnzL + nnzU) + 16.0 * (double)(n_Lsf + n_Usf) + (8.0 + 8.0 + 8.0 + 8.0 + 16.0 + 16.0 + 16.0) * (double)n;
+    return (4.0 + vb) * (double)(nnzL + nnzU) + 16.0 * (double)(n_Lsf + n_Usf) + (8.0 + 8.0 + 8.0 + 8.0 + 16.0 + 16.0 + 16.0) * (double)n;
   if (block2_ready)   // 2x2 blocks with one int32 block column + per node row: descriptor share, intra, rhs, y, x
-    return 36.0 * (double)(nnzL + nnzU) / 4.0 + 8.0 * (double)(n / 2) + (32.0 + 4.0 + 48.0) * (double)(n / 2);
+    return (4.0 + 4.0 * vb) * (double)(nnzL + nnzU) / 4.0 + 8.0 * (double)(n / 2) + (32.0 + 4.0 + 48.0) * (double)(n / 2);
   return (double)apply_bytes();
 }
 
 void TriSolve::numeric(const double *a_val_dev) {
   hipStream_t s = ctx->stream;
+  if (storage_stale()) alloc_halves();   // the precision was changed since the analysis
   vec_gather(s, (int)nnz, srcpos.p, a_val_dev, val.p);
   if (kind == 0) {
     for (const Step &st : schedN) {
@@ -987,21 +1016,31 @@ void TriSolve::numeric(const double *a_val_dev) {
       else ilu0_factor_level(s, st.nrows, lvlL_rows.p + st.row_off, rowptr.p, diag.p, col.p, val.p, max_row_nnz);
     }
   }
+  if (block2_ready || stream_ready) {   // off-diagonal values of the halves (rounded to float here when f32)
+    if (f32) {
+      vec_gather(s, (int)nnzL, Lsrc.p, val.p, Lval32.p);
+      vec_gather(s, (int)nnzU, Usrc.p, val.p, Uval32.p);
+    } else {
+      vec_gather(s, (int)nnzL, Lsrc.p, val.p, Lval.p);
+      vec_gather(s, (int)nnzU, Usrc.p, val.p, Uval.p);
+    }
+  }
   if (block2_ready) {
-    vec_gather(s, (int)nnzL, Lsrc.p, val.p, Lval.p);
-    vec_gather(s, (int)nnzU, Usrc.p, val.p, Uval.p);
     vec_gather(s, 2 * n, intra_src.p, val.p, intra.p);   // per node: l10, u01, d0, d1
     invert_node_diagonals(s, n / 2, intra.p);            // d0, d1 -> 1/d0, 1/d1
   }
   if (stream_ready) {
-    vec_gather(s, (int)nnzL, Lsrc.p, val.p, Lval.p);
-    vec_gather(s, (int)nnzU, Usrc.p, val.p, Uval.p);
     vec_gather(s, n, diag.p, val.p, dinv.p);
     vec_recip(s, n, dinv.p, dinv.p);
   }
   if (grouped && (block2_ready || stream_ready)) {
-    vec_gather_or_zero(s, (long)Lcpl.n, Lcpl_src.p, val.p, Lcpl.p);
-    vec_gather_or_zero(s, (long)Ucpl.n, Ucpl_src.p, val.p, Ucpl.p);
+    if (f32) {
+      vec_gather_or_zero(s, (long)Lcpl32.n, Lcpl_src.p, val.p, Lcpl32.p);
+      vec_gather_or_zero(s, (long)Ucpl32.n, Ucpl_src.p, val.p, Ucpl32.p);
+    } else {
+      vec_gather_or_zero(s, (long)Lcpl.n, Lcpl_src.p, val.p, Lcpl.p);
+      vec_gather_or_zero(s, (long)Ucpl.n, Ucpl_src.p, val.p, Ucpl.p);
+    }
   }
   if (ring_ready)
     for (Ring *Rg : {&ringL, &ringU}) {
@@ -1023,22 +1062,29 @@ void TriSolve::apply(const double *b, double *x) {
       sf_err.alloc(1);
       NSK_HIP(hipMemsetAsync(sf_err.p, 0, sizeof(int), s));
     }
-    const TriHalf L{Lrp.p, Lcol.p, Lval.p, Lsf.p}, U{Urp.p, Ucol.p, Uval.p, Usf.p};
     // the lower half arms x for the upper half, the upper half re-arms y for the next call: no fill launches
     if (!sf_armed) { vec_fill_sentinel(s, n, y.p); sf_armed = true; }
-    const TriChain cl{gmax, chain.p, Lcpl.p}, cu{gmax, chain.p, Ucpl.p};
-    tri_stream_syncfree(s, L, n_Lsf, 1, kind, kStreamNnz, 0, dinv.p, d_perm.p, b, nullptr, y.p, x, sf_err.p, sf_dbg, cl);
-    tri_stream_syncfree(s, U, n_Usf, 0, kind, kStreamNnz, sf_fault ? 1 : 0, dinv.p, d_perm.p, nullptr, y.p, x, y.p, sf_err.p,
-                        sf_dbg ? sf_dbg + (size_t)n_Lsf * 16 : nullptr, cu);
+    auto run = [&](const auto &L, const auto &U, const auto &cl, const auto &cu) {
+      tri_stream_syncfree(s, L, n_Lsf, 1, kind, kStreamNnz, 0, dinv.p, d_perm.p, b, nullptr, y.p, x, sf_err.p, sf_dbg, cl);
+      tri_stream_syncfree(s, U, n_Usf, 0, kind, kStreamNnz, sf_fault ? 1 : 0, dinv.p, d_perm.p, nullptr, y.p, x, y.p, sf_err.p,
+                          sf_dbg ? sf_dbg + (size_t)n_Lsf * 16 : nullptr, cu);
+    };
+    if (f32) run(TriHalf32{Lrp.p, Lcol.p, Lval32.p, Lsf.p}, TriHalf32{Urp.p, Ucol.p, Uval32.p, Usf.p},
+                 TriChain32{gmax, chain.p, Lcpl32.p}, TriChain32{gmax, chain.p, Ucpl32.p});
+    else run(TriHalf{Lrp.p, Lcol.p, Lval.p, Lsf.p}, TriHalf{Urp.p, Ucol.p, Uval.p, Usf.p},
+             TriChain{gmax, chain.p, Lcpl.p}, TriChain{gmax, chain.p, Ucpl.p});
     ++ctx->st.tri_applies;
     ctx->st.tri_bytes += (double)apply_bytes();
     return;
   }
   if (stream_ready && use_stream && !tiny && !grouped) {   // (line groups: the per-colour kernels do not know them)
     // x doubles as the intermediate vector: rows not yet solved hold L^-1 b, solved rows hold the result
-    const TriHalf L{Lrp.p, Lcol.p, Lval.p, Ldesc.p}, U{Urp.p, Ucol.p, Uval.p, Udesc.p};
-    for (int c = 0; c < n_colors; ++c) tri_stream_level(s, L, LB[c], LB[c + 1], 1, kind, kStreamNnz, dinv.p, d_perm.p, b, x);
-    for (int c = n_colors - 1; c >= 0; --c) tri_stream_level(s, U, UB[c], UB[c + 1], 0, kind, kStreamNnz, dinv.p, d_perm.p, nullptr, x);
+    auto run = [&](const auto &L, const auto &U) {
+      for (int c = 0; c < n_colors; ++c) tri_stream_level(s, L, LB[c], LB[c + 1], 1, kind, kStreamNnz, dinv.p, d_perm.p, b, x);
+      for (int c = n_colors - 1; c >= 0; --c) tri_stream_level(s, U, UB[c], UB[c + 1], 0, kind, kStreamNnz, dinv.p, d_perm.p, nullptr, x);
+    };
+    if (f32) run(TriHalf32{Lrp.p, Lcol.p, Lval32.p, Ldesc.p}, TriHalf32{Urp.p, Ucol.p, Uval32.p, Udesc.p});
+    else run(TriHalf{Lrp.p, Lcol.p, Lval.p, Ldesc.p}, TriHalf{Urp.p, Ucol.p, Uval.p, Udesc.p});
     ++ctx->st.tri_applies;
     ctx->st.tri_bytes += (double)apply_bytes();
     return;
@@ -1051,16 +1097,20 @@ void TriSolve::apply(const double *b, double *x) {
     // lower half into y, upper half into x (xc); each half is ONE launch.  The lower half arms the upper half's
     // vector with the sentinel, the upper half re-arms y for the next call: no fill launches
     if (!sf_armed) { vec_fill_sentinel(s, n, y.p); sf_armed = true; }
-    const TriBlk L{Lrp.p, Lcol.p, Lval.p, Lsf.p}, U{Urp.p, Ucol.p, Uval.p, Usf.p};
-    const TriChain cl{gmax, chain.p, Lcpl.p}, cu{gmax, chain.p, Ucpl.p};
-    if (x_layout) {  // colour-ordered working vectors y, xc; the upper half also writes the caller-order result
-      if (xc.n != (size_t)n + 1) xc.alloc((size_t)n + 1);
-      tri_blk_syncfree(s, L, n_Lsf, 1, kind, 1, 0, intra.p, permn.p, b, nullptr, y.p, nullptr, xc.p, sf_err.p, cl);
-      tri_blk_syncfree(s, U, n_Usf, 0, kind, 1, sf_fault ? 1 : 0, intra.p, permn.p, nullptr, y.p, xc.p, x, y.p, sf_err.p, cu);
-    } else {
-      tri_blk_syncfree(s, L, n_Lsf, 1, kind, 0, 0, intra.p, permn.p, b, nullptr, y.p, nullptr, x, sf_err.p, cl);
-      tri_blk_syncfree(s, U, n_Usf, 0, kind, 0, sf_fault ? 1 : 0, intra.p, permn.p, nullptr, y.p, x, nullptr, y.p, sf_err.p, cu);
-    }
+    if (x_layout && xc.n != (size_t)n + 1) xc.alloc((size_t)n + 1);
+    auto run = [&](const auto &L, const auto &U, const auto &cl, const auto &cu) {
+      if (x_layout) {  // colour-ordered working vectors y, xc; the upper half also writes the caller-order result
+        tri_blk_syncfree(s, L, n_Lsf, 1, kind, 1, 0, intra.p, permn.p, b, nullptr, y.p, nullptr, xc.p, sf_err.p, cl);
+        tri_blk_syncfree(s, U, n_Usf, 0, kind, 1, sf_fault ? 1 : 0, intra.p, permn.p, nullptr, y.p, xc.p, x, y.p, sf_err.p, cu);
+      } else {
+        tri_blk_syncfree(s, L, n_Lsf, 1, kind, 0, 0, intra.p, permn.p, b, nullptr, y.p, nullptr, x, sf_err.p, cl);
+        tri_blk_syncfree(s, U, n_Usf, 0, kind, 0, sf_fault ? 1 : 0, intra.p, permn.p, nullptr, y.p, x, nullptr, y.p, sf_err.p, cu);
+      }
+    };
+    if (f32) run(TriBlk32{Lrp.p, Lcol.p, Lval32.p, Lsf.p}, TriBlk32{Urp.p, Ucol.p, Uval32.p, Usf.p},
+                 TriChain32{gmax, chain.p, Lcpl32.p}, TriChain32{gmax, chain.p, Ucpl32.p});
+    else run(TriBlk{Lrp.p, Lcol.p, Lval.p, Lsf.p}, TriBlk{Urp.p, Ucol.p, Uval.p, Usf.p},
+             TriChain{gmax, chain.p, Lcpl.p}, TriChain{gmax, chain.p, Ucpl.p});
     ++ctx->st.tri_applies;
     ctx->st.tri_bytes += (double)apply_bytes();
     return;
@@ -1068,9 +1118,12 @@ void TriSolve::apply(const double *b, double *x) {
   if (block2_ready && x_layout && use_stream && !tiny && !grouped)
     throw Error(-33, "the colour-ordered layout of the blocked factor needs the single-launch solves");
   if (block2_ready && use_stream && !tiny && !grouped) {
-    const TriBlk L{Lrp.p, Lcol.p, Lval.p, Ldesc.p}, U{Urp.p, Ucol.p, Uval.p, Udesc.p};
-    for (int c = 0; c < n_colors; ++c) tri_blk_level(s, L, LB[c], LB[c + 1], 1, kind, intra.p, permn.p, b, x);
-    for (int c = n_colors - 1; c >= 0; --c) tri_blk_level(s, U, UB[c], UB[c + 1], 0, kind, intra.p, permn.p, nullptr, x);
+    auto run = [&](const auto &L, const auto &U) {
+      for (int c = 0; c < n_colors; ++c) tri_blk_level(s, L, LB[c], LB[c + 1], 1, kind, intra.p, permn.p, b, x);
+      for (int c = n_colors - 1; c >= 0; --c) tri_blk_level(s, U, UB[c], UB[c + 1], 0, kind, intra.p, permn.p, nullptr, x);
+    };
+    if (f32) run(TriBlk32{Lrp.p, Lcol.p, Lval32.p, Ldesc.p}, TriBlk32{Urp.p, Ucol.p, Uval32.p, Udesc.p});
+    else run(TriBlk{Lrp.p, Lcol.p, Lval.p, Ldesc.p}, TriBlk{Urp.p, Ucol.p, Uval.p, Udesc.p});
     ++ctx->st.tri_applies;
     ctx->st.tri_bytes += (double)apply_bytes();
     return;

@@ -74,6 +74,12 @@ struct TriSolve {
   DBuf<int4> Lsf, Usf;     // the same runs in the dispatch order of the single-launch kernels
   int n_Lsf = 0, n_Usf = 0;
   DBuf<double> Lval, Uval, dinv;
+  // Single-precision storage of the off-diagonal values of the split halves (NSK_OPT_FACTOR_PRECISION = 32): Lval32 / Uval32
+  // (and Lcpl32 / Ucpl32) replace Lval / Uval (Lcpl / Ucpl), which are then not allocated.  The combined factor `val`, the
+  // diagonal data (dinv, intra) and every vector stay double; the one rounding is the gather in numeric().
+  bool want_f32 = false;   // what the next numeric() stores (set by the handle before it)
+  bool f32 = false;        // what the halves hold now
+  DBuf<float> Lval32, Uval32;
   std::vector<int> LB, UB;  // per colour: first workgroup of that colour in Lblk / Ublk (n_colors + 1)
   int64_t nnzL = 0, nnzU = 0;
   long long *sf_dbg = nullptr;   // diagnostics buffer of the next apply (16 int64 per workgroup), see nsk_debug_tri_trace
@@ -90,6 +96,7 @@ struct TriSolve {
   DBuf<unsigned char> chain;
   DBuf<int> Lcpl_src, Ucpl_src;
   DBuf<double> Lcpl, Ucpl;
+  DBuf<float> Lcpl32, Ucpl32;
 
   // natural ordering: the LDS-ring solve (nsk_kernels.h: tri_ring) when the factor qualifies
   struct Ring {
@@ -113,12 +120,21 @@ struct TriSolve {
   void analyze(Ctx *c, const Csr &A, int kind_, int ordering_, const std::vector<int> &sub_off,
                bool want_block2 = false, const double *xy = nullptr, int group = 1);
   void numeric(const double *a_val_dev);           // refresh values (+ factorise for ILU)
+  bool storage_stale() const { return (stream_ready || block2_ready) && f32 != want_f32; }   // numeric() would reallocate
+  // true when apply() goes through the split halves (single-launch or per-colour kernels), false when it takes the ring,
+  // the level walker or the single-workgroup path for tiny factors — which read the double factor `val`
+  bool halves_in_use() const;
+  // bytes per stored off-diagonal value of what apply() streams: 4 for single-precision halves in use, else 8
+  int value_bytes() const { return f32 && halves_in_use() ? 4 : 8; }
   void apply(const double *b, double *x);          // x = M^{-1} b, caller's ordering
   TriView view() const { return TriView{n, rowptr.p, diag.p, col.p, val.p, perm.empty() ? nullptr : d_perm.p}; }
   // 12 nnz_factor + 4 (rows + 1) * 2 + 16 rows
   size_t apply_bytes() const { return (size_t)12 * nnz + 8 * ((size_t)n + 1) + 16 * (size_t)n; }
   // bytes the storage format in use really streams per apply (values, indices, descriptors, vectors)
   double format_bytes() const;
+
+ private:
+  void alloc_halves();   // the value arrays of the split halves, in the precision want_f32 asks for
 };
 
 }  // namespace nsk

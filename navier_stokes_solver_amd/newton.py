@@ -20,6 +20,16 @@ N_MAX_ITERS = 15             # NSSolverStationary.cpp:653
 RESIDUAL_TOLERANCE = 1e-9    # :654
 
 
+def report_factor_precision(ls):
+    """After a handle's first preconditioner set-up: one line when a triangular factor holds fp32 values
+    (NSK_FACTOR_PRECISION=32, read by the library — a labelled deviation from the reference, include/nsk.h)."""
+    if getattr(ls, "_precision_reported", False):
+        return
+    ls._precision_reported = True
+    if ls.rank == 0 and 4 in (ls.tri_value_bytes(0), ls.tri_value_bytes(1)):
+        print("[nsk] NSK_FACTOR_PRECISION=32: ILU/SGS factors stored in fp32 (deviation from the reference)")
+
+
 class InletVelocity:
     """`InletVelocity::incrementVelocity` (NSSolverStationary.hpp:95-108): u = 0.1, +0.15 per call up to 1.0."""
 
@@ -215,6 +225,7 @@ class DeviceBackend:
     def solve(self):
         ls = self.ls
         ls.setup_preconditioner(self.prec, self.variant, self.alpha)        # a fresh preconditioner per solve_system()
+        report_factor_precision(ls)
         its, res, rc = ls.solve_resident(self.solver, self.tol, self.max_iter)
         if rc != 0:
             raise RuntimeError(f"solve_system: no convergence (status {rc}) after {its} iterations, residual {res:g}")
@@ -285,6 +296,7 @@ class SimplexBackend:
             self.delta_u, self.delta_p = x[:self.space.n_u], x[self.space.n_u:]
         else:
             self.ls.setup_preconditioner(self.prec, self.S.STATIONARY, self.alpha)     # a fresh preconditioner per solve_system()
+            report_factor_precision(self.ls)
             its, res, rc = self.ls.solve_resident(self.solver, self.tol, self.max_iter)
             if rc != 0:
                 raise RuntimeError(f"solve_system: no convergence (status {rc}) after {its} iterations, residual {res:g}")
@@ -406,6 +418,7 @@ class MultiRankSimplexBackend(SimplexBackend):
         def run(r):
             ls = self.handles[r]
             ls.setup_preconditioner(self.prec, self.S.STATIONARY, self.alpha)
+            report_factor_precision(ls)
             its, res, rc = ls.solve_resident(self.solver, self.tol, self.max_iter)
             return (its, res, rc) + ls.download_solution()
 
