@@ -28,6 +28,7 @@
  *   -10..-11 HIP runtime / out of device scalar slots      -20..-25 RCCL / in-process group transport (-25: a peer of the in-process group failed or left)
  *   -30..-32 triangular-solve analysis (missing diagonal, row too long)
  *   -40..-47 missing blocks, bad preconditioner / solver type, call order
+ *   -48 NSK_OPT_INNER_MATRIX_PRECISION = 32: a value of F, S or M_p is finite in fp64 but outside the range of fp32
  *   -50..-59 bad arguments of the hand-off calls           -60..-66 device assembly / Newton state
  *   -70 single-launch triangular solve gave up waiting AND the per-colour retry failed too (see NSK_OPT_TRI_SYNC_FREE)
  *   -80..-84 AMG set-up (operator too large for 32-bit indices, rows too wide, rounds / estimates that do not end)
@@ -122,7 +123,7 @@ enum {
                                  restarted FGMRES sits on an edge: BASELINE config 5's first time step at 600x200 (-p 0) takes
                                  1 061 / 865 / 1 363 outer iterations with the 8-byte sums and 1 162 / no convergence in 100 000
                                  with the 16-byte ones (profiles/r04_cli_first_level_*) */
-  NSK_OPT_FACTOR_PRECISION = 16 /* storage precision of the ILU(0) / SGS factors' OFF-DIAGONAL values in the split halves the
+  NSK_OPT_FACTOR_PRECISION = 16, /* storage precision of the ILU(0) / SGS factors' OFF-DIAGONAL values in the split halves the
                                  multicolour kernels stream: 64 (default) double, as today; 32: rounded to float once per
                                  set-up (the gather behind the numeric factorisation), and the double copies of those halves
                                  are not kept.  What stays double: the numeric ILU(0) itself (it runs on the double
@@ -134,6 +135,24 @@ enum {
                                  whose Ifpack factors are double: the outer FGMRES stays double and checks the true residual,
                                  the preconditioner alone is perturbed.  Other values: -61.  NSK_FACTOR_PRECISION=32 / 64 in
                                  the environment overrides the option for every handle (A/B runs; other values ignored) */
+  NSK_OPT_INNER_MATRIX_PRECISION = 17 /* storage precision of the matrix values the preconditioner's INNER solves multiply by:
+                                 the inner FGMRES on F and the inner CG on S (stationary aSIMPLE) or M_p (blockDiagonal,
+                                 blockTriangular).  64 (default): double, as today.  32: they read copies of F, S and M_p
+                                 rounded to float (F's 2x2 node-block copy, gathered from the double values; S and M_p
+                                 scalar), made at every set-up and made again before use whenever the values change
+                                 (nsk_update_values, nsk_scale_values, nsk_assemble) without one; a set-up that finds a
+                                 value finite in fp64 but outside fp32's range returns -48.  What stays double: vectors,
+                                 products, sums and the kernels' LDS partials (values are widened as they are loaded); the
+                                 outer J x (fused F | Bt block row, or its per-block SpMVs); B and Bt inside the aSIMPLE
+                                 apply; nsk_spmv, nsk_time_op ops 0-5 and nsk_get_block; the numeric ILU(0) and the Schur
+                                 SpGEMM, which read the double values.  Blocks whose SpMV takes no stream kernel
+                                 (NSK_OPT_STREAM_KERNELS = 0; F without its 2x2 copy, e.g. NSK_OPT_BSR_VELOCITY = 0) stay
+                                 double — nsk_inner_value_bytes reports what each inner solve reads.  A LABELLED DEVIATION
+                                 from the reference, whose inner solves multiply by the double matrices: every inner solve
+                                 stops at a loose tolerance and the outer FGMRES stays double and checks the true residual,
+                                 so only the preconditioner is perturbed.  Other values: -61.  NSK_INNER_MATRIX_PRECISION=32
+                                 / 64 in the environment overrides the option for every handle (A/B runs; other values
+                                 ignored).  Independent of NSK_OPT_FACTOR_PRECISION; the velocity AMG keeps double */
 };
 
 typedef struct {
@@ -228,6 +247,15 @@ int nsk_tri_get_perm(nsk_handle h, int which, int32_t *perm);
  * 4 (NSK_OPT_FACTOR_PRECISION = 32 and the factor runs through the split-half kernels), 8 (double), 0 when the slot is no
  * triangular factor (the velocity AMG of the stationary blockTriangular preconditioner) */
 int nsk_tri_get_value_bytes(nsk_handle h, int which, int32_t *bytes);
+/* bytes per matrix value the inner solves of the current set-up read for blk (NSK_BLK_F, NSK_BLK_S or NSK_BLK_MP): 4
+ * (NSK_OPT_INNER_MATRIX_PRECISION = 32 and the block's SpMV takes a stream kernel), 8 (double), 0 when this set-up runs
+ * no inner solve on that block (S under types 0 / 1, M_p under aSIMPLE, every block under the unsteady aSIMPLE); -62 for
+ * other blocks */
+int nsk_inner_value_bytes(nsk_handle h, int blk, int32_t *bytes);
+/* y = A x for blk = NSK_BLK_F, NSK_BLK_S or NSK_BLK_MP with exactly the values, kernel and row runs of the inner solves
+ * of the current set-up (same bits as nsk_spmv(.., add = 0) when they read double).  Conventions of nsk_spmv: owned x,
+ * ghosts imported, collective when nranks > 1 (the interior rows overlap the halo exchange as in the inner solves). */
+int nsk_inner_spmv(nsk_handle h, int blk, const double *x_owned, double *y);
 /* preconditioner.vmult(dst, src), applied `calls` times on the same object; dst is in/out */
 int nsk_precond_vmult(nsk_handle h, const double *src_u, const double *src_p, double *dst_u, double *dst_p,
                       int calls);
@@ -311,8 +339,10 @@ int nsk_reset_stats(nsk_handle h);
 
 /* Device-side timing of one operation repeated `reps` times between HIP events on the
  * library's stream: op 0..5 = SpMV of block op; 10 = jacobian vmult; 20/21 = velocity /
- * pressure triangular apply; 30 = dot; 31 = axpy; 32 = fused add_and_dot.
- * Returns average milliseconds per repetition and the algorithmic bytes of one repetition. */
+ * pressure triangular apply; 30 = dot; 31 = axpy; 32 = fused add_and_dot; 50 + blk (50, 53, 55) = the inner
+ * solves' SpMV of F, M_p, S (nsk_inner_spmv; needs a set-up).
+ * Returns average milliseconds per repetition and the algorithmic bytes of one repetition — for ops 50 + blk the bytes
+ * the stored format really moves (fp32 values: 4 bytes each). */
 int nsk_time_op(nsk_handle h, int op, int reps, double *avg_ms, double *bytes);
 
 /* HIP-event sampling of operation classes INSIDE the following solves: every launch of a sampled op
@@ -320,7 +350,10 @@ int nsk_time_op(nsk_handle h, int op, int reps, double *avg_ms, double *bytes);
  * is bracketed by events on the library's stream until max_samples are taken. */
 int nsk_profile_begin(nsk_handle h, int op, int max_samples);
 /* bytes_per_launch: algorithmic bytes (CSR); bytes_format: what the storage format the kernel streams
- * really holds (node-block copies are smaller than CSR) — roofline fractions from the latter cannot exceed 1 */
+ * really holds (node-block copies are smaller than CSR) — roofline fractions from the latter cannot exceed 1.
+ * With NSK_OPT_INNER_MATRIX_PRECISION = 32, bytes_format of F, S and M_p is the fp32 copy's: with the default fused
+ * J x every sampled F and S launch is an inner one; with NSK_OPT_FUSE_BLOCK_ROW = 0 the F samples mix the outer J x's
+ * double launches with the inner fp32 ones, and the figure then understates the outer ones. */
 int nsk_profile_read(nsk_handle h, int op, double *avg_ms, int *n_samples, double *bytes_per_launch,
                      int64_t *n_calls, double *bytes_format);
 int nsk_profile_end(nsk_handle h);

@@ -137,6 +137,7 @@ struct nsk_handle_s {
   int schur_sign = 1;       // NSK_OPT_SCHUR_SIGN: +1 the reference's S = B D^-1 Bt, -1 the negated (SIMPLE's) one
   int blas1_pairs = -1;     // NSK_OPT_BLAS1_PAIRS: -1 by variant (stationary on, unsteady off), 0, 1
   int factor_precision = 64;   // NSK_OPT_FACTOR_PRECISION: 64, or 32 (single-precision off-diagonal values of the split halves)
+  int inner_matrix_precision = 64;   // NSK_OPT_INNER_MATRIX_PRECISION: 64, or 32 (fp32 values of F, S, M_p in the inner solves)
   // pressure_mass does not depend on the state: its values only change when the caller hands over new ones, and a
   // factor of the same values under the same analysis is the same factor — it is kept (the natural-order ILU(0) of M_p
   // at 600x200 takes 0.47 s per set-up, one workgroup walking 4 001 levels: 8.5 s of config 5's first time level)
@@ -220,11 +221,32 @@ struct nsk_handle_s {
     pools_ready = true;
   }
   void halo(int space, const DVec &x) { ctx.comm.halo_exchange(sp[space], x, s()); }
-  void spmv_nohalo(Csr &A, const DVec &x, double *y, int mode = 0, const double *z = nullptr) {
+  // Does the current set-up run an inner solve on block b (FGMRES on F, CG on S or M_p)?
+  bool inner_solve_on(int b) const {
+    if (prec_type < 0) return false;
+    if (b == NSK_BLK_F) return prec_type != 2 || variant == 0;
+    if (b == NSK_BLK_MP) return prec_type != 2;
+    if (b == NSK_BLK_S) return prec_type == 2 && variant == 0;
+    return false;
+  }
+  // Bytes per value the inner solves' SpMV of A reads: 4 when A holds an fp32 copy for the path the current options
+  // select (F: the 2x2 stream kernel; S, M_p: the scalar stream kernel), else 8 (CSR-vector kernels, no copy).
+  int inner_width(const Csr &A) const {
+    if (A.inner32 == 1) return use_stream && use_bsr && A.blk_ok ? 4 : 8;
+    if (A.inner32 == 2) return use_stream && A.stream_ok && !(A.blk_ok && use_bsr) ? 4 : 8;
+    return 8;
+  }
+  // inner: the SpMV of an inner solve (spmv_halo), which reads the fp32 copy where inner_width says so (y = A x only)
+  void spmv_nohalo(Csr &A, const DVec &x, double *y, int mode = 0, const double *z = nullptr, bool inner = false) {
     const int op = (int)(&A - blk);
     EventSampler::Slot *smp = sampler.want(op);
     if (smp) (void)hipEventRecord(smp->e0[smp->used], s());
-    if (A.blk_ok && use_stream && use_bsr && mode == 0)
+    const bool f32 = inner && mode == 0 && inner_width(A) == 4;
+    if (f32 && A.inner32 == 1)
+      nsk::spmv_blk_stream(s(), A.blk_view32(), A.blk_rowblk.p, A.blk_nblk, x.own, x.ghost, y);
+    else if (f32)
+      nsk::spmv_stream(s(), A.view32(), A.rowblk.p, A.nblk, A.even_rows, x.own, x.ghost, y);
+    else if (A.blk_ok && use_stream && use_bsr && mode == 0)
       nsk::spmv_blk_stream(s(), A.blk_view(), A.blk_R, A.blk_C, A.blk_rowblk.p, A.blk_nblk, x.own, x.ghost, y);
     else if (A.stream_ok && use_stream)
       nsk::spmv_stream(s(), A.view(), A.rowblk.p, A.nblk, A.even_rows, x.own, x.ghost, y, mode, z);
@@ -238,18 +260,22 @@ struct nsk_handle_s {
   // lattice columns of the strip) are computed on a second stream while the halo exchange occupies the main one; the
   // boundary rows follow it.  Row-run plans are cut at the interior range (Csr::find_interior), so the three launches
   // are sub-ranges of the same plan.
+  // This is the SpMV of the preconditioner's inner solves (and of nsk_inner_spmv): where A holds an fp32 copy
+  // (NSK_OPT_INNER_MATRIX_PRECISION = 32) it reads that, converted again first when val has changed since.
   bool overlap_halo = true;   // NSK_IOPT_OVERLAP_HALO
   long overlapped_spmvs = 0;
   void spmv_halo(Csr &A, int space, const DVec &x, double *y) {
     const bool blocked = A.blk_ok && use_stream && use_bsr;
     const bool streamed = !blocked && A.stream_ok && use_stream;
+    const bool f32 = inner_width(A) == 4;
+    if (f32 && A.val32_version != A.values_version) A.refresh_f32(s(), false);   // (stream-ordered: no host sync)
     const int b0 = blocked ? A.blk_int_b0 : A.int_b0, b1 = blocked ? A.blk_int_b1 : A.int_b1;
     const int nb = blocked ? A.blk_nblk : A.nblk;
     EventSampler::Slot *smp = sampler.find((int)(&A - blk));
     const bool sampling = smp && smp->used < smp->cap;   // (a launch that is being timed stays one launch)
     if (!overlap_halo || ctx.comm.nranks <= 1 || !(blocked || streamed) || b1 <= b0 || sampling) {
       halo(space, x);
-      spmv_nohalo(A, x, y);
+      spmv_nohalo(A, x, y, 0, nullptr, true);
       return;
     }
     if (smp) ++smp->seen;
@@ -257,7 +283,9 @@ struct nsk_handle_s {
     ctx.ensure_stream2();
     auto part = [&](hipStream_t st, int c0, int c1) {
       if (c1 <= c0) return;
-      if (blocked) nsk::spmv_blk_stream(st, A.blk_view(), A.blk_R, A.blk_C, A.blk_rowblk.p + c0, c1 - c0, x.own, x.ghost, y);
+      if (blocked && f32) nsk::spmv_blk_stream(st, A.blk_view32(), A.blk_rowblk.p + c0, c1 - c0, x.own, x.ghost, y);
+      else if (blocked) nsk::spmv_blk_stream(st, A.blk_view(), A.blk_R, A.blk_C, A.blk_rowblk.p + c0, c1 - c0, x.own, x.ghost, y);
+      else if (f32) nsk::spmv_stream(st, A.view32(), A.rowblk.p + c0, c1 - c0, A.even_rows, x.own, x.ghost, y);
       else nsk::spmv_stream(st, A.view(), A.rowblk.p + c0, c1 - c0, A.even_rows, x.own, x.ghost, y, 0, nullptr);
     };
     NSK_HIP(hipEventRecord(ctx.ev_fork, s()));                 // x is complete here
@@ -551,6 +579,7 @@ void H::setup(int type, int variant_, double alpha_) {
     spgemm_bdbt_numeric(s(), B.view(), Dinv, Dinv + n_u(), Bt.view(), Btg.present ? Btg.view() : Bt.view(), S.rowptr.p,
                         S.col.p, S.val.p, S.n_rows, std::max(1, s_max_row));
     if (schur_sign < 0) vec_scale(s(), (int)S.nnz, sref(-1.0), S.val.p);   // opt-in deviation (nsk.h: NSK_OPT_SCHUR_SIGN)
+    ++S.values_version;
     if (!tS_ok || tS_key != key) {
       Phase ph("analyse S factor (host)");
       tS.analyze(&ctx, S, 0, tri_ordering, sub_offsets(1), false, xy(1), group_p);
@@ -581,7 +610,40 @@ void H::setup(int type, int variant_, double alpha_) {
     tP = &tMp;
     if (!tmp_p) tmp_p = pool_p.get(true);
   }
+  // fp32 values of the inner solves' matrices; NSK_INNER_MATRIX_PRECISION=32 / 64 overrides the option (A/B measurements
+  // with unchanged callers), any other value is ignored.  A block without an inner solve in this set-up, or whose SpMV
+  // would not take a stream kernel, keeps no copy (and 64 frees them all).
+  static const int env_inner = [] {
+    const char *e = std::getenv("NSK_INNER_MATRIX_PRECISION");
+    const int v = e ? std::atoi(e) : 0;
+    return v == 32 || v == 64 ? v : 0;
+  }();
+  const bool inner32 = (env_inner ? env_inner : inner_matrix_precision) == 32;
+  for (int b : {(int)NSK_BLK_F, (int)NSK_BLK_MP, (int)NSK_BLK_S}) {
+    Csr &A = blk[b];
+    int mode = 0;
+    if (inner32 && A.present && use_stream && inner_solve_on(b)) {
+      if (b == NSK_BLK_F) mode = use_bsr && A.blk_ok && A.blk_R == 2 && A.blk_C == 2 ? 1 : 0;
+      else mode = A.stream_ok && !A.blk_ok ? 2 : 0;
+    }
+    if (!mode) { A.release_f32(); continue; }
+    A.inner32 = mode;
+    A.refresh_f32(s(), true);
+  }
   ctx.sync();
+  for (int b : {(int)NSK_BLK_F, (int)NSK_BLK_MP, (int)NSK_BLK_S}) {
+    Csr &A = blk[b];
+    if (!A.inner32) continue;
+    unsigned over = 0;
+    NSK_HIP(hipMemcpy(&over, A.f32_overflow.p, sizeof(unsigned), hipMemcpyDeviceToHost));
+    if (over) {
+      for (Csr *c : {&blk[NSK_BLK_F], &blk[NSK_BLK_MP], &blk[NSK_BLK_S]}) c->release_f32();
+      prec_type = -1;   // no preconditioner: call nsk_setup_preconditioner again (e.g. with the option at 64)
+      static const char *names[6] = {"F (block 0,0)", "Bt", "B", "M_p (pressure mass)", "Bt ghost rows", "S (Schur approximation)"};
+      throw Error(-48, std::string("NSK_OPT_INNER_MATRIX_PRECISION = 32: ") + std::to_string(over) + " value(s) of " +
+                           names[b] + " are finite in fp64 but outside the range of fp32");
+    }
+  }
   setup_ms = wall_ms() - t0;
 }
 
@@ -1025,6 +1087,8 @@ int nsk_set_block_csr(nsk_handle h, int b, int n_rows, int n_cols, const int32_t
   A.col.upload(col, (size_t)nnz, h->s());
   A.val.upload(val, (size_t)nnz, h->s());
   if (b == NSK_BLK_MP) ++h->mp_values_version;
+  ++A.values_version;
+  A.release_f32();   // (a new pattern: the next set-up converts again)
   A.lpr = pick_lpr(nnz, n_rows);
   A.present = true;
   A.build_stream_plan(h->s());
@@ -1052,6 +1116,7 @@ int nsk_update_values(nsk_handle h, int b, const double *val) {
   Csr &A = h->blk[b];
   NSK_HIP(hipMemcpyAsync(A.val.p, val, sizeof(double) * (size_t)A.nnz, hipMemcpyHostToDevice, h->s()));
   if (b == NSK_BLK_MP) ++h->mp_values_version;
+  ++A.values_version;
   A.refresh_blocked(h->s());
   h->ctx.sync();
   return 0;
@@ -1112,6 +1177,10 @@ int nsk_set_option(nsk_handle h, int opt, double v) {
     case NSK_OPT_FACTOR_PRECISION:
       if (v != 64.0 && v != 32.0) throw Error(-61, "NSK_OPT_FACTOR_PRECISION: 64 or 32");
       h->factor_precision = (int)v;
+      break;
+    case NSK_OPT_INNER_MATRIX_PRECISION:
+      if (v != 64.0 && v != 32.0) throw Error(-61, "NSK_OPT_INNER_MATRIX_PRECISION: 64 or 32");
+      h->inner_matrix_precision = (int)v;
       break;
     case NSK_IOPT_TRI_X_LAYOUT:
       h->x_layout_mode = v == 0.0 ? 0 : 2;
@@ -1536,6 +1605,7 @@ int nsk_assemble(nsk_handle h, int stokes, double nu, double inv_dt, double p_ou
     simplex_assemble(s, SM, A.sol_u, A.sol_p, (A.have_old && inv_dt != 0.0) ? A.old_u : nullptr, nu, inv_dt, p_out, stokes != 0,
                      F.rowptr.p, F.col.p, F.val.p, h->ctx.slot(sl), inhomogeneous_bc ? A.bc.p : nullptr, h->rhs_b,
                      h->rhs_b + h->n_u(), h->x_b, h->x_b + h->n_u());
+    ++F.values_version;
     F.refresh_blocked(s);
     h->ctx.norm2(h->N(), h->rhs_b, sl + 1);
     const double nrm = h->ctx.read_slots(sl + 2, 1)[0];
@@ -1549,6 +1619,7 @@ int nsk_assemble(nsk_handle h, int stokes, double nu, double inv_dt, double p_ou
   asm_d0(s, M, A.cq.p, nu, inv_dt, stokes, h->ctx.slot(sl));
   h->ctx.comm.allreduce_sum(h->ctx.slot(sl), 1, s);   // the rank owning global DoF 0 wrote it, the others 0
   asm_F_rows(s, M, A.cq.p, nu, inv_dt, stokes, h->ctx.slot(sl), F.rowptr.p, F.val.p);
+  ++F.values_version;
   F.refresh_blocked(s);
   // the time term of the residual needs solution_old (nsk_state_save_old); without one it is left out
   asm_rhs_u(s, M, A.cq.p, nu, A.have_old ? inv_dt : 0.0, p_out, stokes, h->ctx.slot(sl),
@@ -1569,6 +1640,7 @@ int nsk_scale_values(nsk_handle h, int blk, double factor) {
   Csr &A = h->blk[blk];
   vec_scale(h->s(), (int)A.nnz, sref(factor), A.val.p);
   if (blk == NSK_BLK_MP) ++h->mp_values_version;
+  ++A.values_version;
   A.refresh_blocked(h->s());
   return 0;
   NSK_CATCH(h)
@@ -1601,6 +1673,7 @@ int nsk_time_assemble(nsk_handle h, double nu, double inv_dt, int reps, double *
     asm_cell_state(s, M, A.sol_u, A.sol_p, A.have_old ? A.old_u : nullptr, A.cq.p);
     asm_d0(s, M, A.cq.p, nu, inv_dt, 0, h->ctx.slot(sl));
     asm_F_rows(s, M, A.cq.p, nu, inv_dt, 0, h->ctx.slot(sl), F.rowptr.p, F.val.p);
+    ++F.values_version;
     F.refresh_blocked(s);
     asm_rhs_u(s, M, A.cq.p, nu, A.have_old ? inv_dt : 0.0, 1.0, 0, h->ctx.slot(sl), nullptr, h->rhs_b, h->x_b);
     asm_rhs_p(s, M, A.cq.p, 0, h->rhs_b + h->n_u());
@@ -1689,6 +1762,34 @@ int nsk_tri_get_value_bytes(nsk_handle h, int which, int32_t *bytes) {
   else *bytes = (which == NSK_TRI_VELOCITY ? &h->tF : h->tP)->value_bytes();
   return 0;
   NSK_CATCH(h)
+}
+
+int nsk_inner_value_bytes(nsk_handle h, int b, int32_t *bytes) {
+  NSK_TRY(h)
+  if (b != NSK_BLK_F && b != NSK_BLK_S && b != NSK_BLK_MP) throw Error(-62, "nsk_inner_value_bytes: F, S or M_p");
+  if (h->prec_type < 0) throw Error(-46, "call nsk_setup_preconditioner first");
+  *bytes = h->inner_solve_on(b) ? h->inner_width(h->blk[b]) : 0;
+  return 0;
+  NSK_CATCH(h)
+}
+
+int nsk_inner_spmv(nsk_handle h, int b, const double *x, double *y) {
+  NSK_TRY(h)
+  (void)hipSetDevice(h->ctx.device);
+  if (b != NSK_BLK_F && b != NSK_BLK_S && b != NSK_BLK_MP) throw Error(-62, "nsk_inner_spmv: F, S or M_p");
+  if (h->prec_type < 0) throw Error(-46, "call nsk_setup_preconditioner first");
+  if (!h->blk[b].present) throw Error(-62, "nsk_inner_spmv: block not set");
+  const int space = b == NSK_BLK_F ? 0 : 1;
+  VecPool &pool = space == 0 ? h->pool_u : h->pool_p;
+  double *xv = pool.get(true), *yv = pool.get(true);
+  NSK_HIP(hipMemcpyAsync(xv, x, sizeof(double) * (size_t)pool.n, hipMemcpyHostToDevice, h->s()));
+  h->spmv_halo(h->blk[b], space, pool.view(xv), yv);
+  NSK_HIP(hipMemcpyAsync(y, yv, sizeof(double) * (size_t)pool.n, hipMemcpyDeviceToHost, h->s()));
+  h->ctx.sync();
+  pool.put(xv);
+  pool.put(yv);
+  return 0;
+  NSK_CATCH_ABORT(h)
 }
 
 int nsk_tri_get_perm(nsk_handle h, int which, int32_t *perm) {
@@ -1841,7 +1942,8 @@ int nsk_profile_read(nsk_handle h, int op, double *avg_ms, int *n_samples, doubl
     else *bytes = 0.0;
   }
   if (bytes_format) {   // what the storage format in use really holds (<= the CSR figure for the node-block copies)
-    if (op >= 0 && op <= NSK_BLK_S) *bytes_format = h->blk[op].format_bytes(h->use_stream && h->use_bsr);
+    // (F, S, M_p with fp32 copies for the inner solves: the fp32 format — see nsk.h, NSK_OPT_INNER_MATRIX_PRECISION)
+    if (op >= 0 && op <= NSK_BLK_S) *bytes_format = h->blk[op].format_bytes(h->use_stream && h->use_bsr, h->inner_width(h->blk[op]));
     else if (op == 20) *bytes_format = h->tF.format_bytes();
     else if (op == 21 && h->tP) *bytes_format = h->tP->format_bytes();
     else *bytes_format = 0.0;
@@ -1884,6 +1986,20 @@ int nsk_time_op(nsk_handle h, int op, int reps, double *avg_ms, double *bytes) {
     const DVec xv = pc.view(xs);
     by = (double)A.spmv_bytes();
     f = [=, &A]() { h->halo(cs, xv); h->spmv_nohalo(A, xv, yb, 0); };
+    pc.put(xs);   // stays valid until the pool hands it out again (not during this call)
+  } else if (op == 50 + NSK_BLK_F || op == 50 + NSK_BLK_MP || op == 50 + NSK_BLK_S) {
+    // the inner solves' SpMV of that block, with the values and kernel they read (fp32 copy or double)
+    const int b = op - 50;
+    if (h->prec_type < 0) throw Error(-46, "call nsk_setup_preconditioner first");
+    if (!h->blk[b].present) throw Error(-62, "nsk_time_op: block not set");
+    Csr &A = h->blk[b];
+    const int cs = b == NSK_BLK_F ? 0 : 1;
+    VecPool &pc = cs == 0 ? h->pool_u : h->pool_p;
+    double *xs = pc.get(true);
+    vec_set(h->s(), pc.n, xs, 1.0);
+    const DVec xv = pc.view(xs);
+    by = A.format_bytes(h->use_stream && h->use_bsr, h->inner_width(A));
+    f = [=, &A]() { h->spmv_halo(A, cs, xv, yb); };
     pc.put(xs);   // stays valid until the pool hands it out again (not during this call)
   } else if (op == 10) {
     Csr &F = h->blk[NSK_BLK_F], &Bt = h->blk[NSK_BLK_BT], &B = h->blk[NSK_BLK_B];

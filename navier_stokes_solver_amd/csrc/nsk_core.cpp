@@ -659,6 +659,25 @@ void Csr::refresh_blocked(hipStream_t s) {
   if (blk_ok) vec_gather(s, (int)(blk_count * blk_R * blk_C), blk_src.p, val.p, blk_val.p);
 }
 
+void Csr::refresh_f32(hipStream_t s, bool count_overflow) {
+  if (!inner32) return;
+  if (count_overflow) {
+    if (!f32_overflow.p) f32_overflow.alloc(1);
+    NSK_HIP(hipMemsetAsync(f32_overflow.p, 0, sizeof(unsigned), s));
+  }
+  unsigned *ovf = count_overflow ? f32_overflow.p : nullptr;
+  if (inner32 == 1) {   // F: gathered straight from val into the 2x2 layout (every entry of val has one place there)
+    const size_t n = (size_t)blk_count * blk_R * blk_C;
+    if (blk_val32.n != n) blk_val32.alloc(n);
+    vec_gather(s, (int)n, blk_src.p, val.p, blk_val32.p);
+    if (ovf) vec_to_float(s, (int)nnz, val.p, nullptr, ovf);
+  } else {
+    if (val32.n != (size_t)nnz) val32.alloc((size_t)nnz);
+    vec_to_float(s, (int)nnz, val.p, val32.p, ovf);
+  }
+  val32_version = values_version;
+}
+
 double *VecPool::get(bool zero) {
   double *p;
   if (!free_list.empty()) {

@@ -150,11 +150,23 @@ struct Csr {  // device CSR block with host copy of the pattern
   void refresh_blocked(hipStream_t s);              // blk_val[k] = val[blk_src[k]] on the device
   BlkView blk_view() const { return BlkView{blk_rows, n_own_cols / blk_C, blk_rowptr.p, blk_col.p, blk_val.p}; }
   CsrView view() const { return CsrView{n_rows, n_own_cols, rowptr.p, col.p, val.p}; }
-  // bytes the storage format the SpMV kernels actually stream holds (values, indices, descriptors) + y + x once
-  double format_bytes(bool blocked) const {
+  // fp32 copies of the values for the preconditioner's inner solves (NSK_OPT_INNER_MATRIX_PRECISION = 32): inner32 = 1
+  // F's 2x2 copy in blk_val32, 2 the scalar values in val32, 0 none (the inner solves read val / blk_val).  Every write of
+  // val bumps values_version; a copy converted from an older version is converted again before its next use.
+  int inner32 = 0;
+  DBuf<float> blk_val32, val32;
+  long values_version = 0, val32_version = -1;
+  DBuf<unsigned> f32_overflow;   // values finite in fp64 and infinite in fp32, counted by the set-up's conversion
+  void release_f32() { inner32 = 0; blk_val32.release(); val32.release(); f32_overflow.release(); val32_version = -1; }
+  void refresh_f32(hipStream_t s, bool count_overflow);   // (re)convert the copy inner32 names from val, stream-ordered
+  BlkView32 blk_view32() const { return BlkView32{blk_rows, n_own_cols / blk_C, blk_rowptr.p, blk_col.p, blk_val32.p}; }
+  CsrView32 view32() const { return CsrView32{n_rows, n_own_cols, rowptr.p, col.p, val32.p}; }
+  // bytes the storage format the SpMV kernels actually stream holds (values, indices, descriptors) + y + x once;
+  // value_bytes 4: the fp32 copies
+  double format_bytes(bool blocked, int value_bytes = 8) const {
     if (blocked && blk_ok)
-      return (double)blk_count * (4.0 + 8.0 * blk_R * blk_C) + 4.0 * (blk_rows + 1.0) + 8.0 * n_rows + 8.0 * n_cols;
-    return (double)spmv_bytes();
+      return (double)blk_count * (4.0 + (double)value_bytes * blk_R * blk_C) + 4.0 * (blk_rows + 1.0) + 8.0 * n_rows + 8.0 * n_cols;
+    return (double)spmv_bytes() - (8.0 - value_bytes) * (double)nnz;
   }
   size_t spmv_bytes() const {  // 12 nnz + 4 (rows+1) + 8 rows + 8 cols
     return (size_t)12 * nnz + 4 * ((size_t)n_rows + 1) + 8 * (size_t)n_rows + 8 * (size_t)n_cols;

@@ -28,13 +28,18 @@ constexpr int kMaxReduceBlocks = 512;
 constexpr int kMaxReduceOut = 8;
 
 // ---- CSR SpMV: y = A x | y += A x.  Columns >= n_own read x_ghost[col - n_own]. ----
-struct CsrView {
+// V: the type the values are stored in — double, or float for the fp32 copies the preconditioner's inner solves read
+// (NSK_OPT_INNER_MATRIX_PRECISION = 32).  Kernels widen a float value to double as they load it; products and sums stay double.
+template <class V>
+struct CsrViewT {
   int n_rows;
   int n_own_cols;
   const int *rowptr;
   const int *col;
-  const double *val;
+  const V *val;
 };
+using CsrView = CsrViewT<double>;
+using CsrView32 = CsrViewT<float>;
 // mode 0: y = A x ; 1: y += A x ; 2: y = z - A x
 void spmv(hipStream_t s, const CsrView &A, int lanes_per_row, const double *x_own, const double *x_ghost, double *y,
           int mode, const double *z);
@@ -47,6 +52,10 @@ constexpr int kStreamNnz = 2048;
 constexpr int kStreamRows = 64;  // rows per run = workgroup size / lanes per row in the reduce phase
 void spmv_stream(hipStream_t s, const CsrView &A, const int *rowblk, int nblk, int even_rows, const double *x_own,
                  const double *x_ghost, double *y, int mode, const double *z);
+// fp32 values (y = A x only): the same plan, lane decomposition and summation order as the double launch, so the result
+// has the bits of the double kernel run on the values rounded to float beforehand
+void spmv_stream(hipStream_t s, const CsrView32 &A, const int *rowblk, int nblk, int even_rows, const double *x_own,
+                 const double *x_ghost, double *y);
 void spmv2_stream(hipStream_t s, const CsrView &A, const double *xa_own, const double *xa_ghost, const CsrView &B,
                   const double *xb_own, const double *xb_ghost, const int *rowblk, int nblk, double *y);
 
@@ -54,18 +63,24 @@ void spmv2_stream(hipStream_t s, const CsrView &A, const double *xa_own, const d
 // node share one sparsity pattern, so F is made of 2x2 blocks, (0,1) of 2x1 and (1,0) of 1x2 blocks.  One
 // int32 block-column id then serves R*C values: 9 B/nnz for F and 10 B/nnz for the off-diagonal blocks
 // instead of CSR's 12 B/nnz, and the x-gather is one (vector) load per block.
-struct BlkView {
+template <class V>
+struct BlkViewT {
   int n_brows;          // block rows
   int n_own_bcols;      // owned block columns (ghost block columns follow)
   const int *rowptr;    // per block row, in blocks
   const int *col;       // block-column id
-  const double *val;    // R*C per block, row-major
+  const V *val;         // R*C per block, row-major (float 2x2: one 16-byte load per block)
 };
+using BlkView = BlkViewT<double>;
+using BlkView32 = BlkViewT<float>;
 constexpr int kBlkMax = 1024;  // blocks per workgroup (both matrices together in the fused kernel)
 // y = A x on an R x C blocked matrix (R, C in {1,2}); rowblk = runs of block rows.
 // epi_d != null (R x C = 2 x 1 only): y = ((y .* epi_d) - A x) .* epi_dinv instead (aSIMPLE's velocity correction)
 void spmv_blk_stream(hipStream_t s, const BlkView &A, int R, int C, const int *rowblk, int nblk, const double *x_own,
                      const double *x_ghost, double *y, const double *epi_d = nullptr, const double *epi_dinv = nullptr);
+// fp32 2x2 blocks (F's copy for the inner solves), y = A x: same bits as the double launch on the rounded values
+void spmv_blk_stream(hipStream_t s, const BlkView32 &A, const int *rowblk, int nblk, const double *x_own,
+                     const double *x_ghost, double *y);
 // y = A xa + B xb with A 2x2-blocked and B 2x1-blocked over the same block rows (velocity block row of J)
 void spmv_blk_fused22_21(hipStream_t s, const BlkView &A, const double *xa_own, const double *xa_ghost,
                          const BlkView &B, const double *xb_own, const double *xb_ghost, const int *rowblk, int nblk,
@@ -126,6 +141,9 @@ void vec_cg_fused_update(hipStream_t s, int n, const double *sc7, const double *
 void scalar_sqrt(hipStream_t s, const double *in, double *out);                         // out = sqrt(|in|)
 void vec_gather(hipStream_t s, int n, const int *idx, const double *x, double *y);      // y[i] = x[idx[i]]
 void vec_gather(hipStream_t s, int n, const int *idx, const double *x, float *y);       // y[i] = (float) x[idx[i]] (rounded to nearest)
+// y[i] = (float) x[i] (rounded to nearest; y may be null); overflow != null: *overflow += the entries finite in double and
+// infinite in float
+void vec_to_float(hipStream_t s, int n, const double *x, float *y, unsigned *overflow);
 void extract_diag(hipStream_t s, const CsrView &A, double *d, double *dinv);
 
 // ---- level-scheduled sparse triangular solves on a permuted CSR factor ----

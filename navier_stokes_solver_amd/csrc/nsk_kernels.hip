@@ -95,8 +95,13 @@ constexpr int RG = 4;  // lanes cooperating on one row in the reduce phase
 // i.e. up to 8 x 2 serialised memory round trips per thread.  A run never exceeds kStreamNnz = 8 * BLK
 // entries, so the loops below are written with a fixed trip count in three stages — all index/value loads,
 // then all gathers, then the LDS stores — which keeps 16 + 8 loads in flight per thread.
-template <int VEC>
-__device__ __forceinline__ void stream_products(const int *__restrict__ col, const double *__restrict__ val, int k0,
+// V = float (the fp32 copies of the inner solves' matrices): the same loads at half the width — a pair is one 8-byte load
+// (4-byte aligned for VEC == 3, aligned for VEC == 2) — widened to double as they land; products and LDS stay double.
+__device__ __forceinline__ double2 widen2(double2 v) { return v; }
+__device__ __forceinline__ double2 widen2(float2 v) { return make_double2((double)v.x, (double)v.y); }
+
+template <class V, int VEC>
+__device__ __forceinline__ void stream_products(const int *__restrict__ col, const V *__restrict__ val, int k0,
                                                 int k1, int n_own, const double *__restrict__ xo,
                                                 const double *__restrict__ xg, double *prod) {
   if (VEC == 3) {
@@ -108,8 +113,9 @@ __device__ __forceinline__ void stream_products(const int *__restrict__ col, con
     constexpr int U = kStreamNnz / (2 * BLK);
     typedef int vi2 __attribute__((ext_vector_type(2)));
     typedef double vd2 __attribute__((ext_vector_type(2)));
+    typedef V vv2 __attribute__((ext_vector_type(2)));
     typedef vi2 vi2u __attribute__((aligned(4)));
-    typedef vd2 vd2u __attribute__((aligned(8)));
+    typedef vv2 vd2u __attribute__((aligned(sizeof(V))));
     int c0[U], c1[U];
     double v0[U], v1[U], x0[U], x1[U];
 #pragma unroll
@@ -117,11 +123,11 @@ __device__ __forceinline__ void stream_products(const int *__restrict__ col, con
       const int k = k0 + 2 * ((int)threadIdx.x + u * BLK);
       if (k + 1 < k1) {
         const vi2 ci = *reinterpret_cast<const vi2u *>(col + k);
-        const vd2 vi = *reinterpret_cast<const vd2u *>(val + k);
-        c0[u] = ci[0]; c1[u] = ci[1]; v0[u] = vi[0]; v1[u] = vi[1];
+        const vv2 vi = *reinterpret_cast<const vd2u *>(val + k);
+        c0[u] = ci[0]; c1[u] = ci[1]; v0[u] = (double)vi[0]; v1[u] = (double)vi[1];
       } else {   // the run's odd last entry (nothing may be read behind it), or nothing
         const bool ok = k < k1;
-        c0[u] = ok ? col[k] : 0; v0[u] = ok ? val[k] : 0.0; c1[u] = 0; v1[u] = 0.0;
+        c0[u] = ok ? col[k] : 0; v0[u] = ok ? (double)val[k] : 0.0; c1[u] = 0; v1[u] = 0.0;
       }
     }
 #pragma unroll
@@ -137,6 +143,7 @@ __device__ __forceinline__ void stream_products(const int *__restrict__ col, con
     }
   } else if (VEC == 2) {
     constexpr int U = kStreamNnz / (2 * BLK);
+    typedef typename std::conditional<std::is_same<V, double>::value, double2, float2>::type V2;
     int2 c[U];
     double2 v[U];
 #pragma unroll
@@ -144,7 +151,7 @@ __device__ __forceinline__ void stream_products(const int *__restrict__ col, con
       const int k = k0 + 2 * ((int)threadIdx.x + u * BLK);
       const bool ok = k < k1;
       c[u] = ok ? *reinterpret_cast<const int2 *>(col + k) : make_int2(0, 0);
-      v[u] = ok ? *reinterpret_cast<const double2 *>(val + k) : make_double2(0.0, 0.0);
+      v[u] = ok ? widen2(*reinterpret_cast<const V2 *>(val + k)) : make_double2(0.0, 0.0);
     }
     double x0[U], x1[U];
 #pragma unroll
@@ -166,7 +173,7 @@ __device__ __forceinline__ void stream_products(const int *__restrict__ col, con
       const int k = k0 + (int)threadIdx.x + u * BLK;
       const bool ok = k < k1;
       c[u] = ok ? col[k] : 0;
-      v[u] = ok ? val[k] : 0.0;
+      v[u] = ok ? (double)val[k] : 0.0;
     }
 #pragma unroll
     for (int u = 0; u < U; ++u) xv[u] = *(c[u] < n_own ? xo + c[u] : xg + (c[u] - n_own));
@@ -196,8 +203,8 @@ __device__ __forceinline__ double row_sum_lds(const double *prod, int b, int e, 
 // A run holds at most kStreamRows = BLK/RG rows, so the reduce phase is ONE pass: lane group t/RG owns
 // row r0 + t/RG, and its row bounds (and, in the triangular kernels, perm / rhs / diagonal) are
 // loaded BEFORE the streaming phase so their latency hides behind it.
-template <int VEC, int MODE>
-__global__ __launch_bounds__(BLK) void spmv_stream_kernel(CsrView A, const int *__restrict__ rowblk,
+template <class V, int VEC, int MODE>
+__global__ __launch_bounds__(BLK) void spmv_stream_kernel(CsrViewT<V> A, const int *__restrict__ rowblk,
                                                           const double *__restrict__ xo,
                                                           const double *__restrict__ xg, double *__restrict__ y,
                                                           const double *__restrict__ z) {
@@ -214,7 +221,7 @@ __global__ __launch_bounds__(BLK) void spmv_stream_kernel(CsrView A, const int *
     if (MODE == 1) zv = z ? z[r] : y[r];
     if (MODE == 2) zv = z[r];
   }
-  stream_products<VEC>(A.col, A.val, k0, k1, A.n_own_cols, xo, xg, prod);
+  stream_products<V, VEC>(A.col, A.val, k0, k1, A.n_own_cols, xo, xg, prod);
   __syncthreads();
   const double sum = row_sum_lds(prod, jb, je, lane);
   if (have && lane == 0) {
@@ -241,9 +248,9 @@ __global__ __launch_bounds__(BLK) void spmv2_stream_kernel(CsrView A, const doub
     ab = A.rowptr[r] - a0; ae = A.rowptr[r + 1] - a0;
     bb = B.rowptr[r] - b0; be = B.rowptr[r + 1] - b0;
   }
-  stream_products<VECA>(A.col, A.val, a0, a1, A.n_own_cols, xao, xag, prod);
+  stream_products<double, VECA>(A.col, A.val, a0, a1, A.n_own_cols, xao, xag, prod);
   double *prodB = prod + (a1 - a0);
-  stream_products<1>(B.col, B.val, b0, b1, B.n_own_cols, xbo, xbg, prodB);
+  stream_products<double, 1>(B.col, B.val, b0, b1, B.n_own_cols, xbo, xbg, prodB);
   __syncthreads();
   double sum = 0.0;
   for (int j = ab + lane; j < ae; j += RG) sum += prod[j];
@@ -253,8 +260,9 @@ __global__ __launch_bounds__(BLK) void spmv2_stream_kernel(CsrView A, const doub
 }
 
 // ------------------------------------------------------------------ blocked SpMV (R x C dense blocks)
-template <int R, int C>
-__device__ __forceinline__ void blk_products(const BlkView &A, int k0, int k1, const double *__restrict__ xo,
+// V = float (2 x 2 only: F's fp32 copy for the inner solves): a block is ONE 16-byte load, widened to double as it lands
+template <class V, int R, int C>
+__device__ __forceinline__ void blk_products(const BlkViewT<V> &A, int k0, int k1, const double *__restrict__ xo,
                                              const double *__restrict__ xg, double *p0, double *p1) {
   constexpr int U = kBlkMax / BLK;  // staged like stream_products: loads, gathers, LDS stores
   int m[U];
@@ -265,10 +273,16 @@ __device__ __forceinline__ void blk_products(const BlkView &A, int k0, int k1, c
     const int k = k0 + (int)threadIdx.x + u * BLK;
     const bool ok = k < k1;
     m[u] = ok ? __builtin_nontemporal_load(A.col + k) : 0;
-    const double *v = A.val + (size_t)(R * C) * (ok ? k : k0);
-    if (R * C == 4) { a0[u] = *reinterpret_cast<const double2 *>(v); a1[u] = *reinterpret_cast<const double2 *>(v + 2); }
-    else if (R * C == 2) { a0[u] = *reinterpret_cast<const double2 *>(v); a1[u] = make_double2(0.0, 0.0); }
-    else { a0[u] = make_double2(v[0], 0.0); a1[u] = make_double2(0.0, 0.0); }
+    const V *v = A.val + (size_t)(R * C) * (ok ? k : k0);
+    if constexpr (std::is_same<V, float>::value) {
+      static_assert(R == 2 && C == 2, "fp32 values: 2 x 2 blocks only");
+      const float4 q = *reinterpret_cast<const float4 *>(v);
+      a0[u] = make_double2((double)q.x, (double)q.y); a1[u] = make_double2((double)q.z, (double)q.w);
+    } else {
+      if (R * C == 4) { a0[u] = *reinterpret_cast<const double2 *>(v); a1[u] = *reinterpret_cast<const double2 *>(v + 2); }
+      else if (R * C == 2) { a0[u] = *reinterpret_cast<const double2 *>(v); a1[u] = make_double2(0.0, 0.0); }
+      else { a0[u] = make_double2(v[0], 0.0); a1[u] = make_double2(0.0, 0.0); }
+    }
   }
 #pragma unroll
   for (int u = 0; u < U; ++u) {
@@ -299,8 +313,8 @@ __device__ __forceinline__ void blk_products(const BlkView &A, int k0, int k1, c
 
 // EPI = 1 (aSIMPLE's velocity correction, NSSolver.hpp:343-349, in the kernel's epilogue instead of two more passes
 // over the vector): y = ((y .* d) - A x) .* dinv, with the products rounded one by one like the separate vector calls.
-template <int R, int C, int EPI>
-__global__ __launch_bounds__(BLK) void spmv_blk_kernel(BlkView A, const int *__restrict__ rowblk,
+template <class V, int R, int C, int EPI>
+__global__ __launch_bounds__(BLK) void spmv_blk_kernel(BlkViewT<V> A, const int *__restrict__ rowblk,
                                                        const double *__restrict__ xo, const double *__restrict__ xg,
                                                        double *__restrict__ y, const double *__restrict__ d,
                                                        const double *__restrict__ dinv) {
@@ -312,7 +326,7 @@ __global__ __launch_bounds__(BLK) void spmv_blk_kernel(BlkView A, const int *__r
   const bool have = r < r1;
   int jb = 0, je = 0;
   if (have) { jb = A.rowptr[r] - k0; je = A.rowptr[r + 1] - k0; }
-  blk_products<R, C>(A, k0, k1, xo, xg, p0, p1);
+  blk_products<V, R, C>(A, k0, k1, xo, xg, p0, p1);
   __syncthreads();
   double s0 = 0.0, s1 = 0.0;
   for (int j = jb + lane; j < je; j += RG) { s0 += p0[j]; if (R == 2) s1 += p1[j]; }
@@ -347,8 +361,8 @@ __global__ __launch_bounds__(BLK) void spmv_blk_fused_kernel(BlkView A, const do
     ab = A.rowptr[r] - a0; ae = A.rowptr[r + 1] - a0;
     bb = B.rowptr[r] - b0 + (a1 - a0); be = B.rowptr[r + 1] - b0 + (a1 - a0);
   }
-  blk_products<2, 2>(A, a0, a1, xao, xag, p0, p1);
-  blk_products<2, 1>(B, b0, b1, xbo, xbg, p0 + (a1 - a0), p1 + (a1 - a0));
+  blk_products<double, 2, 2>(A, a0, a1, xao, xag, p0, p1);
+  blk_products<double, 2, 1>(B, b0, b1, xbo, xbg, p0 + (a1 - a0), p1 + (a1 - a0));
   __syncthreads();
   double s0 = 0.0, s1 = 0.0;
   for (int j = ab + lane; j < ae; j += RG) { s0 += p0[j]; s1 += p1[j]; }
@@ -1403,7 +1417,7 @@ void spmv(hipStream_t s, const CsrView &A, int lpr, const double *xo, const doub
 void spmv_stream(hipStream_t s, const CsrView &A, const int *rowblk, int nblk, int even_rows, const double *xo,
                  const double *xg, double *y, int mode, const double *z) {
   if (nblk <= 0) return;
-#define NSK_SS(V, M) hipLaunchKernelGGL((spmv_stream_kernel<V, M>), dim3(nblk), dim3(BLK), 0, s, A, rowblk, xo, xg, y, z)
+#define NSK_SS(V, M) hipLaunchKernelGGL((spmv_stream_kernel<double, V, M>), dim3(nblk), dim3(BLK), 0, s, A, rowblk, xo, xg, y, z)
   // pairs of entries per lane also where the row pointers are not all even (S: 0.271 -> 0.264 ms at 1200x400);
   // NSK_SPMV_WIDE=0: one entry per load there, as in rounds 1-3 (A/B measurements)
   static const bool wide = [] { const char *e = getenv("NSK_SPMV_WIDE"); return !e || atoi(e) != 0; }();
@@ -1414,6 +1428,19 @@ void spmv_stream(hipStream_t s, const CsrView &A, const int *rowblk, int nblk, i
   } else {
     if (mode == 0) NSK_SS(1, 0); else if (mode == 1) NSK_SS(1, 1); else NSK_SS(1, 2);
   }
+#undef NSK_SS
+}
+
+void spmv_stream(hipStream_t s, const CsrView32 &A, const int *rowblk, int nblk, int even_rows, const double *xo,
+                 const double *xg, double *y) {
+  if (nblk <= 0) return;
+  // the double launcher's choice of pair loads (NSK_SPMV_WIDE included): the same lanes sum the same entries
+  static const bool wide = [] { const char *e = getenv("NSK_SPMV_WIDE"); return !e || atoi(e) != 0; }();
+  const double *z = nullptr;
+#define NSK_SS(V) hipLaunchKernelGGL((spmv_stream_kernel<float, V, 0>), dim3(nblk), dim3(BLK), 0, s, A, rowblk, xo, xg, y, z)
+  if (wide && !even_rows) NSK_SS(3);
+  else if (even_rows) NSK_SS(2);
+  else NSK_SS(1);
 #undef NSK_SS
 }
 
@@ -1447,15 +1474,21 @@ void spmv_blk_stream(hipStream_t s, const BlkView &A, int R, int C, const int *r
                      const double *xg, double *y, const double *epi_d, const double *epi_dinv) {
   if (nblk <= 0) return;
   if (epi_d) {   // only built for the (2 x 1) block shape of the (0,1) block
-    hipLaunchKernelGGL((spmv_blk_kernel<2, 1, 1>), dim3(nblk), dim3(BLK), 0, s, A, rowblk, xo, xg, y, epi_d, epi_dinv);
+    hipLaunchKernelGGL((spmv_blk_kernel<double, 2, 1, 1>), dim3(nblk), dim3(BLK), 0, s, A, rowblk, xo, xg, y, epi_d, epi_dinv);
     return;
   }
-#define NSK_BK(RR, CC) hipLaunchKernelGGL((spmv_blk_kernel<RR, CC, 0>), dim3(nblk), dim3(BLK), 0, s, A, rowblk, xo, xg, y, nullptr, nullptr)
+#define NSK_BK(RR, CC) hipLaunchKernelGGL((spmv_blk_kernel<double, RR, CC, 0>), dim3(nblk), dim3(BLK), 0, s, A, rowblk, xo, xg, y, nullptr, nullptr)
   if (R == 2 && C == 2) NSK_BK(2, 2);
   else if (R == 2 && C == 1) NSK_BK(2, 1);
   else if (R == 1 && C == 2) NSK_BK(1, 2);
   else NSK_BK(1, 1);
 #undef NSK_BK
+}
+
+void spmv_blk_stream(hipStream_t s, const BlkView32 &A, const int *rowblk, int nblk, const double *xo, const double *xg,
+                     double *y) {
+  if (nblk > 0)
+    hipLaunchKernelGGL((spmv_blk_kernel<float, 2, 2, 0>), dim3(nblk), dim3(BLK), 0, s, A, rowblk, xo, xg, y, nullptr, nullptr);
 }
 
 void spmv_blk_fused22_21(hipStream_t s, const BlkView &A, const double *xao, const double *xag, const BlkView &B,
@@ -1672,6 +1705,14 @@ void vec_gather(hipStream_t s, int n, const int *idx, const double *x, double *y
 }
 void vec_gather(hipStream_t s, int n, const int *idx, const double *x, float *y) {
   NSK_EW(n, [=] __device__(int i) { y[i] = (float)x[idx[i]]; });   // round to nearest even: the factor's one rounding
+}
+void vec_to_float(hipStream_t s, int n, const double *x, float *y, unsigned *overflow) {
+  NSK_EW(n, [=] __device__(int i) {
+    const double v = x[i];
+    const float f = (float)v;   // round to nearest even, as vec_gather
+    if (y) y[i] = f;
+    if (overflow && __builtin_isinf(f) && !__builtin_isinf(v) && v == v) atomicAdd(overflow, 1u);
+  });
 }
 void halo_pack(hipStream_t s, int n, const int *idx, const double *x, double *buf) { vec_gather(s, n, idx, x, buf); }
 void local_sum(hipStream_t s, int count, const LocalSumArgs &A, double *out) {

@@ -35,6 +35,8 @@ OPT_MASS_ORDERING = 13
 OPT_BLAS1_PAIRS = 15  # 16-byte loads in the reductions: 1 / 0 / -1 (default: stationary on, unsteady off), see include/nsk.h
 OPT_SCHUR_SIGN = 14   # +1 the reference's S (default); -1: labelled deviation, see include/nsk.h
 OPT_FACTOR_PRECISION = 16  # 64 (default) / 32: off-diagonal factor values stored in fp32 — labelled deviation, see include/nsk.h
+OPT_INNER_MATRIX_PRECISION = 17  # 64 (default) / 32: inner solves multiply by fp32 copies of F, S, M_p — labelled deviation, see include/nsk.h
+TIMEOP_INNER_SPMV = 50     # time_op(TIMEOP_INNER_SPMV + blk): the inner solves' SpMV of F, M_p or S
 IOPT_FUSED_MGS, IOPT_OVERLAP_HALO = 106, 107
 IOPT_TIMEOP_BETWEEN = 109  # time_op: SpMV of this block between two repetitions, outside the timed brackets (-1: back to back)
 IOPT_HOST_ANALYSIS = 108   # 1: symbolic set-up of the multicolour factors on the host (A/B, tests); default: on the device
@@ -45,7 +47,7 @@ EXPORTS = [
     "nsk_set_support_points",
     "nsk_set_block_csr", "nsk_update_values", "nsk_set_option", "nsk_setup_preconditioner", "nsk_solve",
     "nsk_upload_system", "nsk_solve_resident", "nsk_download_solution", "nsk_spmv", "nsk_jacobian_vmult", "nsk_dot", "nsk_vec_op",
-    "nsk_tri_apply", "nsk_amg_info", "nsk_tri_get_perm", "nsk_tri_get_value_bytes", "nsk_precond_vmult", "nsk_block_nnz", "nsk_get_block", "nsk_get_stats",
+    "nsk_tri_apply", "nsk_amg_info", "nsk_tri_get_perm", "nsk_tri_get_value_bytes", "nsk_inner_value_bytes", "nsk_inner_spmv", "nsk_precond_vmult", "nsk_block_nnz", "nsk_get_block", "nsk_get_stats",
     "nsk_reset_stats", "nsk_get_history", "nsk_cancel", "nsk_abort_group", "nsk_assembly_set_cells", "nsk_assembly_set_simplex", "nsk_assembly_set_dirichlet", "nsk_state_set", "nsk_state_get",
     "nsk_state_save", "nsk_state_save_old", "nsk_state_update", "nsk_assemble", "nsk_scale_values", "nsk_download_rhs", "nsk_time_assemble", "nsk_time_op", "nsk_profile_begin", "nsk_profile_read", "nsk_profile_end",
 ]
@@ -131,6 +133,8 @@ def lib() -> C.CDLL:
         L.nsk_tri_apply.argtypes = [vp, C.c_int, f64p, f64p]
         L.nsk_tri_get_perm.argtypes = [vp, C.c_int, i32p]
         L.nsk_tri_get_value_bytes.argtypes = [vp, C.c_int, C.POINTER(C.c_int32)]
+        L.nsk_inner_value_bytes.argtypes = [vp, C.c_int, C.POINTER(C.c_int32)]
+        L.nsk_inner_spmv.argtypes = [vp, C.c_int, f64p, f64p]
         L.nsk_precond_vmult.argtypes = [vp, f64p, f64p, f64p, f64p, C.c_int]
         L.nsk_block_nnz.restype = C.c_int64
         L.nsk_block_nnz.argtypes = [vp, C.c_int]
@@ -383,6 +387,20 @@ class LinearSolver:
         b = C.c_int32(0)
         self._ck(self.L.nsk_tri_get_value_bytes(self.h, which, C.byref(b)))
         return b.value
+
+    def inner_value_bytes(self, blk):
+        """Bytes per matrix value the inner solves of the current set-up read for BLK_F, BLK_S or BLK_MP: 4 (fp32 copy,
+        OPT_INNER_MATRIX_PRECISION = 32), 8 (fp64), 0 when the set-up runs no inner solve on that block."""
+        b = C.c_int32(0)
+        self._ck(self.L.nsk_inner_value_bytes(self.h, blk, C.byref(b)))
+        return b.value
+
+    def inner_spmv(self, blk, x):
+        """y = A x with the values, kernel and row runs the inner solves use (BLK_F, BLK_S or BLK_MP); collective."""
+        x = _f64(x)
+        out = np.zeros(self.n_u if blk == BLK_F else self.n_p)
+        self._ck(self.L.nsk_inner_spmv(self.h, blk, x.ctypes.data, out.ctypes.data))
+        return out
 
     def precond_vmult(self, src_u, src_p, dst_u=None, dst_p=None, calls=1):
         su, sp_ = _f64(src_u), _f64(src_p)
