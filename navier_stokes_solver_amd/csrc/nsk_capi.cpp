@@ -1741,6 +1741,106 @@ int nsk_debug_tri_trace(nsk_handle h, int which, int64_t *out16, int max_runs, i
   NSK_CATCH(h)
 }
 
+// test hook (nsk_internal.h): one Krylov vector operation on caller vectors, through the entry points the solvers call
+int nsk_debug_krylov(nsk_handle h, int op, int n, int m, int offset, const double *par, int n_vec, double *const *vec,
+                     const int64_t *len, double *slots64, int32_t *info8) {
+  NSK_TRY(h)
+  (void)hipSetDevice(h->ctx.device);
+  Ctx &c = h->ctx;
+  static const int kVecs[] = {2, 1, 3, 2, 4, -1, -1, -1, 3, 0, 6, 4, 3};   // vectors per op (-1: m + 1)
+  if (op < NSK_DBG_KRY_DOT || op > NSK_DBG_KRY_DENSE_MV) throw Error(-65, "nsk_debug_krylov: unknown op");
+  const bool multi = kVecs[op] < 0;
+  if (multi && (m < 1 || m > (op == NSK_DBG_KRY_GS_COLUMN ? kMgsMaxVecs : 8))) throw Error(-61, "nsk_debug_krylov: m");
+  if (n < 1 || (offset != 0 && offset != 1) || n_vec != (multi ? m + 1 : kVecs[op]))
+    throw Error(-61, "nsk_debug_krylov: n, offset or number of vectors");
+  for (int k = 0; k < n_vec; ++k)
+    if (len[k] != ((op == NSK_DBG_KRY_DENSE_MV && k == 0) ? (int64_t)n * n : (int64_t)n))
+      throw Error(-61, "nsk_debug_krylov: vector length");
+  // every vector in an allocation of its own: `offset` guard words in front, kGuard behind, all holding NaN (all bits set)
+  constexpr int kGuard = 4;
+  hipStream_t st = h->s();
+  std::vector<DBuf<double>> buf((size_t)n_vec);
+  std::vector<double *> d((size_t)n_vec);
+  for (int k = 0; k < n_vec; ++k) {
+    const size_t tot = (size_t)len[k] + offset + kGuard;
+    buf[k].alloc(tot);
+    NSK_HIP(hipMemsetAsync(buf[k].p, 0xFF, sizeof(double) * tot, st));
+    d[k] = buf[k].p + offset;
+    NSK_HIP(hipMemcpyAsync(d[k], vec[k], sizeof(double) * (size_t)len[k], hipMemcpyHostToDevice, st));
+  }
+  struct Restore {
+    Ctx &c;
+    int top;
+    ~Restore() { c.slot_top = top; }
+  } restore{c, c.slot_top};
+  const int so = c.alloc_slots(64);
+  NSK_HIP(hipMemsetAsync(c.slot(so), 0xFF, sizeof(double) * 64, st));
+  auto set_slots = [&](int count) {
+    NSK_HIP(hipMemcpyAsync(c.slot(so), par, sizeof(double) * (size_t)count, hipMemcpyHostToDevice, st));
+  };
+  c.red_paths = 0;
+  int path = -1;
+  switch (op) {
+    case NSK_DBG_KRY_DOT: c.dot(n, d[0], d[1], so); break;
+    case NSK_DBG_KRY_NORM2: c.norm2(n, d[0], so); break;
+    case NSK_DBG_KRY_AXPY_DOT: c.axpy_dot(n, sref(par[0]), d[0], d[1], d[2], so); break;
+    case NSK_DBG_KRY_AXPY_NORM2: c.axpy_norm2(n, sref(par[0]), d[0], d[1], so); break;
+    case NSK_DBG_KRY_CG_UPDATE: c.cg_update(n, sref(par[0]), d[0], d[1], d[2], d[3], so); break;
+    case NSK_DBG_KRY_MULTI_DOT: c.multi_dot(n, d[0], d.data() + 1, m, so); break;
+    case NSK_DBG_KRY_MULTI_AXPY:
+      set_slots(m);
+      c.multi_axpy(n, d[0], d.data() + 1, m, so, par[m] != 0.0 ? so + m : -1);
+      break;
+    case NSK_DBG_KRY_GS_COLUMN: {
+      const int mode = (int)par[0];
+      if (mode < 0 || mode > 2) throw Error(-61, "nsk_debug_krylov: Gram-Schmidt mode 0, 1 or 2");
+      c.mgs_tier = 0;
+      const long fallbacks = c.mgs_fallbacks;
+      // (a sweep whose wait ran out is redone on w as it came in)
+      arnoldi_column(c, n, d[0], d.data() + 1, m, so, mode, [&] {
+        NSK_HIP(hipMemcpyAsync(d[0], vec[0], sizeof(double) * (size_t)n, hipMemcpyHostToDevice, st));
+      });
+      if (mode == 0) path = c.mgs_fallbacks == fallbacks ? c.mgs_tier : 0;
+      break;
+    }
+    case NSK_DBG_KRY_DOT3: c.dot3(n, d[0], d[1], d[2], so); break;
+    case NSK_DBG_KRY_CG_SCALARS:
+      set_slots(7);
+      cg_fused_scalars(st, c.slot(so), (int)par[7]);
+      break;
+    case NSK_DBG_KRY_CG_FUSED_UPDATE:
+      set_slots(7);
+      vec_cg_fused_update(st, n, c.slot(so), d[0], d[1], d[2], d[3], d[4], d[5]);
+      break;
+    case NSK_DBG_KRY_CHEBY: vec_cheby_step(st, n, par[0], par[1], d[0], d[1], d[2], d[3], (int)par[2]); break;
+    case NSK_DBG_KRY_DENSE_MV: dense_mv(st, n, d[0], d[1], d[2]); break;
+  }
+  int bad_guards = 0;
+  std::vector<double> all;
+  for (int k = 0; k < n_vec; ++k) {
+    all.resize(buf[k].n);
+    NSK_HIP(hipMemcpyAsync(all.data(), buf[k].p, sizeof(double) * all.size(), hipMemcpyDeviceToHost, st));
+    c.sync();
+    std::copy(all.begin() + offset, all.begin() + offset + len[k], vec[k]);
+    for (size_t i = 0; i < all.size(); ++i) {
+      if (i == (size_t)offset) i += (size_t)len[k];
+      if (i < all.size()) {
+        uint64_t bits;
+        memcpy(&bits, &all[i], 8);
+        bad_guards += bits != ~0ull;
+      }
+    }
+  }
+  memcpy(slots64, c.read_slots(so, 64), sizeof(double) * 64);
+  info8[0] = (int32_t)c.red_paths;
+  info8[1] = path;
+  info8[2] = std::min(c.n_cu, kMgsThreads);
+  info8[3] = bad_guards;
+  for (int k = 4; k < 8; ++k) info8[k] = 0;
+  return 0;
+  NSK_CATCH(h)
+}
+
 int nsk_amg_info(nsk_handle h, int shard, int level, int64_t *rows, int64_t *nnz, double *lambda_max) {
   NSK_TRY(h)
   if (h->amg_active) h->amg_ready();

@@ -393,13 +393,13 @@ const double *Ctx::read_slots(int first, int count) {
 // Reductions.  With more than one rank the local sum is all-reduced in place on the
 // same stream and the norm slot (sum slot + 1) is then recomputed from the global sum.
 void Ctx::dot(int n, const double *x, const double *y, int so) {
-  vec_dot(stream, ws, n, x, y, slot(so), 0);
+  red_paths |= vec_dot(stream, ws, n, x, y, slot(so), 0);
   comm.allreduce_sum(slot(so), 1, stream);
   ++st.reductions;
   st.blas1_bytes += 16.0 * n;
 }
 void Ctx::norm2(int n, const double *x, int so) {
-  vec_dot(stream, ws, n, x, x, slot(so), 1);
+  red_paths |= vec_dot(stream, ws, n, x, x, slot(so), 1);
   if (comm.active()) {
     comm.allreduce_sum(slot(so), 1, stream);
     scalar_sqrt(stream, slot(so), slot(so) + 1);
@@ -408,13 +408,13 @@ void Ctx::norm2(int n, const double *x, int so) {
   st.blas1_bytes += 8.0 * n;
 }
 void Ctx::axpy_dot(int n, SRef a, const double *x, double *y, const double *w, int so) {
-  vec_axpy_dot(stream, ws, n, a, x, y, w, slot(so), 0);
+  red_paths |= vec_axpy_dot(stream, ws, n, a, x, y, w, slot(so), 0);
   comm.allreduce_sum(slot(so), 1, stream);
   ++st.reductions;
   st.blas1_bytes += 32.0 * n;
 }
 void Ctx::axpy_norm2(int n, SRef a, const double *x, double *y, int so) {
-  vec_axpy_dot(stream, ws, n, a, x, y, y, slot(so), 1);
+  red_paths |= vec_axpy_dot(stream, ws, n, a, x, y, y, slot(so), 1);
   if (comm.active()) {
     comm.allreduce_sum(slot(so), 1, stream);
     scalar_sqrt(stream, slot(so), slot(so) + 1);
@@ -423,7 +423,7 @@ void Ctx::axpy_norm2(int n, SRef a, const double *x, double *y, int so) {
   st.blas1_bytes += 24.0 * n;
 }
 void Ctx::cg_update(int n, SRef a, const double *d, const double *h, double *x, double *g, int so) {
-  vec_cg_update(stream, ws, n, a, d, h, x, g, slot(so));
+  red_paths |= vec_cg_update(stream, ws, n, a, d, h, x, g, slot(so));
   if (comm.active()) {
     comm.allreduce_sum(slot(so), 1, stream);
     scalar_sqrt(stream, slot(so), slot(so) + 1);
@@ -433,7 +433,7 @@ void Ctx::cg_update(int n, SRef a, const double *d, const double *h, double *x, 
 }
 
 void Ctx::dot3(int n, const double *r, const double *u, const double *w, int so) {
-  vec_dot3(stream, ws, n, r, u, w, slot(so));
+  red_paths |= vec_dot3(stream, ws, n, r, u, w, slot(so));
   comm.allreduce_sum(slot(so), 3, stream);   // ONE all-reduce for the three scalars of a CG step
   ++st.reductions;
   st.blas1_bytes += 24.0 * n;
@@ -441,7 +441,7 @@ void Ctx::dot3(int n, const double *r, const double *u, const double *w, int so)
 void Ctx::multi_dot(int n, const double *w, double *const *v, int m, int so, bool defer) {
   VecPack P{};
   for (int k = 0; k < m; ++k) P.v[k] = v[k];
-  vec_multi_dot(stream, ws, n, w, P, m, slot(so));
+  red_paths |= vec_multi_dot(stream, ws, n, w, P, m, slot(so));
   if (!defer) {
     comm.allreduce_sum(slot(so), m, stream);
     ++st.reductions;
@@ -455,7 +455,7 @@ void Ctx::allreduce_slots(int first, int count) {
 void Ctx::multi_axpy(int n, double *w, double *const *v, int m, int coef_slot, int norm_slot) {
   VecPack P{};
   for (int k = 0; k < m; ++k) P.v[k] = v[k];
-  vec_multi_axpy(stream, ws, n, w, P, m, slot(coef_slot), norm_slot >= 0 ? slot(norm_slot) : nullptr);
+  red_paths |= vec_multi_axpy(stream, ws, n, w, P, m, slot(coef_slot), norm_slot >= 0 ? slot(norm_slot) : nullptr);
   if (norm_slot >= 0 && comm.active()) {
     comm.allreduce_sum(slot(norm_slot), 1, stream);
     scalar_sqrt(stream, slot(norm_slot), slot(norm_slot) + 1);
@@ -508,7 +508,8 @@ bool Ctx::mgs_sweep(int n, double *w, double *const *v, int nv, int so) {
   A.err = mgs_err.p;
   A.fault = mgs_fault ? 1 : 0;
   NSK_HIP(hipMemsetAsync(slot(so + nv + 2), 0, sizeof(double), stream));   // the "sums invalid" flag: raised by any workgroup
-  if (!nsk::mgs_sweep(stream, A, G)) return false;
+  mgs_tier = nsk::mgs_sweep(stream, A, G);
+  if (!mgs_tier) return false;
   mgs_parity = 1 - mgs_parity;
   st.reductions += nv + 1;
   st.blas1_bytes += 8.0 * n * (nv + 2);

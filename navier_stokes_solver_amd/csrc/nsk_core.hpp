@@ -298,6 +298,10 @@ struct Ctx {
   DBuf<double> mgs_tables;
   DBuf<int> mgs_err;
   int mgs_parity = 0, mgs_grid = 0;
+  // which kernels ran (test hook nsk_debug_krylov): red_paths ORs the launchers' kRedScalar / kRedPairs, mgs_tier = the
+  // entries per thread of the last sweep that was launched
+  unsigned red_paths = 0;
+  int mgs_tier = 0;
   void spmv(Csr &A, Space &colspace, const DVec &x, double *y, int mode = 0, const double *z = nullptr);
 };
 

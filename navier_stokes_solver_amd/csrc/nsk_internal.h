@@ -63,6 +63,38 @@ int nsk_debug_ilu0_at_offset(int what, int n, const int32_t *rowptr, const int32
 int nsk_debug_schur_at_offset(int n_p, int n_u, const int32_t *b_rp, const int32_t *b_col, const double *b_val,
                               const double *dinv, const int32_t *bt_rp, const int32_t *bt_col, const double *bt_val,
                               const int32_t *s_rp, const int32_t *s_col, double *s_val_out, int64_t base);
+/* Test hook for the Krylov vector kernels (tests/test_gpu_krylov_kernels.py): ONE operation `op` (NSK_DBG_KRY_*) through
+ * the entry points the solvers call (Ctx:: reductions on the handle's workspace and slots, arnoldi_column, nsk:: launchers).
+ * vec[k] (host, len[k] doubles, in/out) is copied into a fresh device buffer of its own that starts `offset` (0 or 1)
+ * doubles into the allocation (offset 1: not 16-byte aligned, the pair kernels do not apply) and is followed by guard
+ * words; what the op wrote comes back.  The pair choice is the handle's (NSK_OPT_BLAS1_PAIRS).  slots64 receives 64
+ * device scalar slots (NaN where the op wrote none); par: the op's scalars.
+ *   DOT        x, y                     [0] = x.y
+ *   NORM2      x                        [0] = x.x, [1] = |x|
+ *   AXPY_DOT   x, y, w    par a         y += a x ; [0] = y.w
+ *   AXPY_NORM2 x, y       par a         y += a x ; [0] = y.y, [1] = |y|
+ *   CG_UPDATE  d, h, x, g par a         x += a d ; g += a h ; [0] = g.g, [1] = |g|
+ *   MULTI_DOT  w, v_0 .. v_{m-1}        [k] = w.v_k                               (m = 1 .. 8)
+ *   MULTI_AXPY w, v_0 .. v_{m-1}        par h_0 .. h_{m-1}, norm: w -= sum h_k v_k ; [k] = h_k, norm != 0: [m] = w.w,
+ *                                       [m+1] = |w|                               (m = 1 .. 8)
+ *   GS_COLUMN  w, v_0 .. v_{m-1}        par mode (NSK_OPT_INNER_FUSED_GS 0 / 1 / 2): arnoldi_column; [k] = h_k, [m] = w.w,
+ *                                       [m+1] = |w|                               (m = 1 .. 32)
+ *   DOT3       r, u, w                  [0] = r.u, [1] = w.u, [2] = r.r
+ *   CG_SCALARS (none)                   par sc_0 .. sc_6, first: cg_fused_scalars on slots [0..7) = sc
+ *   CG_FUSED_UPDATE u, w, p, s, x, r    par sc_0 .. sc_6: vec_cg_fused_update with slots [0..7) = sc
+ *   CHEBY      dinv, r, w, x            par c1, c2, set_x: vec_cheby_step
+ *   DENSE_MV   M (n x n), b, x          x = M b
+ * info8: [0] reduction kernels that ran (bit 0: 8-byte-per-lane form, bit 1: pair form), [1] modified Gram-Schmidt path
+ * of GS_COLUMN (4 / 8 / 12: the one-launch sweep with that many entries per thread, 0 the chain of launches, -1 not that
+ * path), [2] the sweep's grid (co-resident workgroups), [3] guard words that changed (writes outside the vectors).
+ * Device and stream of the handle; 0 or a negative error code. */
+enum {
+  NSK_DBG_KRY_DOT = 0, NSK_DBG_KRY_NORM2 = 1, NSK_DBG_KRY_AXPY_DOT = 2, NSK_DBG_KRY_AXPY_NORM2 = 3, NSK_DBG_KRY_CG_UPDATE = 4,
+  NSK_DBG_KRY_MULTI_DOT = 5, NSK_DBG_KRY_MULTI_AXPY = 6, NSK_DBG_KRY_GS_COLUMN = 7, NSK_DBG_KRY_DOT3 = 8,
+  NSK_DBG_KRY_CG_SCALARS = 9, NSK_DBG_KRY_CG_FUSED_UPDATE = 10, NSK_DBG_KRY_CHEBY = 11, NSK_DBG_KRY_DENSE_MV = 12
+};
+int nsk_debug_krylov(struct nsk_handle_s *h, int op, int n, int m, int offset, const double *par, int n_vec,
+                     double *const *vec, const int64_t *len, double *slots64, int32_t *info8);
 #ifdef __cplusplus
 }
 #endif

@@ -102,28 +102,31 @@ void vec_recip(hipStream_t s, int n, const double *x, double *y);               
 void vec_cheby_step(hipStream_t s, int n, double c1, double c2, const double *dinv, const double *r, double *w,
                     double *x, int set_x);
 void dense_mv(hipStream_t s, int n, const double *M, const double *b, double *x);       // x = M b, M n x n row-major
-// reductions: results land in out[0] (and out[1] = sqrt(out[0]) when want_sqrt)
-void vec_dot(hipStream_t s, const ReduceWs &ws, int n, const double *x, const double *y, double *out, int want_sqrt);
+// reductions: results land in out[0] (and out[1] = sqrt(out[0]) when want_sqrt).  The launchers return which kernel ran
+// (what the test hook nsk_debug_krylov reports): kRedScalar the 8-byte-per-lane form, kRedPairs the 16-byte pair form
+// (NSK_OPT_BLAS1_PAIRS and every vector 16-byte aligned), 0 nothing launched.
+constexpr int kRedScalar = 1, kRedPairs = 2;
+int vec_dot(hipStream_t s, const ReduceWs &ws, int n, const double *x, const double *y, double *out, int want_sqrt);
 // y += a x ; out = y . w  (w may alias y)  — deal.II add_and_dot, one pass
-void vec_axpy_dot(hipStream_t s, const ReduceWs &ws, int n, SRef a, const double *x, double *y, const double *w,
-                  double *out, int want_sqrt);
+int vec_axpy_dot(hipStream_t s, const ReduceWs &ws, int n, SRef a, const double *x, double *y, const double *w,
+                 double *out, int want_sqrt);
 // CG update: x += a d ; g += a h ; out = g.g, out[1] = sqrt
-void vec_cg_update(hipStream_t s, const ReduceWs &ws, int n, SRef a, const double *d, const double *h, double *x,
-                   double *g, double *out);
+int vec_cg_update(hipStream_t s, const ReduceWs &ws, int n, SRef a, const double *d, const double *h, double *x,
+                  double *g, double *out);
 // Fused classical Gram-Schmidt building blocks (up to 8 basis vectors per pass):
 //   multi_dot : out[k] = w . v[k]                      (w read once)
 //   multi_axpy: w -= sum_k h[k] v[k] ; if norm_out: norm_out[0] = w.w, norm_out[1] = sqrt
 struct VecPack {
   const double *v[8];
 };
-void vec_multi_dot(hipStream_t s, const ReduceWs &ws, int n, const double *w, const VecPack &P, int m, double *out);
+int vec_multi_dot(hipStream_t s, const ReduceWs &ws, int n, const double *w, const VecPack &P, int m, double *out);
 void gs_pythagoras(hipStream_t s, double *h, int m);   // h[m] = w.w  ->  h[m] = w.w - sum h_i^2, h[m+1] = sqrt
-void vec_multi_axpy(hipStream_t s, const ReduceWs &ws, int n, double *w, const VecPack &P, int m, const double *h,
-                    double *norm_out);
+int vec_multi_axpy(hipStream_t s, const ReduceWs &ws, int n, double *w, const VecPack &P, int m, const double *h,
+                   double *norm_out);
 // One-launch modified Gram-Schmidt sweep (nsk_kernels.hip: mgs_sweep_kernel): out[i] = h_i (i < nv), out[nv] = |aux|^2,
 // out[nv+1] = |aux|, out[nv+2] = 1 if a wait gave up (sums invalid), else 0.  `table` / `rearm`: two tables of (kMgsMaxVecs + 1) x G words, the first holding the sentinel in
-// all rows (each sweep arms the other one for its successor).  Returns false (nothing launched) when the
-// vector is too long for G co-resident workgroups to keep in registers.
+// all rows (each sweep arms the other one for its successor).  Returns the entries per thread of the kernel that ran (4, 8
+// or 12), or 0 (nothing launched) when the vector is too long for G co-resident workgroups to keep in registers.
 constexpr int kMgsThreads = 1024, kMgsMaxVecs = 32;
 struct MgsArgs {
   int n, nv;
@@ -132,9 +135,9 @@ struct MgsArgs {
   int *err;
   int fault;   // test hook: workgroup 0 withholds its first partial sum, so every wait on it runs out
 };
-bool mgs_sweep(hipStream_t s, const MgsArgs &A, int G);
+int mgs_sweep(hipStream_t s, const MgsArgs &A, int G);
 // single-reduction (Chronopoulos-Gear) CG building blocks: see SolverCG::solve_fused
-void vec_dot3(hipStream_t s, const ReduceWs &ws, int n, const double *r, const double *u, const double *w, double *out);
+int vec_dot3(hipStream_t s, const ReduceWs &ws, int n, const double *r, const double *u, const double *w, double *out);
 void cg_fused_scalars(hipStream_t s, double *sc7, int first);
 void vec_cg_fused_update(hipStream_t s, int n, const double *sc7, const double *u, const double *w, double *p, double *sv,
                          double *x, double *r);

@@ -1760,19 +1760,20 @@ bool blas1_pairs(const ReduceWs &ws) {   // the handle's choice (NSK_OPT_BLAS1_P
 typedef const double2 *cd2;
 }  // namespace
 
-void vec_dot(hipStream_t s, const ReduceWs &ws, int n, const double *x, const double *y, double *out, int want_sqrt) {
+int vec_dot(hipStream_t s, const ReduceWs &ws, int n, const double *x, const double *y, double *out, int want_sqrt) {
   auto f1 = [=] __device__(int i) -> double { return x[i] * y[i]; };
   if (blas1_pairs(ws) && aligned16(x, y) && n >= 2) {
     NSK_RED2(n, ([=] __device__(int j) -> double {
                const double2 a = cd2(x)[j], b = cd2(y)[j];
                return a.x * b.x + a.y * b.y;
              }), f1);
-    return;
+    return kRedPairs;
   }
   NSK_RED(n, f1);
+  return kRedScalar;
 }
-void vec_axpy_dot(hipStream_t s, const ReduceWs &ws, int n, SRef a, const double *x, double *y, const double *w,
-                  double *out, int want_sqrt) {
+int vec_axpy_dot(hipStream_t s, const ReduceWs &ws, int n, SRef a, const double *x, double *y, const double *w,
+                 double *out, int want_sqrt) {
   const bool pairs = blas1_pairs(ws) && aligned16(x, y, w) && n >= 2;
   if (w == y) {
     auto f1 = [=] __device__(int i) -> double {
@@ -1809,9 +1810,10 @@ void vec_axpy_dot(hipStream_t s, const ReduceWs &ws, int n, SRef a, const double
                }), f1);
     else NSK_RED(n, f1);
   }
+  return pairs ? kRedPairs : kRedScalar;
 }
-void vec_cg_update(hipStream_t s, const ReduceWs &ws, int n, SRef a, const double *d, const double *h, double *x,
-                   double *g, double *out) {
+int vec_cg_update(hipStream_t s, const ReduceWs &ws, int n, SRef a, const double *d, const double *h, double *x,
+                  double *g, double *out) {
   const int want_sqrt = 1;
   auto f1 = [=] __device__(int i) -> double {
     const double al = sval(a);
@@ -1833,9 +1835,10 @@ void vec_cg_update(hipStream_t s, const ReduceWs &ws, int n, SRef a, const doubl
                reinterpret_cast<double2 *>(g)[j] = gv;
                return gv.x * gv.x + gv.y * gv.y;
              }), f1);
-    return;
+    return kRedPairs;
   }
   NSK_RED(n, f1);
+  return kRedScalar;
 }
 
 // ------------------------------------------------------------------ one-launch modified Gram-Schmidt sweep
@@ -1930,13 +1933,13 @@ __global__ __launch_bounds__(kMgsThreads) void mgs_sweep_kernel(MgsArgs A) {
   if (gave_up && t == 0) A.out[A.nv + 2] = 1.0;
 }
 
-bool mgs_sweep(hipStream_t s, const MgsArgs &A, int G) {
+int mgs_sweep(hipStream_t s, const MgsArgs &A, int G) {
   const long per = ((long)A.n + (long)G * kMgsThreads - 1) / ((long)G * kMgsThreads);
-  if (G < 1 || G > kMgsThreads || A.nv > kMgsMaxVecs || per > 12) return false;
-  if (per <= 4) hipLaunchKernelGGL((mgs_sweep_kernel<4>), dim3(G), dim3(kMgsThreads), 0, s, A);
-  else if (per <= 8) hipLaunchKernelGGL((mgs_sweep_kernel<8>), dim3(G), dim3(kMgsThreads), 0, s, A);
-  else hipLaunchKernelGGL((mgs_sweep_kernel<12>), dim3(G), dim3(kMgsThreads), 0, s, A);
-  return true;
+  if (G < 1 || G > kMgsThreads || A.nv > kMgsMaxVecs || per > 12) return 0;
+  if (per <= 4) { hipLaunchKernelGGL((mgs_sweep_kernel<4>), dim3(G), dim3(kMgsThreads), 0, s, A); return 4; }
+  if (per <= 8) { hipLaunchKernelGGL((mgs_sweep_kernel<8>), dim3(G), dim3(kMgsThreads), 0, s, A); return 8; }
+  hipLaunchKernelGGL((mgs_sweep_kernel<12>), dim3(G), dim3(kMgsThreads), 0, s, A);
+  return 12;
 }
 
 // out[0] = r.u, out[1] = w.u, out[2] = r.r in ONE pass (single-reduction CG)
@@ -1951,8 +1954,9 @@ __global__ __launch_bounds__(RBLK) void dot3_kernel(int n, const double *__restr
   }
   reduce_finish<3>(acc, ws, out, 0);
 }
-void vec_dot3(hipStream_t s, const ReduceWs &ws, int n, const double *r, const double *u, const double *w, double *out) {
+int vec_dot3(hipStream_t s, const ReduceWs &ws, int n, const double *r, const double *u, const double *w, double *out) {
   hipLaunchKernelGGL(dot3_kernel, dim3(red_grid(n)), dim3(RBLK), 0, s, n, r, u, w, ws, out);
+  return kRedScalar;
 }
 // Scalars of one single-reduction CG step, on the device: sc = {gamma_new, delta, rr | gamma, alpha, beta, norm}
 //   first != 0:  beta = 0, alpha = gamma_new / delta
@@ -1990,19 +1994,22 @@ bool pack_aligned16(const double *w, const VecPack &P, int m) {
   return (a & 15u) == 0;
 }
 }  // namespace
-void vec_multi_dot(hipStream_t s, const ReduceWs &ws, int n, const double *w, const VecPack &P, int m, double *out) {
+int vec_multi_dot(hipStream_t s, const ReduceWs &ws, int n, const double *w, const VecPack &P, int m, double *out) {
+  if (m < 1 || m > 8) return 0;
   if (blas1_pairs(ws) && n >= 2 && pack_aligned16(w, P, m)) {
 #define NSK_MD(M) case M: hipLaunchKernelGGL((multi_dot2_kernel<M>), dim3(red_grid_pairs(n, 256)), dim3(RBLK), 0, s, n, w, P, ws, out); break;
     switch (m) { NSK_MD(1) NSK_MD(2) NSK_MD(3) NSK_MD(4) NSK_MD(5) NSK_MD(6) NSK_MD(7) NSK_MD(8) default: break; }
 #undef NSK_MD
-    return;
+    return kRedPairs;
   }
 #define NSK_MD(M) case M: hipLaunchKernelGGL((multi_dot_kernel<M>), dim3(red_grid(n)), dim3(RBLK), 0, s, n, w, P, ws, out); break;
   switch (m) { NSK_MD(1) NSK_MD(2) NSK_MD(3) NSK_MD(4) NSK_MD(5) NSK_MD(6) NSK_MD(7) NSK_MD(8) default: break; }
 #undef NSK_MD
+  return kRedScalar;
 }
-void vec_multi_axpy(hipStream_t s, const ReduceWs &ws, int n, double *w, const VecPack &P, int m, const double *h,
-                    double *norm_out) {
+int vec_multi_axpy(hipStream_t s, const ReduceWs &ws, int n, double *w, const VecPack &P, int m, const double *h,
+                   double *norm_out) {
+  if (m < 1 || m > 8) return 0;
   // (without the norm the update is entry by entry: the same bits in pairs, whatever the handle chose for the sums)
   if ((!norm_out || blas1_pairs(ws)) && n >= 2 && pack_aligned16(w, P, m)) {
 #define NSK_MA(M)                                                                                                \
@@ -2012,7 +2019,7 @@ void vec_multi_axpy(hipStream_t s, const ReduceWs &ws, int n, double *w, const V
     break;
     switch (m) { NSK_MA(1) NSK_MA(2) NSK_MA(3) NSK_MA(4) NSK_MA(5) NSK_MA(6) NSK_MA(7) NSK_MA(8) default: break; }
 #undef NSK_MA
-    return;
+    return kRedPairs;
   }
 #define NSK_MA(M)                                                                                                \
   case M:                                                                                                        \
@@ -2021,6 +2028,7 @@ void vec_multi_axpy(hipStream_t s, const ReduceWs &ws, int n, double *w, const V
     break;
   switch (m) { NSK_MA(1) NSK_MA(2) NSK_MA(3) NSK_MA(4) NSK_MA(5) NSK_MA(6) NSK_MA(7) NSK_MA(8) default: break; }
 #undef NSK_MA
+  return kRedScalar;
 }
 
 namespace {

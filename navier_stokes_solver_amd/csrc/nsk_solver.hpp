@@ -190,6 +190,55 @@ inline double lsq_householder(int rows, int cols, const double *H, int ld, doubl
   return std::sqrt(r2);
 }
 
+// ------------------------------------------------------------------ Arnoldi column of SolverFGMRES
+// Orthogonalises w against the basis v[0 .. m) the way FGMRES forms column m - 1 of its Hessenberg matrix, and leaves
+// h_i in slots HS + i (i < m), |w|^2 in HS + m and |w| in HS + m + 1.  fused_gs (NSK_OPT_INNER_FUSED_GS):
+//   0  modified Gram-Schmidt: the one-launch sweep (Ctx::mgs_sweep) when it applies, else the chain of dot / add_and_dot
+//      launches; a sweep whose wait ran out is redone link by link on the w that `redo` forms again;
+//   1  classical Gram-Schmidt in two fused sweeps: all h_i from one read of w (8 basis vectors per pass), then
+//      w -= sum h_i v_i and |w|.  Same Arnoldi relation as deal.II's modified Gram-Schmidt in exact arithmetic; ~2.5x
+//      fewer bytes and 4 launches instead of m + 1 (the passes' partial sums land in consecutive slots: one all-reduce);
+//   2  the same with |w|^2 = w.w - sum h_i^2 (w.w rides in the coefficient pass): one cross-rank reduction, not two.
+// m <= kMgsMaxVecs.  Returns the host copy of slots HS .. HS + m + 2 (the last one is the sweep's "timed out" word, and
+// only meaningful when the sweep ran).  Shared with the test hook nsk_debug_krylov.
+template <class Redo>
+const double *arnoldi_column(Ctx &ctx, int n, double *w, double *const *v, int m, int HS, int fused_gs, Redo &&redo) {
+  const int j = m - 1;
+  int mgs_flag = -1;
+  if (fused_gs) {
+    const bool one_red = fused_gs == 2;
+    double *vv[kMgsMaxVecs + 1];
+    for (int i = 0; i <= j; ++i) vv[i] = v[i];
+    vv[j + 1] = w;   // one_red: w.w as one more "coefficient" of the same pass
+    const int mm = j + 1 + (one_red ? 1 : 0);
+    for (int i0 = 0; i0 < mm; i0 += 8) ctx.multi_dot(n, w, &vv[i0], std::min(8, mm - i0), HS + i0, true);
+    ctx.allreduce_slots(HS, mm);
+    if (one_red) gs_pythagoras(ctx.stream, ctx.slot(HS), j + 1);
+    for (int i0 = 0; i0 <= j; i0 += 8)
+      ctx.multi_axpy(n, w, &v[i0], std::min(8, j + 1 - i0), HS + i0, (!one_red && i0 + 8 > j) ? HS + j + 1 : -1);
+  } else if (ctx.mgs_sweep(n, w, v, j + 1, HS)) {
+    // modified Gram-Schmidt, the whole chain in one launch (Ctx::mgs_sweep)
+    mgs_flag = HS + j + 3;
+  } else {
+    // modified Gram-Schmidt with add_and_dot; all coefficients stay on the device
+    ctx.dot(n, w, v[0], HS);
+    for (int i = 1; i <= j; ++i) ctx.axpy_dot(n, sref(-1.0, ctx.slot(HS + i - 1)), v[i - 1], w, v[i], HS + i);
+    ctx.axpy_norm2(n, sref(-1.0, ctx.slot(HS + j)), v[j], w, HS + j + 1);
+  }
+  const double *h = ctx.read_slots(HS, j + 4);
+  if (mgs_flag >= 0 && h[j + 3] != 0.0) {
+    // a wait of the one-launch sweep gave up (its workgroups were not co-resident: another process on the GPU?):
+    // w is formed again and orthogonalised link by link; the sweep stays off for this handle
+    ctx.mgs_timed_out();
+    redo();
+    ctx.dot(n, w, v[0], HS);
+    for (int i = 1; i <= j; ++i) ctx.axpy_dot(n, sref(-1.0, ctx.slot(HS + i - 1)), v[i - 1], w, v[i], HS + i);
+    ctx.axpy_norm2(n, sref(-1.0, ctx.slot(HS + j)), v[j], w, HS + j + 1);
+    h = ctx.read_slots(HS, j + 3);
+  }
+  return h;
+}
+
 // ------------------------------------------------------------------ SolverFGMRES (A.1), max_basis_size = 30
 struct SolverFGMRES : SolverBase {
   using SolverBase::SolverBase;
@@ -197,7 +246,8 @@ struct SolverFGMRES : SolverBase {
   int iterations = 0;
   int fused_gs = 0;  // inner solves: 1 fused classical Gram-Schmidt instead of modified; 2 the same with the new
                      // vector's norm from |w|^2 - sum h_i^2 (w.w rides in the coefficient pass): ONE cross-rank
-                     // reduction per iteration instead of two (NSK_OPT_INNER_FUSED_GS = 2, for several GPUs)
+                     // reduction per iteration instead of two (NSK_OPT_INNER_FUSED_GS = 2, for several GPUs).  See
+                     // arnoldi_column
   void solve(const MatVec &A, DVec &x, const DVec &b, const PrecVmult &P) {
     std::vector<double *> v(kBasis, nullptr), z(kBasis, nullptr);
     double *auxp = pool.get(false);
@@ -233,48 +283,11 @@ struct SolverFGMRES : SolverBase {
         if (!v[j]) v[j] = pool.get(false);
         if (!z[j]) z[j] = pool.get(true);  // zero on first use, stale (previous cycle) afterwards
         DVec vj = pool.view(v[j]), zj = pool.view(z[j]);
-        int mgs_flag = -1;
         if (a != 0.0 && std::isfinite(1.0 / a)) vec_equ(s(), n, sref(1.0, nullptr, ctx.slot(a_slot)), aux.own, vj.own);
         else vec_set(s(), n, vj.own, 0.0);
         P(zj, vj);
         A(zj, aux.own);
-        if (fused_gs) {
-          // classical Gram-Schmidt in two fused sweeps: all h(i,j) from one read of aux (8 basis vectors
-          // per pass), then aux -= sum h(i,j) v_i and ||aux||.  Same Arnoldi relation as deal.II's
-          // modified Gram-Schmidt in exact arithmetic; ~2.5x fewer bytes and 4 launches instead of j+2.
-          // (the passes' partial sums land in consecutive slots: one all-reduce for the whole column)
-          const bool one_red = fused_gs == 2;
-          double *vv[kBasis + 1];
-          for (int i = 0; i <= j; ++i) vv[i] = v[i];
-          vv[j + 1] = aux.own;   // one_red: w.w as one more "coefficient" of the same pass
-          const int m = j + 1 + (one_red ? 1 : 0);
-          for (int i0 = 0; i0 < m; i0 += 8) ctx.multi_dot(n, aux.own, &vv[i0], std::min(8, m - i0), HS + i0, true);
-          ctx.allreduce_slots(HS, m);
-          if (one_red) gs_pythagoras(s(), ctx.slot(HS), j + 1);
-          for (int i0 = 0; i0 <= j; i0 += 8)
-            ctx.multi_axpy(n, aux.own, &v[i0], std::min(8, j + 1 - i0), HS + i0, (!one_red && i0 + 8 > j) ? HS + j + 1 : -1);
-        } else if (ctx.mgs_sweep(n, aux.own, v.data(), j + 1, HS)) {
-          // modified Gram-Schmidt, the whole chain in one launch (Ctx::mgs_sweep)
-          mgs_flag = HS + j + 3;
-        } else {
-          // modified Gram-Schmidt with add_and_dot; all coefficients stay on the device
-          ctx.dot(n, aux.own, v[0], HS);
-          for (int i = 1; i <= j; ++i)
-            ctx.axpy_dot(n, sref(-1.0, ctx.slot(HS + i - 1)), v[i - 1], aux.own, v[i], HS + i);
-          ctx.axpy_norm2(n, sref(-1.0, ctx.slot(HS + j)), v[j], aux.own, HS + j + 1);
-        }
-        const double *h = ctx.read_slots(HS, j + 4);
-        if (mgs_flag >= 0 && h[j + 3] != 0.0) {
-          // a wait of the one-launch sweep gave up (its workgroups were not co-resident: another process on the GPU?):
-          // w = A z_j is formed again and orthogonalised link by link; the sweep stays off for this handle
-          ctx.mgs_timed_out();
-          A(zj, aux.own);
-          ctx.dot(n, aux.own, v[0], HS);
-          for (int i = 1; i <= j; ++i)
-            ctx.axpy_dot(n, sref(-1.0, ctx.slot(HS + i - 1)), v[i - 1], aux.own, v[i], HS + i);
-          ctx.axpy_norm2(n, sref(-1.0, ctx.slot(HS + j)), v[j], aux.own, HS + j + 1);
-          h = ctx.read_slots(HS, j + 3);
-        }
+        const double *h = arnoldi_column(ctx, n, aux.own, v.data(), j + 1, HS, fused_gs, [&] { A(zj, aux.own); });
         for (int i = 0; i <= j; ++i) H[i * kBasis + j] = h[i];
         H[(j + 1) * kBasis + j] = a = h[j + 2];
         a_slot = HS + j + 2;
