@@ -400,9 +400,8 @@ void H::schur_symbolic() {
   const int np = B.n_rows, ncols = sp[1].n + sp[1].ng;
   // One rank (no ghost columns): the structural product on the device, with the row-product kernels of the AMG set-up
   // (hash sets in LDS, rows sorted) — 0.73 s of host work at 1200x400 otherwise, the longest item of the first set-up
-  // once the factors' analysis had moved to the device.  NSK_IOPT_HOST_ANALYSIS / NSK_HOST_ANALYSIS=1: the host loop.
-  static const bool host_only = [] { const char *e = getenv("NSK_HOST_ANALYSIS"); return e && atoi(e) != 0; }();
-  bool on_device = !host_only && !tS.host_analysis && sp[0].ng == 0 && sp[1].ng == 0 && B.n_cols == Bt.n_rows && np > 0;
+  // once the factors' analysis had moved to the device.  NSK_IOPT_HOST_ANALYSIS: the host loop.
+  bool on_device = !tS.host_analysis && sp[0].ng == 0 && sp[1].ng == 0 && B.n_cols == Bt.n_rows && np > 0;
   DBuf<int> rp_d, col_d;
   int64_t nnz_s = 0;
   if (on_device) {
@@ -526,7 +525,7 @@ void H::setup(int type, int variant_, double alpha_) {
     std::thread side;
     std::exception_ptr side_err;
     bool side_done_s = false;
-    if (type == 2 && (!tF_ok || tF_key != key) && (!tS_ok || tS_key != key) && std::getenv("NSK_SERIAL_SETUP") == nullptr) {
+    if (type == 2 && (!tF_ok || tF_key != key) && (!tS_ok || tS_key != key)) {
       side = std::thread([&] {
         try {
           (void)hipSetDevice(ctx.device);

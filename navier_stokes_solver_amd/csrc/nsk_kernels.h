@@ -239,7 +239,7 @@ void tri_stream_syncfree(hipStream_t s, const TriHalf &M, int n_blocks, int lowe
                          const double *own, double *w, double *reset /* gets the sentinel at the rows' positions */,
                          int *err, long long *dbg = nullptr /* diagnostics: 16 int64 per workgroup */,
                          TriChain chain = TriChain{1, nullptr, nullptr});
-// single-precision halves: built for the pair-wise loads only (NSK_TRI_WIDE=0 is ignored for them)
+// single-precision halves: the same pair-wise loads, values widened to double as they land
 void tri_stream_syncfree(hipStream_t s, const TriHalf32 &M, int n_blocks, int lower, int kind, int run_nnz,
                          int wrong_order, const double *dinv, const int *perm, const double *rhs, const double *own,
                          double *w, double *reset, int *err, long long *dbg, TriChain32 chain);
@@ -282,7 +282,7 @@ constexpr int kRingSlots = 16384;     // the ring: 128 KB of the CU's 160 KB of 
                                       // give-up word) — two epochs + the longest dependency must fit: with 8 192 slots the
                                       // 240-row levels of 1200x400 did not, and the solve fell back to the level walker
 constexpr int kRingDepth = 2;         // passes OF A GROUP whose records are in flight (registers)
-constexpr int kRingStep = 12;         // n_pass and epoch are multiples of this (any groups x depth the kernel is built for divides it)
+constexpr int kRingStep = 12;         // n_pass and epoch are multiples of this (and so of kRingGroups x kRingDepth)
 constexpr int kRingMaxEpoch = 48;     // passes between two workgroup barriers, at most (a multiple of kRingStep)
 constexpr int kRingMaxRows = 1 << 26; // (the header keeps a position in 26 bits)
 struct RingHalf {
@@ -292,7 +292,6 @@ struct RingHalf {
   const char *ent;            // 12-byte entries {double value; u32 LDS byte offset of the column's slot}
   const char *rowrec;         // [positions] 16 bytes {double diagonal; u32 byte offset of the result in dst; u32 LDS byte offset of the row's slot}
   const int2 *rearm;          // [n_pass / epoch + 1] positions {first, count} set back to NaN behind barrier k
-  unsigned long long *trace;  // diagnostics (NSK_RING_TRACE): 8 counters per wavefront, or null
 };
 // own: the row's own value (right-hand side / lower half's result) in POSITION order; dst: see RingHalf::rowrec
 // lower: dst = kind ? (own - s) / d : own - s ; upper: dst = kind ? own - s / d : (own - s) / d

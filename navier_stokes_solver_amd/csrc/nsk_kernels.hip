@@ -554,14 +554,13 @@ __device__ __forceinline__ double sf_wait(const double *p, unsigned long long fi
   return __longlong_as_double((long long)v);
 }
 
-// WIDE = 2 (default; NSK_TRI_WIDE=0 switches back): a lane takes PAIRS of consecutive entries (one 8-byte index load + one 16-byte value
-// load per pair, lanes on consecutive pairs) instead of one 4- / 8-byte load per entry — half the streaming instructions;
-// the products land in the same LDS words, the row sums read them in the same order: same bits.  Round 4 also measured a
-// thread taking its 8 entries CONSECUTIVELY (two 16-byte index + four 16-byte value loads): ILU(S) apply 0.459 -> 0.637 ms
-// at 1200x400, lanes 32 / 64 bytes apart touch four times the lines per instruction; removed again.
+// A lane takes PAIRS of consecutive entries (one 8-byte index load + one 16-byte value load per pair, lanes on consecutive
+// pairs): half the streaming instructions of one 4- / 8-byte load per entry (ILU(S) apply 0.449 -> 0.422 ms at 1200x400,
+// same bits).  Round 4 also measured a thread taking its 8 entries CONSECUTIVELY (two 16-byte index + four 16-byte value
+// loads): ILU(S) apply 0.459 -> 0.637 ms at 1200x400, lanes 32 / 64 bytes apart touch four times the lines per instruction.
 // V = float (factor stored in single precision): a pair is one 8-byte value load, still lane-contiguous; values are widened
-// to double as they land in registers.  Only WIDE = 2 is built for it.
-template <class V, int LOWER, int KIND, int NNZ, int GMAX, int WIDE>
+// to double as they land in registers.
+template <class V, int LOWER, int KIND, int NNZ, int GMAX>
 __global__ __launch_bounds__(BLK, 8) void tri_stream_sf_kernel(TriHalfT<V> M, const int4 *__restrict__ desc, int nb, int wrong_order,
                                                             const double *__restrict__ dinv,
                                                             const int *__restrict__ perm,
@@ -601,33 +600,22 @@ __global__ __launch_bounds__(BLK, 8) void tri_stream_sf_kernel(TriHalfT<V> M, co
     const char *wb = reinterpret_cast<const char *>(w);
     // entry u of this thread is entry idx(u) of the run
     const int tb = (int)threadIdx.x;
-    auto idx = [&](int u) { return WIDE == 2 ? 2 * (tb + (u >> 1) * BLK) + (u & 1) : tb + u * BLK; };
+    auto idx = [&](int u) { return 2 * (tb + (u >> 1) * BLK) + (u & 1); };
     {
       double v[U];
       unsigned long long g[U];
-      if (WIDE == 2) {
-        // pairs of consecutive entries, lanes on consecutive pairs: U / 2 index loads of 8 bytes + U / 2 value loads of 16
-        typedef int vi2 __attribute__((ext_vector_type(2)));
-        typedef V vd2 __attribute__((ext_vector_type(2)));
-        typedef vi2 vi2u __attribute__((aligned(4)));
-        typedef vd2 vd2u __attribute__((aligned(sizeof(V))));
+      // pairs of consecutive entries, lanes on consecutive pairs: U / 2 index loads of 8 bytes + U / 2 value loads of 16
+      typedef int vi2 __attribute__((ext_vector_type(2)));
+      typedef V vd2 __attribute__((ext_vector_type(2)));
+      typedef vi2 vi2u __attribute__((aligned(4)));
+      typedef vd2 vd2u __attribute__((aligned(sizeof(V))));
 #pragma unroll
-        for (int c = 0; c < U / 2; ++c) {
-          const int k = k0 + 2 * (tb + c * BLK), kk = (any && k < k1) ? k : kz;   // (the arrays end with spare entries)
-          const vi2 q = __builtin_nontemporal_load(reinterpret_cast<const vi2u *>(colp + kk));
-          const vd2 t = __builtin_nontemporal_load(reinterpret_cast<const vd2u *>(valp + kk));
-          o[2 * c] = (unsigned)q[0]; o[2 * c + 1] = (unsigned)q[1];
-          v[2 * c] = t[0]; v[2 * c + 1] = t[1];
-        }
-      } else {
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          // loads without branches or arithmetic on their results: all 2 U stay in flight.  A tail lane re-reads the
-          // run's first entry and is masked out below
-          const int k = k0 + (int)threadIdx.x + u * BLK, kk = k < k1 ? k : kz;
-          o[u] = (unsigned)__builtin_nontemporal_load(colp + kk);
-          v[u] = __builtin_nontemporal_load(valp + kk);
-        }
+      for (int c = 0; c < U / 2; ++c) {
+        const int k = k0 + 2 * (tb + c * BLK), kk = (any && k < k1) ? k : kz;   // (the arrays end with spare entries)
+        const vi2 q = __builtin_nontemporal_load(reinterpret_cast<const vi2u *>(colp + kk));
+        const vd2 t = __builtin_nontemporal_load(reinterpret_cast<const vd2u *>(valp + kk));
+        o[2 * c] = (unsigned)q[0]; o[2 * c + 1] = (unsigned)q[1];
+        v[2 * c] = t[0]; v[2 * c + 1] = t[1];
       }
       // row bounds, perm and the row's own right-hand side (which hangs on perm[r]) are asked for AFTER the streaming
       // loads have been issued, so that no wait stands between the descriptor and the stream: three dependent trips
@@ -657,8 +645,7 @@ __global__ __launch_bounds__(BLK, 8) void tri_stream_sf_kernel(TriHalfT<V> M, co
         const int k = idx(u);
         const bool op = g[u] == kSentinel && k < k1 - k0;
         open |= op ? 1u << u : 0u;
-        // (WIDE: unconditional, so that a thread's consecutive words go out as 16-byte LDS stores; words behind the run's
-        //  last entry are never read)
+        // (only the run's own entries are stored: the words behind its last entry are never read)
         if (k < k1 - k0) prod[k] = op ? v[u] : v[u] * __longlong_as_double((long long)g[u]);
       }
     }
@@ -1105,18 +1092,16 @@ __device__ __forceinline__ double ring_pair_partner(double v) {   // lane 2k rec
   return __hiloint2double(hi, lo);
 }
 
-template <int KIND, bool LOWER, int G, int D, bool TRACE>
-__global__ __launch_bounds__(64 * kRingWaves * G) void tri_ring_kernel(RingHalf R, const int2 *__restrict__ rearm, const uint4 *__restrict__ hdr,
+template <int KIND, bool LOWER>
+__global__ __launch_bounds__(kRingThreads) void tri_ring_kernel(RingHalf R, const int2 *__restrict__ rearm, const uint4 *__restrict__ hdr,
                                                                       const char *__restrict__ ent, const char *__restrict__ rowrec,
                                                                       const double *__restrict__ own_src, double *__restrict__ dst) {
   // (rearm, hdr, ent, rowrec = R's pointers once more, as restrict parameters: read-only and uniform => scalar loads)
   __shared__ double ring_lds[kRingSlots + 2];
-  constexpr int E = kRingRegs, kThreads = 64 * kRingWaves * G;
-  unsigned long long tr_wait = 0, tr_tries = 0, tr_comp = 0, tr_issue = 0, tr_rows = 0, tr_t0 = 0;
-  if (TRACE) tr_t0 = __builtin_amdgcn_s_memtime();
+  constexpr int E = kRingRegs;
   const int t = threadIdx.x, lane = t & 63;
   const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
-  const int group = wave / kRingWaves, wslot = wave % kRingWaves;   // this wavefront takes the passes q = group (mod G)
+  const int group = wave / kRingWaves, wslot = wave % kRingWaves;   // this wavefront takes the passes q = group (mod kRingGroups)
   const double nan_v = __longlong_as_double((long long)kSentinel);
   // (LDS pointers keep their address space: through a generic pointer every access would be a FLAT instruction that
   //  waits for all vector-memory traffic — the records in flight)
@@ -1124,13 +1109,13 @@ __global__ __launch_bounds__(64 * kRingWaves * G) void tri_ring_kernel(RingHalf 
   using lds_double = __attribute__((address_space(3))) double;
   using lds_int = __attribute__((address_space(3))) int;
   lds_char *const lds = (lds_char *)ring_lds;
-  for (int k = t; k < kRingSlots; k += kThreads) ring_lds[1 + k] = nan_v;
+  for (int k = t; k < kRingSlots; k += kRingThreads) ring_lds[1 + k] = nan_v;
   if (t == 0) { ring_lds[0] = 0.0; ring_lds[kRingSlots + 1] = 0.0; }
   volatile lds_int *const give_up = (volatile lds_int *)(lds + 8 * (kRingSlots + 1));
 
-  // per stage: the records of one pass (registers); per stage one header in flight for the pass D of this group's later
-  unsigned e_lo[D][E], e_hi[D][E], e_off[D][E], rr[D][4], n_lanes[D];
-  unsigned hx[D], hy[D], hz[D];
+  // per stage: the records of one pass (registers), and one header in flight for this group's pass kRingDepth passes later
+  unsigned e_lo[kRingDepth][E], e_hi[kRingDepth][E], e_off[kRingDepth][E], rr[kRingDepth][4], n_lanes[kRingDepth];
+  unsigned hx[kRingDepth], hy[kRingDepth], hz[kRingDepth];
   const unsigned vo12 = (unsigned)lane * 12u;
   auto load_hdr = [&](int slot, int q) {   // (uniform address, read-only, restrict: a scalar load)
     const uint4 h = hdr[q * kRingWaves + wslot];
@@ -1176,11 +1161,8 @@ __global__ __launch_bounds__(64 * kRingWaves * G) void tri_ring_kernel(RingHalf 
     const unsigned nl = n_lanes[slot];
     const bool rowlane = (lane & 1) == 0 && (unsigned)lane < nl;
     double u = 0.0;
-    unsigned long long tw0 = 0;
-    if (TRACE) { tw0 = __builtin_amdgcn_s_memtime(); tr_rows += nl != 0; }
     if (nl != 0) {   // (wavefront-uniform; no vector-memory instruction inside: the counts the waits rely on stay static)
       for (int tries = 0;;) {
-        if (TRACE) ++tr_tries;
         double x[E], s[4];
 #pragma unroll
         for (int r = 0; r < E; ++r) x[r] = *(volatile lds_double *)(lds + e_off[slot][r]);
@@ -1197,7 +1179,6 @@ __global__ __launch_bounds__(64 * kRingWaves * G) void tri_ring_kernel(RingHalf 
         if ((++tries & 63) == 0 && (*give_up != 0 || tries >= kRingSpinLimit)) { *give_up = 1; break; }
       }
     }
-    if (TRACE) tr_wait += __builtin_amdgcn_s_memtime() - tw0;
     // the row's own value sits in the pair's odd lane, the row record in its even one
     const double own = ring_pair_partner(__hiloint2double((int)rr[slot][1], (int)rr[slot][0]));
     if (rowlane) {
@@ -1208,48 +1189,40 @@ __global__ __launch_bounds__(64 * kRingWaves * G) void tri_ring_kernel(RingHalf 
       *(lds_double *)(lds + rr[slot][3]) = res;
       *reinterpret_cast<double *>(reinterpret_cast<char *>(dst) + rr[slot][2]) = res;
     }
-    if (TRACE) tr_comp += __builtin_amdgcn_s_memtime() - tw0;
   };
-  // own index j of this group = pass G * j + group
+  // own index j of this group = pass kRingGroups * j + group
 #pragma unroll
-  for (int d = 0; d < D; ++d) load_hdr(d, G * d + group);
+  for (int d = 0; d < kRingDepth; ++d) load_hdr(d, kRingGroups * d + group);
   // (scheduling barriers: the loop's waits count the loads issued since a stage's records — the prologue has to issue
   //  them in the loop's order, or the merged count at the loop head is the prologue's and every pass over-waits)
 #pragma unroll
-  for (int d = 0; d < D; ++d) {
+  for (int d = 0; d < kRingDepth; ++d) {
     __builtin_amdgcn_sched_barrier(0);
     issue(d);
-    load_hdr(d, G * (D + d) + group);
+    load_hdr(d, kRingGroups * (kRingDepth + d) + group);
     __builtin_amdgcn_sched_barrier(0);
   }
   __syncthreads();
   int next_barrier = R.epoch, epoch_id = 1;
-  for (int q0 = 0; q0 < R.n_pass; q0 += G * D) {   // n_pass and epoch are multiples of G * D
+  for (int q0 = 0; q0 < R.n_pass; q0 += kRingGroups * kRingDepth) {   // n_pass and epoch are multiples of kRingGroups * kRingDepth
     if (q0 == next_barrier) {
       // everything before pass q0 is done by everybody: the slots of the epoch AFTER this one can be set back to NaN
       // (their old occupants were last read before this barrier — the analysis checked it), and nobody looks at them
       // before the next barrier
       __syncthreads();
       const int2 ra = rearm[epoch_id];
-      for (int k = t; k < ra.y; k += kThreads) ring_lds[1 + ((ra.x + k) & (kRingSlots - 1))] = nan_v;
+      for (int k = t; k < ra.y; k += kRingThreads) ring_lds[1 + ((ra.x + k) & (kRingSlots - 1))] = nan_v;
       next_barrier += R.epoch;
       ++epoch_id;
     }
 #pragma unroll
-    for (int d = 0; d < D; ++d) {
-      compute(d);                      // pass q0 + G * d + group
+    for (int d = 0; d < kRingDepth; ++d) {
+      compute(d);                      // pass q0 + kRingGroups * d + group
       __builtin_amdgcn_sched_barrier(0);
-      unsigned long long ti0 = 0;
-      if (TRACE) ti0 = __builtin_amdgcn_s_memtime();
-      issue(d);                        // D of this group's passes later
-      load_hdr(d, q0 + G * (d + 2 * D) + group);
-      if (TRACE) tr_issue += __builtin_amdgcn_s_memtime() - ti0;
+      issue(d);                        // kRingDepth of this group's passes later
+      load_hdr(d, q0 + kRingGroups * (d + 2 * kRingDepth) + group);
       __builtin_amdgcn_sched_barrier(0);
     }
-  }
-  if (TRACE && R.trace && lane == 0) {
-    unsigned long long *o = R.trace + 8 * wave;
-    o[0] = tr_wait; o[1] = tr_tries; o[2] = tr_comp; o[3] = tr_issue; o[4] = tr_rows; o[5] = __builtin_amdgcn_s_memtime() - tr_t0;
   }
 }
 
@@ -1418,15 +1391,12 @@ void spmv_stream(hipStream_t s, const CsrView &A, const int *rowblk, int nblk, i
                  const double *xg, double *y, int mode, const double *z) {
   if (nblk <= 0) return;
 #define NSK_SS(V, M) hipLaunchKernelGGL((spmv_stream_kernel<double, V, M>), dim3(nblk), dim3(BLK), 0, s, A, rowblk, xo, xg, y, z)
-  // pairs of entries per lane also where the row pointers are not all even (S: 0.271 -> 0.264 ms at 1200x400);
-  // NSK_SPMV_WIDE=0: one entry per load there, as in rounds 1-3 (A/B measurements)
-  static const bool wide = [] { const char *e = getenv("NSK_SPMV_WIDE"); return !e || atoi(e) != 0; }();
-  if (wide && !even_rows) {
-    if (mode == 0) NSK_SS(3, 0); else if (mode == 1) NSK_SS(3, 1); else NSK_SS(3, 2);
-  } else if (even_rows) {
+  // pairs of entries per lane: 16-byte aligned where every row pointer is even, 4- / 8-byte aligned loads otherwise
+  // (S: 0.271 -> 0.264 ms at 1200x400 against one entry per load)
+  if (even_rows) {
     if (mode == 0) NSK_SS(2, 0); else if (mode == 1) NSK_SS(2, 1); else NSK_SS(2, 2);
   } else {
-    if (mode == 0) NSK_SS(1, 0); else if (mode == 1) NSK_SS(1, 1); else NSK_SS(1, 2);
+    if (mode == 0) NSK_SS(3, 0); else if (mode == 1) NSK_SS(3, 1); else NSK_SS(3, 2);
   }
 #undef NSK_SS
 }
@@ -1434,13 +1404,11 @@ void spmv_stream(hipStream_t s, const CsrView &A, const int *rowblk, int nblk, i
 void spmv_stream(hipStream_t s, const CsrView32 &A, const int *rowblk, int nblk, int even_rows, const double *xo,
                  const double *xg, double *y) {
   if (nblk <= 0) return;
-  // the double launcher's choice of pair loads (NSK_SPMV_WIDE included): the same lanes sum the same entries
-  static const bool wide = [] { const char *e = getenv("NSK_SPMV_WIDE"); return !e || atoi(e) != 0; }();
+  // the double launcher's choice of pair loads: the same lanes sum the same entries
   const double *z = nullptr;
 #define NSK_SS(V) hipLaunchKernelGGL((spmv_stream_kernel<float, V, 0>), dim3(nblk), dim3(BLK), 0, s, A, rowblk, xo, xg, y, z)
-  if (wide && !even_rows) NSK_SS(3);
-  else if (even_rows) NSK_SS(2);
-  else NSK_SS(1);
+  if (even_rows) NSK_SS(2);
+  else NSK_SS(3);
 #undef NSK_SS
 }
 
@@ -1605,17 +1573,7 @@ static void tri_stream_syncfree_t(hipStream_t s, const TriHalfT<V> &M, int nb, i
                                   int wrong_order, const double *dinv, const int *perm, const double *rhs, const double *own,
                                   double *w, double *reset, int *err, long long *dbg, TriChainT<V> ch) {
   if (nb <= 0) return;
-  // pairs of consecutive entries per lane (ILU(S) apply 0.449 -> 0.422 ms at 1200x400, same bits); NSK_TRI_WIDE=0: one 4- /
-  // 8-byte load per entry, the kernels of rounds 1-3 (A/B measurements).  Single-precision halves exist for the pairs only
-  // (half the instantiations, half the build time): NSK_TRI_WIDE=0 takes WIDE = 2 for them
-  static const int wide = [] { const char *e = getenv("NSK_TRI_WIDE"); return e ? atoi(e) : 2; }();
-#define NSK_SF_LAUNCH(W, L, K, N, G) hipLaunchKernelGGL((tri_stream_sf_kernel<V, L, K, N, G, W>), dim3(nb), dim3(BLK), 0, s, M, M.desc, nb, wrong_order, dinv, perm, rhs, own, w, reset, err, dbg, ch.chain, ch.cpl)
-#define NSK_SF(L, K, N, G)                                   \
-  do {                                                       \
-    if constexpr (std::is_same<V, float>::value) NSK_SF_LAUNCH(2, L, K, N, G); \
-    else if (wide == 2) NSK_SF_LAUNCH(2, L, K, N, G);        \
-    else NSK_SF_LAUNCH(0, L, K, N, G);                       \
-  } while (0)
+#define NSK_SF(L, K, N, G) hipLaunchKernelGGL((tri_stream_sf_kernel<V, L, K, N, G>), dim3(nb), dim3(BLK), 0, s, M, M.desc, nb, wrong_order, dinv, perm, rhs, own, w, reset, err, dbg, ch.chain, ch.cpl)
 #define NSK_SFG(L, K, N)                                   \
   do {                                                     \
     if (ch.gmax <= 1) NSK_SF(L, K, N, 1);                  \
@@ -1633,7 +1591,6 @@ static void tri_stream_syncfree_t(hipStream_t s, const TriHalfT<V> &M, int nb, i
 #undef NSK_SFN
 #undef NSK_SFG
 #undef NSK_SF
-#undef NSK_SF_LAUNCH
 }
 void tri_stream_syncfree(hipStream_t s, const TriHalf &M, int nb, int lower, int kind, int run_nnz, int wrong_order,
                          const double *dinv, const int *perm, const double *rhs, const double *own, double *w,
@@ -1753,16 +1710,12 @@ namespace {
 inline bool aligned16(const void *a, const void *b = nullptr, const void *c = nullptr, const void *d = nullptr) {
   return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d) & 15u) == 0;
 }
-bool blas1_pairs(const ReduceWs &ws) {   // the handle's choice (NSK_OPT_BLAS1_PAIRS); NSK_BLAS1_PAIRS=0/1 overrides it (A/B measurements)
-  static const int forced = [] { const char *e = getenv("NSK_BLAS1_PAIRS"); return e ? (atoi(e) != 0 ? 1 : 0) : -1; }();
-  return forced >= 0 ? forced != 0 : ws.pairs != 0;
-}
 typedef const double2 *cd2;
 }  // namespace
 
 int vec_dot(hipStream_t s, const ReduceWs &ws, int n, const double *x, const double *y, double *out, int want_sqrt) {
   auto f1 = [=] __device__(int i) -> double { return x[i] * y[i]; };
-  if (blas1_pairs(ws) && aligned16(x, y) && n >= 2) {
+  if (ws.pairs && aligned16(x, y) && n >= 2) {
     NSK_RED2(n, ([=] __device__(int j) -> double {
                const double2 a = cd2(x)[j], b = cd2(y)[j];
                return a.x * b.x + a.y * b.y;
@@ -1774,7 +1727,7 @@ int vec_dot(hipStream_t s, const ReduceWs &ws, int n, const double *x, const dou
 }
 int vec_axpy_dot(hipStream_t s, const ReduceWs &ws, int n, SRef a, const double *x, double *y, const double *w,
                  double *out, int want_sqrt) {
-  const bool pairs = blas1_pairs(ws) && aligned16(x, y, w) && n >= 2;
+  const bool pairs = ws.pairs && aligned16(x, y, w) && n >= 2;
   if (w == y) {
     auto f1 = [=] __device__(int i) -> double {
       const double v = y[i] + sval(a) * x[i];
@@ -1822,7 +1775,7 @@ int vec_cg_update(hipStream_t s, const ReduceWs &ws, int n, SRef a, const double
     g[i] = v;
     return v * v;
   };
-  if (blas1_pairs(ws) && aligned16(d, h, x, g) && n >= 2) {
+  if (ws.pairs && aligned16(d, h, x, g) && n >= 2) {
     NSK_RED2(n, ([=] __device__(int j) -> double {
                const double al = sval(a);
                const double2 dv = cd2(d)[j], hv = cd2(h)[j];
@@ -1996,7 +1949,7 @@ bool pack_aligned16(const double *w, const VecPack &P, int m) {
 }  // namespace
 int vec_multi_dot(hipStream_t s, const ReduceWs &ws, int n, const double *w, const VecPack &P, int m, double *out) {
   if (m < 1 || m > 8) return 0;
-  if (blas1_pairs(ws) && n >= 2 && pack_aligned16(w, P, m)) {
+  if (ws.pairs && n >= 2 && pack_aligned16(w, P, m)) {
 #define NSK_MD(M) case M: hipLaunchKernelGGL((multi_dot2_kernel<M>), dim3(red_grid_pairs(n, 256)), dim3(RBLK), 0, s, n, w, P, ws, out); break;
     switch (m) { NSK_MD(1) NSK_MD(2) NSK_MD(3) NSK_MD(4) NSK_MD(5) NSK_MD(6) NSK_MD(7) NSK_MD(8) default: break; }
 #undef NSK_MD
@@ -2011,7 +1964,7 @@ int vec_multi_axpy(hipStream_t s, const ReduceWs &ws, int n, double *w, const Ve
                    double *norm_out) {
   if (m < 1 || m > 8) return 0;
   // (without the norm the update is entry by entry: the same bits in pairs, whatever the handle chose for the sums)
-  if ((!norm_out || blas1_pairs(ws)) && n >= 2 && pack_aligned16(w, P, m)) {
+  if ((!norm_out || ws.pairs) && n >= 2 && pack_aligned16(w, P, m)) {
 #define NSK_MA(M)                                                                                                \
   case M:                                                                                                        \
     if (norm_out) hipLaunchKernelGGL((multi_axpy2_kernel<M, true>), dim3(red_grid_pairs(n, 256)), dim3(RBLK), 0, s, n, w, P, h, ws, norm_out); \
@@ -2031,48 +1984,12 @@ int vec_multi_axpy(hipStream_t s, const ReduceWs &ws, int n, double *w, const Ve
   return kRedScalar;
 }
 
-namespace {
-template <int G, int D, bool TRACE>
-void launch_ring(hipStream_t s, const RingHalf &R, int lower, int kind, const double *own, double *dst) {
-#define NSK_RING(K, L) hipLaunchKernelGGL((tri_ring_kernel<K, L, G, D, TRACE>), dim3(1), dim3(64 * kRingWaves * G), 0, s, R, R.rearm, R.hdr, R.ent, R.rowrec, own, dst)
+void tri_ring(hipStream_t s, const RingHalf &R, int lower, int kind, const double *own, double *dst) {
+  if (R.n_pass <= 0) return;
+#define NSK_RING(K, L) hipLaunchKernelGGL((tri_ring_kernel<K, L>), dim3(1), dim3(kRingThreads), 0, s, R, R.rearm, R.hdr, R.ent, R.rowrec, own, dst)
   if (lower) { if (kind == 0) NSK_RING(0, true); else NSK_RING(1, true); }
   else { if (kind == 0) NSK_RING(0, false); else NSK_RING(1, false); }
 #undef NSK_RING
-}
-}  // namespace
-void tri_ring(hipStream_t s, const RingHalf &R0, int lower, int kind, const double *own, double *dst) {
-  if (R0.n_pass <= 0) return;
-  // study switches: NSK_RING_SHAPE = "groups,depth" (1,2 | 1,3 | 1,4 | 2,2 default), NSK_RING_TRACE = 1 prints in-kernel counters
-  static const int shape = [] { const char *e = getenv("NSK_RING_SHAPE"); int g = kRingGroups, d = kRingDepth; if (e) sscanf(e, "%d,%d", &g, &d); return g * 10 + d; }();
-  static const bool trace = getenv("NSK_RING_TRACE") != nullptr;
-  RingHalf R = R0;
-  static unsigned long long *tbuf = nullptr;
-  if (trace) {
-    if (!tbuf) (void)hipMalloc((void **)&tbuf, sizeof(unsigned long long) * 8 * 16);
-    (void)hipMemsetAsync(tbuf, 0, sizeof(unsigned long long) * 8 * 16, s);
-    R.trace = tbuf;
-    switch (shape) {
-      case 14: launch_ring<1, 4, true>(s, R, lower, kind, own, dst); break;
-      case 12: launch_ring<1, 2, true>(s, R, lower, kind, own, dst); break;
-      case 13: launch_ring<1, 3, true>(s, R, lower, kind, own, dst); break;
-      default: launch_ring<2, 2, true>(s, R, lower, kind, own, dst); break;
-    }
-    unsigned long long h[8 * 16];
-    (void)hipStreamSynchronize(s);
-    (void)hipMemcpy(h, tbuf, sizeof(h), hipMemcpyDeviceToHost);
-    fprintf(stderr, "[ring trace] %s half, shape %d, %d passes, epoch %d\n", lower ? "lower" : "upper", shape, R.n_pass, R.epoch);
-    for (int w = 0; w < 16; ++w)
-      if (h[8 * w + 5])
-        fprintf(stderr, "  wave %2d: kernel %9llu ticks, compute %9llu (of which waiting for operands incl. first look %9llu, %7llu looks), fetch %9llu, passes with rows %6llu\n",
-                w, h[8 * w + 5], h[8 * w + 2], h[8 * w + 0], h[8 * w + 1], h[8 * w + 3], h[8 * w + 4]);
-    return;
-  }
-  switch (shape) {
-    case 14: launch_ring<1, 4, false>(s, R, lower, kind, own, dst); break;
-    case 12: launch_ring<1, 2, false>(s, R, lower, kind, own, dst); break;
-    case 13: launch_ring<1, 3, false>(s, R, lower, kind, own, dst); break;
-    default: launch_ring<2, 2, false>(s, R, lower, kind, own, dst); break;
-  }
 }
 void mem_touch(hipStream_t s, const TouchRanges &R, unsigned *sink) {
   size_t lines = 0;

@@ -8,7 +8,7 @@
 // these kernels build the same arrays there.  One wavefront per row; a row's (at most 448) column ids are staged in LDS
 // and every entry finds its place by counting the smaller ones (the ids of a row are distinct), which is a few thousand
 // broadcast LDS reads per row and no sort network.  The results are the host path's arrays entry for entry
-// (tests/test_gpu_setup.py compares them; NSK_HOST_ANALYSIS=1 selects the host path).
+// (tests/test_gpu_setup.py compares them; NSK_IOPT_HOST_ANALYSIS selects the host path).
 #include "nsk_kernels.h"
 
 namespace nsk {

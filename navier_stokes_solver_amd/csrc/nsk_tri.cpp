@@ -419,9 +419,8 @@ void TriSolve::analyze(Ctx *c, const Csr &A, int kind_, int ordering_, const std
   }
   // Multicolour factors without line groups, nothing dropped from the block: the permuted pattern and the split halves
   // are built ON THE DEVICE from the block's own pattern, which is there already (nsk_setup_kernels.hip) — the host
-  // builds no array of the factor's size.  NSK_HOST_ANALYSIS=1: the host path below (A/B, and what the tests compare with)
-  static const bool host_only = [] { const char *e = getenv("NSK_HOST_ANALYSIS"); return e && atoi(e) != 0; }();
-  const bool dev = !host_only && !host_analysis && !perm.empty() && gmax == 1 && O.identity && A.rowptr.p && A.col.p && (int64_t)A.nnz == (int64_t)nnz &&
+  // builds no array of the factor's size.  host_analysis (NSK_IOPT_HOST_ANALYSIS): the host path below (what the tests compare with)
+  const bool dev = !host_analysis && !perm.empty() && gmax == 1 && O.identity && A.rowptr.p && A.col.p && (int64_t)A.nnz == (int64_t)nnz &&
                    maxw <= 448 && n > 0;
   hipStream_t s = ctx->stream;
   bool missing_diag = false;
@@ -833,29 +832,10 @@ void TriSolve::analyze(Ctx *c, const Csr &A, int kind_, int ordering_, const std
           const int o = (int)P.order.size();
           P.pass_first.push_back(o);
           P.order.insert(P.order.end(), lr.begin() + b, lr.begin() + b + cnt);
-          // longest rows first (ties: row order); a wavefront's chunk is padded to its longest row.  Rows of one length CAN
-          // get wavefronts of their own while the pass has wavefronts to spare (NSK_RING_BY_CLASS=1: no padding at all) —
-          // measured slower, 2.86 against 2.79 ms per application at 600x200: seven thinly filled wavefronts per level
-          // issue more loads than five full ones, and the loads are what a level costs
+          // longest rows first (ties: row order); every wavefront takes 32 rows and pads its chunk to its longest row
+          // (wavefronts of one row length each, without padding, measured slower: 2.86 against 2.79 ms per application at 600x200)
           std::stable_sort(P.order.begin() + o, P.order.end(), [&](int x, int y) { return regs_of(x) > regs_of(y); });
-          int waves_by_class = 0;
-          for (int p = o; p < o + cnt;) {
-            int e = p;
-            while (e < o + cnt && regs_of(P.order[e]) == regs_of(P.order[p])) ++e;
-            waves_by_class += (e - p + kRingRowsPerWave - 1) / kRingRowsPerWave;
-            p = e;
-          }
-          static const bool want_by_class = [] { const char *e = getenv("NSK_RING_BY_CLASS"); return e && atoi(e) != 0; }();
-          const bool by_class = want_by_class && waves_by_class <= kRingWaves;
-          int p = o;
-          for (int w = 0; w < kRingWaves; ++w) {
-            P.wave_first.push_back(p);
-            int e = std::min(o + cnt, p + kRingRowsPerWave);
-            if (by_class)
-              for (int k = p; k < e; ++k) if (regs_of(P.order[k]) != regs_of(P.order[p])) { e = k; break; }
-            p = e;
-          }
-          P.wave_first.push_back(p);   // (== o + cnt: by class when that needs no more than kRingWaves wavefronts, else 32 rows each)
+          for (int w = 0; w <= kRingWaves; ++w) P.wave_first.push_back(o + std::min(cnt, w * kRingRowsPerWave));
         }
       P.pass_first.push_back((int)P.order.size());
       for (int p = 0; p < n; ++p) P.pos[P.order[p]] = p;
@@ -1129,13 +1109,11 @@ void TriSolve::apply(const double *b, double *x) {
     return;
   }
   if (ring_ready && use_stream && !tiny) {   // the caller's order: one workgroup, passes through an LDS ring
-    // a half's records into the memory-side cache with the whole chip, right before its one workgroup starts
-    // (NSK_RING_PREFETCH=0: off): in a solver gigabytes have streamed through that cache since the last application,
-    // and one CU fetching from HBM is what then bounds the solve (3.8 against 2.7 ms at 600x200).  Half
-    // by half, so that factors of up to ~200 MB per half still find room in its 256 MB
-    static const bool prefetch = [] { const char *e = getenv("NSK_RING_PREFETCH"); return !e || atoi(e) != 0; }();
+    // a half's records into the memory-side cache with the whole chip, right before its one workgroup starts: in a
+    // solver gigabytes have streamed through that cache since the last application, and one CU fetching from HBM is
+    // what then bounds the solve (3.8 against 2.7 ms at 600x200).  Half by half, so that factors of up
+    // to ~200 MB per half still find room in its 256 MB
     auto touch = [&](const Ring &Rg) {
-      if (!prefetch) return;
       if (!touch_sink.p) touch_sink.alloc(1);
       const TouchRanges R{{Rg.ent.p, Rg.rowrec.p, (const char *)Rg.hdr.p, nullptr, nullptr, nullptr},
                           {(size_t)Rg.n_ent * 12, (size_t)n * 16, (size_t)Rg.n_pass * kRingWaves * 16, 0, 0, 0}};

@@ -109,7 +109,7 @@ struct TriSolve {
     DBuf<int> rowid;           // [positions] the row at that position (gathers the right-hand side into position order)
     DBuf<double> own;          // [positions]
     DBuf<int2> rearm;
-    RingHalf view() const { return RingHalf{n_pass, epoch, hdr.p, ent.p, rowrec.p, rearm.p, nullptr}; }
+    RingHalf view() const { return RingHalf{n_pass, epoch, hdr.p, ent.p, rowrec.p, rearm.p}; }
   } ringL, ringU;
   bool ring_ready = false;
   DBuf<unsigned> touch_sink;   // (mem_touch's never-written word)
