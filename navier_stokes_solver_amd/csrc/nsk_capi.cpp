@@ -85,6 +85,15 @@ struct EventSampler {
   }
 };
 
+// Row runs of the fused velocity block row y_u = F x_u + Bt x_p: the cap bounds both matrices' entries together
+// (jacobian_vmult; the test hook nsk_debug_spmv builds its two-matrix plans with the same calls)
+static bool fused_blk_plan(const Csr &F, const Csr &Bt, std::vector<int> &rb) {
+  return build_rowblocks(F.h_blk_rowptr.data(), Bt.h_blk_rowptr.data(), F.blk_rows, kBlkMax, nullptr, rb);
+}
+static bool fused_row_plan(const Csr &F, const Csr &Bt, std::vector<int> &rb) {
+  return build_rowblocks(F.h_rowptr.data(), Bt.h_rowptr.data(), F.n_rows, kStreamNnz, nullptr, rb);
+}
+
 struct nsk_handle_s {
   Ctx ctx;
   EventSampler sampler;
@@ -308,7 +317,7 @@ struct nsk_handle_s {
                          F.blk_rows == Bt.blk_rows;
     if (fuse_block_row && blocked && !jblk_ok && jblk_nblk == 0) {
       std::vector<int> rb;
-      if (build_rowblocks(F.h_blk_rowptr.data(), Bt.h_blk_rowptr.data(), F.blk_rows, kBlkMax, nullptr, rb)) {
+      if (fused_blk_plan(F, Bt, rb)) {
         jblk_nblk = (int)rb.size() - 1;
         jblk_blk.upload(rb, s());
         ctx.sync();
@@ -317,7 +326,7 @@ struct nsk_handle_s {
     }
     if (fuse_block_row && use_stream && !jrow_ok && jrow_nblk == 0 && F.even_rows) {
       std::vector<int> rb;
-      if (build_rowblocks(F.h_rowptr.data(), Bt.h_rowptr.data(), F.n_rows, kStreamNnz, nullptr, rb)) {
+      if (fused_row_plan(F, Bt, rb)) {
         jrow_nblk = (int)rb.size() - 1;
         jrow_blk.upload(rb, s());
         ctx.sync();
@@ -1836,6 +1845,203 @@ int nsk_debug_krylov(nsk_handle h, int op, int n, int m, int offset, const doubl
   info8[2] = std::min(c.n_cu, kMgsThreads);
   info8[3] = bad_guards;
   for (int k = 4; k < 8; ++k) info8[k] = 0;
+  return 0;
+  NSK_CATCH(h)
+}
+
+// test hook (nsk_internal.h): one SpMV kernel form on the caller's CSR, through the plan builders and launchers the handle uses
+namespace {
+constexpr int kDbgFront = 2, kDbgBack = 4;   // guard words before (16 bytes: the alignment stays) and behind a vector
+struct DbgVec {   // a device vector in an allocation of its own, guard words (all bits set) on both sides
+  DBuf<double> buf;
+  double *p = nullptr;
+  size_t len = 0;
+  int off = 0;
+  void put(const double *h, size_t n, int offset, hipStream_t st) {
+    len = n;
+    off = kDbgFront + offset;
+    buf.alloc(len + off + kDbgBack);
+    NSK_HIP(hipMemsetAsync(buf.p, 0xFF, sizeof(double) * buf.n, st));
+    p = buf.p + off;
+    if (len) NSK_HIP(hipMemcpyAsync(p, h, sizeof(double) * len, hipMemcpyHostToDevice, st));
+  }
+  // guard words that changed; out (may be null) receives the vector
+  int fetch(double *out, Ctx &c) {
+    if (!buf.p) return 0;
+    std::vector<double> all(buf.n);
+    NSK_HIP(hipMemcpyAsync(all.data(), buf.p, sizeof(double) * all.size(), hipMemcpyDeviceToHost, c.stream));
+    c.sync();
+    if (out) std::copy(all.begin() + off, all.begin() + off + len, out);
+    int bad = 0;
+    for (size_t i = 0; i < all.size(); ++i) {
+      if (i == (size_t)off) i += len;
+      if (i < all.size()) {
+        uint64_t bits;
+        memcpy(&bits, &all[i], 8);
+        bad += bits != ~0ull;
+      }
+    }
+    return bad;
+  }
+};
+
+// what nsk_set_block_csr does with a block, on a Csr of the hook's own
+void dbg_fill_csr(Csr &A, const nsk_dbg_spmv_mat &M, hipStream_t st) {
+  if (M.n_rows < 1 || M.n_cols < 0 || M.n_own_cols < 0 || M.n_own_cols > M.n_cols || M.rowptr[0] != 0)
+    throw Error(-61, "nsk_debug_spmv: matrix shape");
+  for (int i = 0; i < M.n_rows; ++i)
+    if (M.rowptr[i + 1] < M.rowptr[i]) throw Error(-58, "nsk_debug_spmv: rowptr not monotone");
+  const int64_t nnz = M.rowptr[M.n_rows];
+  for (int64_t k = 0; k < nnz; ++k)
+    if (M.col[k] < 0 || M.col[k] >= M.n_cols) throw Error(-59, "nsk_debug_spmv: column id out of range");
+  A.n_rows = M.n_rows;
+  A.n_cols = M.n_cols;
+  A.n_own_cols = M.n_own_cols;
+  A.nnz = nnz;
+  A.h_rowptr.assign(M.rowptr, M.rowptr + M.n_rows + 1);
+  A.h_col.assign(M.col, M.col + nnz);
+  A.rowptr.upload(M.rowptr, (size_t)M.n_rows + 1, st);
+  A.col.upload(M.col, (size_t)nnz, st);
+  A.val.upload(M.val, (size_t)nnz, st);
+  ++A.values_version;
+  A.lpr = pick_lpr(nnz, M.n_rows);
+  A.present = true;
+  A.build_stream_plan(st);
+}
+}  // namespace
+
+int nsk_debug_spmv(nsk_handle h, int form, int lpr, int mode, int misalign, int c0, int c1, const nsk_dbg_spmv_mat *Am,
+                   const nsk_dbg_spmv_mat *Bm, double *y, const double *z, const double *d, const double *dinv,
+                   int32_t *rowblk_out, int rowblk_cap, int32_t *info) {
+  NSK_TRY(h)
+  (void)hipSetDevice(h->ctx.device);
+  Ctx &c = h->ctx;
+  hipStream_t st = h->s();
+  for (int k = 0; k < 16; ++k) info[k] = 0;
+  info[0] = -1;
+  if (form < NSK_DBG_SPMV_CSRV || form > NSK_DBG_SPMV_BLK_FUSED) throw Error(-65, "nsk_debug_spmv: unknown form");
+  const bool two = form == NSK_DBG_SPMV_STREAM2 || form == NSK_DBG_SPMV_BLK_FUSED;
+  const bool modes = form == NSK_DBG_SPMV_CSRV || form == NSK_DBG_SPMV_STREAM;
+  const bool epi = form == NSK_DBG_SPMV_BLK21_EPI;
+  if (!Am || !y || two != (Bm != nullptr)) throw Error(-61, "nsk_debug_spmv: matrices");
+  if (mode < 0 || mode > 2 || (mode != 0 && !modes) || (mode == 2 && !z)) throw Error(-61, "nsk_debug_spmv: mode");
+  if (epi && !(d && dinv)) throw Error(-61, "nsk_debug_spmv: the epilogue needs d and dinv");
+  if ((two || form == NSK_DBG_SPMV_CSRV) && c0 >= 0) throw Error(-61, "nsk_debug_spmv: this form runs whole plans only");
+  int R = 1, C = 1;
+  if (form == NSK_DBG_SPMV_BLK22 || form == NSK_DBG_SPMV_BLK22_F32 || form == NSK_DBG_SPMV_BLK_FUSED) R = C = 2;
+  if (form == NSK_DBG_SPMV_BLK21 || epi) R = 2;
+  if (form == NSK_DBG_SPMV_BLK12) C = 2;
+  const bool blocked = form >= NSK_DBG_SPMV_BLK22 && form != NSK_DBG_SPMV_STREAM2;
+  if ((misalign & 4) && R == 2) throw Error(-61, "nsk_debug_spmv: the R = 2 forms store pairs, y is 16-byte aligned");
+  if (two && Bm->n_rows != Am->n_rows) throw Error(-61, "nsk_debug_spmv: both matrices over the same rows");
+
+  Csr A, B;
+  dbg_fill_csr(A, *Am, st);
+  if (two) dbg_fill_csr(B, *Bm, st);
+  info[2] = A.lpr;
+  info[3] = R;
+  info[4] = C;
+  info[5] = A.stream_ok;
+  info[6] = A.stream_ok && A.even_rows;
+
+  // the plan of the form: rb (host copy of the runs), entries per run from ea (+ eb)
+  std::vector<int> rb;
+  const std::vector<int> *ea = &A.h_rowptr, *eb = nullptr;
+  DBuf<int> fused_rb;
+  const int *d_rb = nullptr;
+  int ib0 = 0, ib1 = 0, refused = 0;
+  auto download = [&](const DBuf<int> &src, int nblk) {
+    rb.resize((size_t)nblk + 1);
+    NSK_HIP(hipMemcpyAsync(rb.data(), src.p, sizeof(int) * rb.size(), hipMemcpyDeviceToHost, st));
+    c.sync();
+    d_rb = src.p;
+  };
+  if (form == NSK_DBG_SPMV_STREAM || form == NSK_DBG_SPMV_STREAM_F32) {
+    if (!A.stream_ok) refused = 1;
+    else { download(A.rowblk, A.nblk); ib0 = A.int_b0; ib1 = A.int_b1; }
+  } else if (form == NSK_DBG_SPMV_STREAM2) {
+    if (!A.even_rows) refused = 3;   // (jacobian_vmult asks for F.even_rows: the kernel reads F in aligned pairs)
+    else if (!fused_row_plan(A, B, rb)) refused = 4;
+    else { eb = &B.h_rowptr; fused_rb.upload(rb, st); d_rb = fused_rb.p; ib1 = (int)rb.size() - 1; }
+  } else if (blocked) {
+    A.build_blocked(R, C, st);
+    if (two) B.build_blocked(2, 1, st);
+    info[7] = A.blk_ok && (!two || B.blk_ok);
+    if (!info[7] || (two && A.blk_rows != B.blk_rows)) refused = 2;
+    else if (two) {
+      if (!fused_blk_plan(A, B, rb)) refused = 4;
+      else { ea = &A.h_blk_rowptr; eb = &B.h_blk_rowptr; fused_rb.upload(rb, st); d_rb = fused_rb.p; ib1 = (int)rb.size() - 1; }
+    } else { download(A.blk_rowblk, A.blk_nblk); ea = &A.h_blk_rowptr; ib0 = A.blk_int_b0; ib1 = A.blk_int_b1; }
+  }
+  info[15] = refused;
+  if (refused) return 1;
+  const int nblk = (int)rb.size() - 1;   // (-1: CSR-vector, no runs)
+  if (form != NSK_DBG_SPMV_CSRV) {
+    info[8] = nblk;
+    info[9] = ib0;
+    info[10] = ib1;
+    for (int b = 0; b < nblk; ++b) {
+      const int e = (*ea)[rb[b + 1]] - (*ea)[rb[b]] + (eb ? (*eb)[rb[b + 1]] - (*eb)[rb[b]] : 0);
+      info[11] = std::max(info[11], rb[b + 1] - rb[b]);
+      info[12] = std::max(info[12], e);
+    }
+    if (rowblk_out) std::copy(rb.begin(), rb.begin() + std::min<size_t>(rb.size(), (size_t)std::max(0, rowblk_cap)), rowblk_out);
+    if (c0 < 0) { c0 = 0; c1 = nblk; }
+    if (c0 > c1 || c1 > nblk) throw Error(-61, "nsk_debug_spmv: run range");
+  }
+
+  // operands: every vector between guard words; the ghost tails, B's x_own and y / z 8 bytes off where asked for
+  const int og = misalign & 1, ob = (misalign >> 1) & 1, oy = (misalign >> 2) & 1;
+  DbgVec xa, xag, xb, xbg, yv, zv, dv, div;
+  xa.put(Am->x_own, (size_t)A.n_own_cols, 0, st);
+  xag.put(Am->x_ghost, (size_t)(A.n_cols - A.n_own_cols), og, st);
+  if (two) {
+    xb.put(Bm->x_own, (size_t)B.n_own_cols, ob, st);
+    xbg.put(Bm->x_ghost, (size_t)(B.n_cols - B.n_own_cols), og, st);
+  }
+  yv.put(y, (size_t)A.n_rows, oy, st);
+  if (z) zv.put(z, (size_t)A.n_rows, oy, st);
+  if (epi) { dv.put(d, (size_t)A.n_rows, 0, st); div.put(dinv, (size_t)A.n_rows, 0, st); }
+
+  const int n_run = c1 - c0;
+  switch (form) {
+    case NSK_DBG_SPMV_CSRV:
+      if (lpr == 0) lpr = A.lpr;
+      if (lpr != 2 && lpr != 4 && lpr != 8 && lpr != 16 && lpr != 32 && lpr != 64) throw Error(-61, "nsk_debug_spmv: lpr");
+      info[2] = nsk::spmv(st, A.view(), lpr, xa.p, xag.p, yv.p, mode, zv.p);
+      break;
+    case NSK_DBG_SPMV_STREAM:
+      info[1] = nsk::spmv_stream(st, A.view(), d_rb + c0, n_run, A.even_rows, xa.p, xag.p, yv.p, mode, zv.p);
+      break;
+    case NSK_DBG_SPMV_STREAM_F32:
+      A.inner32 = 2;
+      A.refresh_f32(st, false);
+      info[1] = nsk::spmv_stream(st, A.view32(), d_rb + c0, n_run, A.even_rows, xa.p, xag.p, yv.p);
+      break;
+    case NSK_DBG_SPMV_BLK22: case NSK_DBG_SPMV_BLK21: case NSK_DBG_SPMV_BLK12: case NSK_DBG_SPMV_BLK11:
+      nsk::spmv_blk_stream(st, A.blk_view(), R, C, d_rb + c0, n_run, xa.p, xag.p, yv.p);
+      break;
+    case NSK_DBG_SPMV_BLK22_F32:
+      A.inner32 = 1;
+      A.refresh_f32(st, false);
+      nsk::spmv_blk_stream(st, A.blk_view32(), d_rb + c0, n_run, xa.p, xag.p, yv.p);
+      break;
+    case NSK_DBG_SPMV_BLK21_EPI:
+      nsk::spmv_blk_stream(st, A.blk_view(), 2, 1, d_rb + c0, n_run, xa.p, xag.p, yv.p, dv.p, div.p);
+      break;
+    case NSK_DBG_SPMV_STREAM2:
+      info[1] = nsk::spmv2_stream(st, A.view(), xa.p, xag.p, B.view(), xb.p, xbg.p, d_rb, nblk, yv.p);
+      break;
+    case NSK_DBG_SPMV_BLK_FUSED:
+      nsk::spmv_blk_fused22_21(st, A.blk_view(), xa.p, xag.p, B.blk_view(), xb.p, xbg.p, d_rb, nblk, yv.p);
+      break;
+  }
+  NSK_HIP(hipGetLastError());
+  info[0] = form;
+  info[14] = form == NSK_DBG_SPMV_CSRV ? 0 : n_run;
+  int bad = yv.fetch(y, c);
+  for (DbgVec *v : {&xa, &xag, &xb, &xbg, &zv, &dv, &div}) bad += v->fetch(nullptr, c);
+  info[13] = bad;
   return 0;
   NSK_CATCH(h)
 }

@@ -95,6 +95,41 @@ enum {
 };
 int nsk_debug_krylov(struct nsk_handle_s *h, int op, int n, int m, int offset, const double *par, int n_vec,
                      double *const *vec, const int64_t *len, double *slots64, int32_t *info8);
+/* Test hook for the sparse matrix-vector kernels (tests/test_gpu_spmv_kernels.py): ONE kernel form on the caller's CSR.
+ * The matrix goes into a Csr the way nsk_set_block_csr fills one (pick_lpr, Csr::build_stream_plan, and for the form
+ * asked for Csr::build_blocked / refresh_blocked / refresh_f32, the combined row runs of jacobian_vmult for the two-
+ * matrix forms) and the product is launched through the nsk:: launchers, so the plan builder and the kernel are tested
+ * together.  A form the plan refuses is reported (return value 1, info[15] says why), never forced.
+ * A: the matrix with its operand (x_own: n_own_cols doubles, x_ghost: n_cols - n_own_cols); B: the second matrix over
+ * the same rows (two-matrix forms; else null).  y (n_rows, in/out), z (n_rows or null: mode 1 adds to y, mode 2 needs
+ * it), d / dinv (n_rows, the epilogue form).  Every device vector is an allocation of its own between guard words (all
+ * bits set).  misalign: bit 0 the ghost tails, bit 1 B's x_own, bit 2 y (and z) start 8 bytes off a 16-byte boundary —
+ * what the call sites promise for them and no more (the ghost tail p + n, pb(x), yb + n_u); bit 2 is refused for the
+ * forms that store pairs (R = 2).  lpr: lanes per row of the CSR-vector form, 0 = pick_lpr.  mode: 0 y = A x, 1 y = (z
+ * or y) + A x, 2 y = z - A x (CSR-vector and stream fp64 only).  [c0, c1): the runs launched, as spmv_halo launches
+ * sub-ranges of one plan; c0 < 0: all of them (the only choice for CSR-vector and the two-matrix forms).
+ * rowblk_out (may be null): the first min(runs + 1, rowblk_cap) entries of the row-run plan that was used.
+ * info16: [0] form launched (-1 none), [1] VEC of the stream kernel as its launcher returns it (2 / 3; 0: other forms,
+ * or an empty run range: nothing launched), [2] lanes per row of the CSR-vector kernel as its launcher returns them
+ * (else pick_lpr's choice), [3] R, [4] C, [5] stream_ok, [6] even_rows, [7] blk_ok, [8] runs of the
+ * plan used, [9] [10] its interior run range, [11] longest run in rows, [12] in entries (blocks for the blocked forms,
+ * both matrices together for the two-matrix forms), [13] guard words that changed, [14] runs launched, [15] why the
+ * plan refused: 0 it did not, 1 a row above kStreamNnz, 2 no R x C node structure or a block row above kBlkMax, 3 the
+ * first matrix has an odd row pointer (the two-matrix stream form needs even_rows), 4 a row of both matrices together
+ * above the cap.  Device and stream of the handle; 0, 1 or a negative error code. */
+enum {
+  NSK_DBG_SPMV_CSRV = 0, NSK_DBG_SPMV_STREAM = 1, NSK_DBG_SPMV_STREAM_F32 = 2, NSK_DBG_SPMV_BLK22 = 3,
+  NSK_DBG_SPMV_BLK21 = 4, NSK_DBG_SPMV_BLK12 = 5, NSK_DBG_SPMV_BLK11 = 6, NSK_DBG_SPMV_BLK22_F32 = 7,
+  NSK_DBG_SPMV_BLK21_EPI = 8, NSK_DBG_SPMV_STREAM2 = 9, NSK_DBG_SPMV_BLK_FUSED = 10
+};
+struct nsk_dbg_spmv_mat {
+  int32_t n_rows, n_cols, n_own_cols, pad_;
+  const int32_t *rowptr, *col;
+  const double *val, *x_own, *x_ghost;
+};
+int nsk_debug_spmv(struct nsk_handle_s *h, int form, int lpr, int mode, int misalign, int c0, int c1,
+                   const struct nsk_dbg_spmv_mat *A, const struct nsk_dbg_spmv_mat *B, double *y, const double *z,
+                   const double *d, const double *dinv, int32_t *rowblk_out, int rowblk_cap, int32_t *info16);
 #ifdef __cplusplus
 }
 #endif

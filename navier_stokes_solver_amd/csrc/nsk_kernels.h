@@ -40,9 +40,10 @@ struct CsrViewT {
 };
 using CsrView = CsrViewT<double>;
 using CsrView32 = CsrViewT<float>;
-// mode 0: y = A x ; 1: y += A x ; 2: y = z - A x
-void spmv(hipStream_t s, const CsrView &A, int lanes_per_row, const double *x_own, const double *x_ghost, double *y,
-          int mode, const double *z);
+// mode 0: y = A x ; 1: y += A x ; 2: y = z - A x.  Returns the lanes per row of the kernel that was launched (what the
+// test hook nsk_debug_spmv reports).
+int spmv(hipStream_t s, const CsrView &A, int lanes_per_row, const double *x_own, const double *x_ghost, double *y,
+         int mode, const double *z);
 
 // LDS-staged "CSR-stream" SpMV: each 256-thread workgroup owns a run of whole rows holding at most
 // kStreamNnz non-zeros (rowblk[b]..rowblk[b+1]); it streams val/col fully coalesced, stages the
@@ -50,14 +51,16 @@ void spmv(hipStream_t s, const CsrView &A, int lanes_per_row, const double *x_ow
 // which allows 16-byte value / 8-byte index loads.
 constexpr int kStreamNnz = 2048;
 constexpr int kStreamRows = 64;  // rows per run = workgroup size / lanes per row in the reduce phase
-void spmv_stream(hipStream_t s, const CsrView &A, const int *rowblk, int nblk, int even_rows, const double *x_own,
-                 const double *x_ghost, double *y, int mode, const double *z);
+// The stream launchers return the VEC of the kernel they launched (2: aligned pairs, 3: unaligned pairs; 0: nothing
+// launched) — what the test hook nsk_debug_spmv reports.
+int spmv_stream(hipStream_t s, const CsrView &A, const int *rowblk, int nblk, int even_rows, const double *x_own,
+                const double *x_ghost, double *y, int mode, const double *z);
 // fp32 values (y = A x only): the same plan, lane decomposition and summation order as the double launch, so the result
 // has the bits of the double kernel run on the values rounded to float beforehand
-void spmv_stream(hipStream_t s, const CsrView32 &A, const int *rowblk, int nblk, int even_rows, const double *x_own,
-                 const double *x_ghost, double *y);
-void spmv2_stream(hipStream_t s, const CsrView &A, const double *xa_own, const double *xa_ghost, const CsrView &B,
-                  const double *xb_own, const double *xb_ghost, const int *rowblk, int nblk, double *y);
+int spmv_stream(hipStream_t s, const CsrView32 &A, const int *rowblk, int nblk, int even_rows, const double *x_own,
+                const double *x_ghost, double *y);
+int spmv2_stream(hipStream_t s, const CsrView &A, const double *xa_own, const double *xa_ghost, const CsrView &B,
+                 const double *xb_own, const double *xb_ghost, const int *rowblk, int nblk, double *y);
 
 // Small dense blocks exploit the node structure of the Taylor-Hood blocks: both velocity components of a
 // node share one sparsity pattern, so F is made of 2x2 blocks, (0,1) of 2x1 and (1,0) of 1x2 blocks.  One

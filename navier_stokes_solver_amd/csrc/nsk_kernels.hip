@@ -265,6 +265,10 @@ template <class V, int R, int C>
 __device__ __forceinline__ void blk_products(const BlkViewT<V> &A, int k0, int k1, const double *__restrict__ xo,
                                              const double *__restrict__ xg, double *p0, double *p1) {
   constexpr int U = kBlkMax / BLK;  // staged like stream_products: loads, gathers, LDS stores
+  // A run without blocks stages nothing (the same for every lane: a scalar branch).  It must not fall through: the lanes
+  // without a block of their own load block k0, which exists only when the run has one — behind the last block of the
+  // matrix (trailing empty block rows, a matrix without entries) there is nothing to read.
+  if (k0 >= k1) return;
   int m[U];
   double2 a0[U], a1[U];
   double x0[U], x1[U];
@@ -1375,47 +1379,50 @@ void launch_tri_level(hipStream_t s, const TriView &T, int lpr, const int *rows,
 }  // namespace
 
 // ================================================================== launchers
-void spmv(hipStream_t s, const CsrView &A, int lpr, const double *xo, const double *xg, double *y, int mode,
-          const double *z) {
+int spmv(hipStream_t s, const CsrView &A, int lpr, const double *xo, const double *xg, double *y, int mode,
+         const double *z) {
   switch (lpr) {
-    case 2: launch_spmv_mode<2>(s, A, xo, xg, y, mode, z); break;
-    case 4: launch_spmv_mode<4>(s, A, xo, xg, y, mode, z); break;
-    case 8: launch_spmv_mode<8>(s, A, xo, xg, y, mode, z); break;
-    case 16: launch_spmv_mode<16>(s, A, xo, xg, y, mode, z); break;
-    case 32: launch_spmv_mode<32>(s, A, xo, xg, y, mode, z); break;
-    default: launch_spmv_mode<64>(s, A, xo, xg, y, mode, z); break;
+    case 2: launch_spmv_mode<2>(s, A, xo, xg, y, mode, z); return 2;
+    case 4: launch_spmv_mode<4>(s, A, xo, xg, y, mode, z); return 4;
+    case 8: launch_spmv_mode<8>(s, A, xo, xg, y, mode, z); return 8;
+    case 16: launch_spmv_mode<16>(s, A, xo, xg, y, mode, z); return 16;
+    case 32: launch_spmv_mode<32>(s, A, xo, xg, y, mode, z); return 32;
+    default: launch_spmv_mode<64>(s, A, xo, xg, y, mode, z); return 64;
   }
 }
 
-void spmv_stream(hipStream_t s, const CsrView &A, const int *rowblk, int nblk, int even_rows, const double *xo,
-                 const double *xg, double *y, int mode, const double *z) {
-  if (nblk <= 0) return;
+int spmv_stream(hipStream_t s, const CsrView &A, const int *rowblk, int nblk, int even_rows, const double *xo,
+                const double *xg, double *y, int mode, const double *z) {
+  if (nblk <= 0) return 0;
 #define NSK_SS(V, M) hipLaunchKernelGGL((spmv_stream_kernel<double, V, M>), dim3(nblk), dim3(BLK), 0, s, A, rowblk, xo, xg, y, z)
   // pairs of entries per lane: 16-byte aligned where every row pointer is even, 4- / 8-byte aligned loads otherwise
   // (S: 0.271 -> 0.264 ms at 1200x400 against one entry per load)
   if (even_rows) {
     if (mode == 0) NSK_SS(2, 0); else if (mode == 1) NSK_SS(2, 1); else NSK_SS(2, 2);
-  } else {
-    if (mode == 0) NSK_SS(3, 0); else if (mode == 1) NSK_SS(3, 1); else NSK_SS(3, 2);
+    return 2;
   }
+  if (mode == 0) NSK_SS(3, 0); else if (mode == 1) NSK_SS(3, 1); else NSK_SS(3, 2);
+  return 3;
 #undef NSK_SS
 }
 
-void spmv_stream(hipStream_t s, const CsrView32 &A, const int *rowblk, int nblk, int even_rows, const double *xo,
-                 const double *xg, double *y) {
-  if (nblk <= 0) return;
+int spmv_stream(hipStream_t s, const CsrView32 &A, const int *rowblk, int nblk, int even_rows, const double *xo,
+                const double *xg, double *y) {
+  if (nblk <= 0) return 0;
   // the double launcher's choice of pair loads: the same lanes sum the same entries
   const double *z = nullptr;
 #define NSK_SS(V) hipLaunchKernelGGL((spmv_stream_kernel<float, V, 0>), dim3(nblk), dim3(BLK), 0, s, A, rowblk, xo, xg, y, z)
-  if (even_rows) NSK_SS(2);
-  else NSK_SS(3);
+  if (even_rows) { NSK_SS(2); return 2; }
+  NSK_SS(3);
+  return 3;
 #undef NSK_SS
 }
 
-void spmv2_stream(hipStream_t s, const CsrView &A, const double *xao, const double *xag, const CsrView &B,
-                  const double *xbo, const double *xbg, const int *rowblk, int nblk, double *y) {
-  if (nblk <= 0) return;
+int spmv2_stream(hipStream_t s, const CsrView &A, const double *xao, const double *xag, const CsrView &B,
+                 const double *xbo, const double *xbg, const int *rowblk, int nblk, double *y) {
+  if (nblk <= 0) return 0;
   hipLaunchKernelGGL((spmv2_stream_kernel<2>), dim3(nblk), dim3(BLK), 0, s, A, xao, xag, B, xbo, xbg, rowblk, y);
+  return 2;
 }
 
 template <class V>
