@@ -254,11 +254,11 @@ struct nsk_handle_s {
     if (f32 && A.inner32 == 1)
       nsk::spmv_blk_stream(s(), A.blk_view32(), A.blk_rowblk.p, A.blk_nblk, x.own, x.ghost, y);
     else if (f32)
-      nsk::spmv_stream(s(), A.view32(), A.rowblk.p, A.nblk, A.even_rows, x.own, x.ghost, y);
+      nsk::spmv_stream(s(), A.view32(), A.rowblk.p, A.nblk, A.even_rows, x.own, x.ghost, y, A.off16.p, A.colbase.p);
     else if (A.blk_ok && use_stream && use_bsr && mode == 0)
       nsk::spmv_blk_stream(s(), A.blk_view(), A.blk_R, A.blk_C, A.blk_rowblk.p, A.blk_nblk, x.own, x.ghost, y);
     else if (A.stream_ok && use_stream)
-      nsk::spmv_stream(s(), A.view(), A.rowblk.p, A.nblk, A.even_rows, x.own, x.ghost, y, mode, z);
+      nsk::spmv_stream(s(), A.view(), A.rowblk.p, A.nblk, A.even_rows, x.own, x.ghost, y, mode, z, A.off16.p, A.colbase.p);
     else
       nsk::spmv(s(), A.view(), A.lpr, x.own, x.ghost, y, mode, z);
     if (smp) (void)hipEventRecord(smp->e1[smp->used++], s());
@@ -271,6 +271,16 @@ struct nsk_handle_s {
   // are sub-ranges of the same plan.
   // This is the SpMV of the preconditioner's inner solves (and of nsk_inner_spmv): where A holds an fp32 copy
   // (NSK_OPT_INNER_MATRIX_PRECISION = 32) it reads that, converted again first when val has changed since.
+  // NSK_IOPT_INDEX16: 16-bit column offsets in the scalar stream kernels of S and M_p (SpMV and the split ILU / SGS halves)
+  // wherever every run qualifies; 0: int32 columns everywhere
+  bool index16 = true;
+  // does the SpMV of A go through the scalar stream kernel on 16-bit offsets with the current options?
+  bool spmv_on_index16(const Csr &A) const { return A.off16.p && A.stream_ok && use_stream && !(A.blk_ok && use_bsr); }
+  void index16_for(Csr &A, const char *name) {
+    A.build_index16(s(), index16);
+    if (verbose() && index16 && A.stream_ok && !A.off16.p)
+      fprintf(stderr, "[nsk] %s: a run of the stream plan spans 65 536 columns or more — int32 column ids stay in use\n", name);
+  }
   bool overlap_halo = true;   // NSK_IOPT_OVERLAP_HALO
   long overlapped_spmvs = 0;
   void spmv_halo(Csr &A, int space, const DVec &x, double *y) {
@@ -294,8 +304,8 @@ struct nsk_handle_s {
       if (c1 <= c0) return;
       if (blocked && f32) nsk::spmv_blk_stream(st, A.blk_view32(), A.blk_rowblk.p + c0, c1 - c0, x.own, x.ghost, y);
       else if (blocked) nsk::spmv_blk_stream(st, A.blk_view(), A.blk_R, A.blk_C, A.blk_rowblk.p + c0, c1 - c0, x.own, x.ghost, y);
-      else if (f32) nsk::spmv_stream(st, A.view32(), A.rowblk.p + c0, c1 - c0, A.even_rows, x.own, x.ghost, y);
-      else nsk::spmv_stream(st, A.view(), A.rowblk.p + c0, c1 - c0, A.even_rows, x.own, x.ghost, y, 0, nullptr);
+      else if (f32) nsk::spmv_stream(st, A.view32(), A.rowblk.p + c0, c1 - c0, A.even_rows, x.own, x.ghost, y, A.off16.p, A.off16.p ? A.colbase.p + c0 : nullptr);
+      else nsk::spmv_stream(st, A.view(), A.rowblk.p + c0, c1 - c0, A.even_rows, x.own, x.ghost, y, 0, nullptr, A.off16.p, A.off16.p ? A.colbase.p + c0 : nullptr);
     };
     NSK_HIP(hipEventRecord(ctx.ev_fork, s()));                 // x is complete here
     NSK_HIP(hipStreamWaitEvent(ctx.stream2, ctx.ev_fork, 0));
@@ -441,6 +451,7 @@ void H::schur_symbolic() {
     S.lpr = pick_lpr(S.nnz, S.n_rows);
     S.present = true;
     S.build_stream_plan(s());
+    index16_for(S, "S");
     ctx.sync();
     s_symbolic = true;
     return;
@@ -486,6 +497,7 @@ void H::schur_symbolic() {
   S.lpr = pick_lpr(S.nnz, S.n_rows);
   S.present = true;
   S.build_stream_plan(s());
+  index16_for(S, "S");
   ctx.sync();
   s_symbolic = true;
 }
@@ -495,6 +507,7 @@ void H::setup(int type, int variant_, double alpha_) {
   ensure_pools();
   ctx.ws.pairs = blas1_pairs < 0 ? (variant_ == 0) : blas1_pairs;   // NSK_OPT_BLAS1_PAIRS
   tMp.sync_free = tS.sync_free = sync_free_mode >= 1;
+  tMp.want_index16 = tS.want_index16 = index16;
   tF.sync_free = sync_free_mode == 2;
   tMp.sf_fault = tS.sf_fault = (fault_inject & 1) != 0;
   tF.sf_fault = (fault_inject & 2) != 0;
@@ -1100,6 +1113,7 @@ int nsk_set_block_csr(nsk_handle h, int b, int n_rows, int n_cols, const int32_t
   A.lpr = pick_lpr(nnz, n_rows);
   A.present = true;
   A.build_stream_plan(h->s());
+  if (b == NSK_BLK_MP) h->index16_for(A, "M_p");
   if (b == NSK_BLK_F) A.build_blocked(2, 2, h->s());
   if (b == NSK_BLK_BT) A.build_blocked(2, 1, h->s());
   if (b == NSK_BLK_B) A.build_blocked(1, 2, h->s());
@@ -1169,6 +1183,15 @@ int nsk_set_option(nsk_handle h, int opt, double v) {
     case NSK_OPT_BSR_VELOCITY: h->use_bsr = v != 0.0; break;
     case NSK_OPT_VELOCITY_AMG: h->velocity_amg = v != 0.0; break;
     case NSK_IOPT_TIMEOP_BETWEEN: h->timeop_between = (int)v; break;
+    case NSK_IOPT_INDEX16:
+      h->index16 = v != 0.0;
+      h->tS.want_index16 = h->tMp.want_index16 = h->index16;
+      (void)hipSetDevice(h->ctx.device);
+      for (int b : {NSK_BLK_MP, NSK_BLK_S})
+        if (h->blk[b].present && h->blk[b].stream_ok) h->index16_for(h->blk[b], b == NSK_BLK_S ? "S" : "M_p");
+      h->ctx.sync();
+      h->tS_ok = h->tMp_ok = false;   // the factors' halves are rebuilt by the next set-up
+      break;
     case NSK_IOPT_HOST_ANALYSIS:
       h->tF.host_analysis = h->tS.host_analysis = h->tMp.host_analysis = v != 0.0;
       h->tF_ok = h->tS_ok = h->tMp_ok = false;
@@ -1919,9 +1942,9 @@ int nsk_debug_spmv(nsk_handle h, int form, int lpr, int mode, int misalign, int 
   hipStream_t st = h->s();
   for (int k = 0; k < 16; ++k) info[k] = 0;
   info[0] = -1;
-  if (form < NSK_DBG_SPMV_CSRV || form > NSK_DBG_SPMV_BLK_FUSED) throw Error(-65, "nsk_debug_spmv: unknown form");
+  if (form < NSK_DBG_SPMV_CSRV || form > NSK_DBG_SPMV_STREAM_I16_F32) throw Error(-65, "nsk_debug_spmv: unknown form");
   const bool two = form == NSK_DBG_SPMV_STREAM2 || form == NSK_DBG_SPMV_BLK_FUSED;
-  const bool modes = form == NSK_DBG_SPMV_CSRV || form == NSK_DBG_SPMV_STREAM;
+  const bool modes = form == NSK_DBG_SPMV_CSRV || form == NSK_DBG_SPMV_STREAM || form == NSK_DBG_SPMV_STREAM_I16;
   const bool epi = form == NSK_DBG_SPMV_BLK21_EPI;
   if (!Am || !y || two != (Bm != nullptr)) throw Error(-61, "nsk_debug_spmv: matrices");
   if (mode < 0 || mode > 2 || (mode != 0 && !modes) || (mode == 2 && !z)) throw Error(-61, "nsk_debug_spmv: mode");
@@ -1931,7 +1954,7 @@ int nsk_debug_spmv(nsk_handle h, int form, int lpr, int mode, int misalign, int 
   if (form == NSK_DBG_SPMV_BLK22 || form == NSK_DBG_SPMV_BLK22_F32 || form == NSK_DBG_SPMV_BLK_FUSED) R = C = 2;
   if (form == NSK_DBG_SPMV_BLK21 || epi) R = 2;
   if (form == NSK_DBG_SPMV_BLK12) C = 2;
-  const bool blocked = form >= NSK_DBG_SPMV_BLK22 && form != NSK_DBG_SPMV_STREAM2;
+  const bool blocked = form >= NSK_DBG_SPMV_BLK22 && form != NSK_DBG_SPMV_STREAM2 && form != NSK_DBG_SPMV_STREAM_I16 && form != NSK_DBG_SPMV_STREAM_I16_F32;
   if ((misalign & 4) && R == 2) throw Error(-61, "nsk_debug_spmv: the R = 2 forms store pairs, y is 16-byte aligned");
   if (two && Bm->n_rows != Am->n_rows) throw Error(-61, "nsk_debug_spmv: both matrices over the same rows");
 
@@ -1956,9 +1979,14 @@ int nsk_debug_spmv(nsk_handle h, int form, int lpr, int mode, int misalign, int 
     c.sync();
     d_rb = src.p;
   };
-  if (form == NSK_DBG_SPMV_STREAM || form == NSK_DBG_SPMV_STREAM_F32) {
+  const bool i16 = form == NSK_DBG_SPMV_STREAM_I16 || form == NSK_DBG_SPMV_STREAM_I16_F32;
+  if (form == NSK_DBG_SPMV_STREAM || form == NSK_DBG_SPMV_STREAM_F32 || i16) {
     if (!A.stream_ok) refused = 1;
     else { download(A.rowblk, A.nblk); ib0 = A.int_b0; ib1 = A.int_b1; }
+    if (!refused && i16) {
+      A.build_index16(st, true);
+      if (!A.off16.p) refused = 5;
+    }
   } else if (form == NSK_DBG_SPMV_STREAM2) {
     if (!A.even_rows) refused = 3;   // (jacobian_vmult asks for F.even_rows: the kernel reads F in aligned pairs)
     else if (!fused_row_plan(A, B, rb)) refused = 4;
@@ -2013,6 +2041,14 @@ int nsk_debug_spmv(nsk_handle h, int form, int lpr, int mode, int misalign, int 
     case NSK_DBG_SPMV_STREAM:
       info[1] = nsk::spmv_stream(st, A.view(), d_rb + c0, n_run, A.even_rows, xa.p, xag.p, yv.p, mode, zv.p);
       break;
+    case NSK_DBG_SPMV_STREAM_I16:
+      info[1] = nsk::spmv_stream(st, A.view(), d_rb + c0, n_run, A.even_rows, xa.p, xag.p, yv.p, mode, zv.p, A.off16.p, A.colbase.p + c0);
+      break;
+    case NSK_DBG_SPMV_STREAM_I16_F32:
+      A.inner32 = 2;
+      A.refresh_f32(st, false);
+      info[1] = nsk::spmv_stream(st, A.view32(), d_rb + c0, n_run, A.even_rows, xa.p, xag.p, yv.p, A.off16.p, A.colbase.p + c0);
+      break;
     case NSK_DBG_SPMV_STREAM_F32:
       A.inner32 = 2;
       A.refresh_f32(st, false);
@@ -2065,6 +2101,21 @@ int nsk_tri_get_value_bytes(nsk_handle h, int which, int32_t *bytes) {
   if (h->prec_type < 0) throw Error(-46, "call nsk_setup_preconditioner first");
   if (which == NSK_TRI_VELOCITY && h->amg_active) *bytes = 0;   // no triangular factor in this setup
   else *bytes = (which == NSK_TRI_VELOCITY ? &h->tF : h->tP)->value_bytes();
+  return 0;
+  NSK_CATCH(h)
+}
+
+int nsk_debug_index_width(nsk_handle h, int b, int32_t *out3) {
+  NSK_TRY(h)
+  if (b != NSK_BLK_S && b != NSK_BLK_MP) throw Error(-62, "nsk_debug_index_width: S or M_p");
+  if (h->prec_type < 0) throw Error(-46, "call nsk_setup_preconditioner first");
+  const Csr &A = h->blk[b];
+  const TriSolve &T = b == NSK_BLK_S ? h->tS : h->tMp;
+  const bool spmv_streams = A.present && A.stream_ok && h->use_stream && !(A.blk_ok && h->use_bsr);
+  out3[0] = !spmv_streams ? 0 : h->spmv_on_index16(A) ? 16 : 32;
+  const bool halves = T.stream_ready && T.halves_in_use();
+  out3[1] = !halves ? 0 : T.Loff16.p ? 16 : 32;
+  out3[2] = !halves ? 0 : T.Uoff16.p ? 16 : 32;
   return 0;
   NSK_CATCH(h)
 }
@@ -2248,7 +2299,7 @@ int nsk_profile_read(nsk_handle h, int op, double *avg_ms, int *n_samples, doubl
   }
   if (bytes_format) {   // what the storage format in use really holds (<= the CSR figure for the node-block copies)
     // (F, S, M_p with fp32 copies for the inner solves: the fp32 format — see nsk.h, NSK_OPT_INNER_MATRIX_PRECISION)
-    if (op >= 0 && op <= NSK_BLK_S) *bytes_format = h->blk[op].format_bytes(h->use_stream && h->use_bsr, h->inner_width(h->blk[op]));
+    if (op >= 0 && op <= NSK_BLK_S) *bytes_format = h->blk[op].format_bytes(h->use_stream && h->use_bsr, h->inner_width(h->blk[op]), h->spmv_on_index16(h->blk[op]));
     else if (op == 20) *bytes_format = h->tF.format_bytes();
     else if (op == 21 && h->tP) *bytes_format = h->tP->format_bytes();
     else *bytes_format = 0.0;
@@ -2303,7 +2354,7 @@ int nsk_time_op(nsk_handle h, int op, int reps, double *avg_ms, double *bytes) {
     double *xs = pc.get(true);
     vec_set(h->s(), pc.n, xs, 1.0);
     const DVec xv = pc.view(xs);
-    by = A.format_bytes(h->use_stream && h->use_bsr, h->inner_width(A));
+    by = A.format_bytes(h->use_stream && h->use_bsr, h->inner_width(A), h->spmv_on_index16(A));
     f = [=, &A]() { h->spmv_halo(A, cs, xv, yb); };
     pc.put(xs);   // stays valid until the pool hands it out again (not during this call)
   } else if (op == 10) {

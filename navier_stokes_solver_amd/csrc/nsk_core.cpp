@@ -518,7 +518,7 @@ bool Ctx::mgs_sweep(int n, double *w, double *const *v, int nv, int so) {
 
 void Ctx::spmv(Csr &A, Space &colspace, const DVec &x, double *y, int mode, const double *z) {
   comm.halo_exchange(colspace, x, stream);
-  if (A.stream_ok) nsk::spmv_stream(stream, A.view(), A.rowblk.p, A.nblk, A.even_rows, x.own, x.ghost, y, mode, z);
+  if (A.stream_ok) nsk::spmv_stream(stream, A.view(), A.rowblk.p, A.nblk, A.even_rows, x.own, x.ghost, y, mode, z, A.off16.p, A.colbase.p);
   else nsk::spmv(stream, A.view(), A.lpr, x.own, x.ghost, y, mode, z);
   ++st.spmv_calls;
   st.spmv_bytes += (double)A.spmv_bytes() + (mode ? 8.0 * A.n_rows : 0.0);
@@ -597,6 +597,40 @@ void Csr::build_stream_plan(hipStream_t s) {
   for (int i = 0; i <= n_rows; ++i)
     if (h_rowptr[i] & 1) { even_rows = false; break; }
   rowblk.upload(rb, s);
+  off16.release();   // (a new plan: build_index16 follows where the 16-bit form is wanted)
+  colbase.release();
+  idx16_wide = false;
+}
+
+void Csr::build_index16(hipStream_t s, bool want) {
+  off16.release();
+  colbase.release();
+  idx16_wide = false;
+  if (!want || !stream_ok || nblk <= 0) return;
+  if (nnz <= 0) {   // no entries at all: every run's base is 0, nothing is ever read through the offsets
+    colbase.alloc((size_t)nblk);
+    off16.alloc(8);
+    NSK_HIP(hipMemsetAsync(colbase.p, 0, sizeof(int) * (size_t)nblk, s));
+    NSK_HIP(hipMemsetAsync(off16.p, 0, 8 * sizeof(unsigned short), s));
+    return;
+  }
+  if (!col.p) return;
+  DBuf<int> wide;
+  wide.alloc(1);
+  colbase.alloc((size_t)nblk);
+  NSK_HIP(hipMemsetAsync(wide.p, 0, sizeof(int), s));
+  nsk::setup_run_col_base(s, nblk, nullptr, rowblk.p, rowptr.p, col.p, colbase.p, wide.p);
+  int w = 0;
+  NSK_HIP(hipMemcpyAsync(&w, wide.p, sizeof(int), hipMemcpyDeviceToHost, s));
+  NSK_HIP(hipStreamSynchronize(s));
+  if (w) {   // a run spans 65 536 columns or more (ghost columns behind the owned ones, a wide numbering): int32 columns
+    idx16_wide = true;
+    colbase.release();
+    return;
+  }
+  off16.alloc((size_t)nnz + 8);   // (spare entries: a pair load may take the word behind the last entry along)
+  NSK_HIP(hipMemsetAsync(off16.p + nnz, 0, 8 * sizeof(unsigned short), s));
+  nsk::setup_run_col_offsets(s, nblk, nullptr, rowblk.p, rowptr.p, col.p, colbase.p, off16.p);
 }
 
 void Csr::build_blocked(int R, int C, hipStream_t s) {

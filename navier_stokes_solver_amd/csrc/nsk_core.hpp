@@ -134,6 +134,13 @@ struct Csr {  // device CSR block with host copy of the pattern
   int nblk = 0;
   bool stream_ok = false, even_rows = false;
   void build_stream_plan(hipStream_t s);
+  // 16-bit column offsets for the stream kernel: off16[k] = col[k] - colbase[b] for the entries of run b,
+  // colbase[b] its smallest column.  Built on the device from col and the plan, once per pattern, when EVERY run spans
+  // fewer than 65 536 columns (idx16_wide: one did not, the int32 columns stay in use).  want = false: released.
+  DBuf<unsigned short> off16;
+  DBuf<int> colbase;
+  bool idx16_wide = false;
+  void build_index16(hipStream_t s, bool want);
   // Rows without ghost columns ("interior": everything but the first and last lattice columns of an x-strip, contiguous
   // in the x-major numbering) form [int_r0, int_r1); the row-run plans are cut there, and [*_int_b0, *_int_b1) are the
   // runs of the interior — what an SpMV can compute while the halo exchange is still in flight.
@@ -162,11 +169,12 @@ struct Csr {  // device CSR block with host copy of the pattern
   BlkView32 blk_view32() const { return BlkView32{blk_rows, n_own_cols / blk_C, blk_rowptr.p, blk_col.p, blk_val32.p}; }
   CsrView32 view32() const { return CsrView32{n_rows, n_own_cols, rowptr.p, col.p, val32.p}; }
   // bytes the storage format the SpMV kernels actually stream holds (values, indices, descriptors) + y + x once;
-  // value_bytes 4: the fp32 copies
-  double format_bytes(bool blocked, int value_bytes = 8) const {
+  // value_bytes 4: the fp32 copies; index16: see below
+  double format_bytes(bool blocked, int value_bytes = 8, bool index16 = false) const {
     if (blocked && blk_ok)
       return (double)blk_count * (4.0 + (double)value_bytes * blk_R * blk_C) + 4.0 * (blk_rows + 1.0) + 8.0 * n_rows + 8.0 * n_cols;
-    return (double)spmv_bytes() - (8.0 - value_bytes) * (double)nnz;
+    // (index16: the caller's SpMV runs the stream kernel on 16-bit offsets — 2 bytes per entry instead of 4, one base per run)
+    return (double)spmv_bytes() - (8.0 - value_bytes) * (double)nnz - (index16 ? 2.0 * (double)nnz - 4.0 * nblk : 0.0);
   }
   size_t spmv_bytes() const {  // 12 nnz + 4 (rows+1) + 8 rows + 8 cols
     return (size_t)12 * nnz + 4 * ((size_t)n_rows + 1) + 8 * (size_t)n_rows + 8 * (size_t)n_cols;

@@ -22,6 +22,9 @@ enum {
   NSK_IOPT_TIMEOP_BETWEEN = 109, // nsk_time_op: a block id (e.g. NSK_BLK_F) whose SpMV runs BETWEEN two repetitions, outside
                                 // the timed brackets (one pair of events per repetition) — the operation as a solver sees
                                 // it, with the caches and clocks another kernel leaves behind; -1 (default): back to back
+  NSK_IOPT_INDEX16 = 110,       // 1 (default): the scalar stream kernels of S and M_p — SpMV, split ILU / SGS halves — read 16-bit
+                                // column offsets on top of one base per run wherever every run of the plan spans fewer than
+                                // 65 536 columns (same bits, 2 bytes per entry less); 0: int32 column ids everywhere
   NSK_IOPT_FUSED_MGS = 106      // 1 (default): the modified Gram-Schmidt chain of an Arnoldi step in ONE launch when the
                                 // vector fits the registers of the co-resident grid (single rank); 0: one launch per link
 };
@@ -116,11 +119,15 @@ int nsk_debug_krylov(struct nsk_handle_s *h, int op, int n, int m, int offset, c
  * both matrices together for the two-matrix forms), [13] guard words that changed, [14] runs launched, [15] why the
  * plan refused: 0 it did not, 1 a row above kStreamNnz, 2 no R x C node structure or a block row above kBlkMax, 3 the
  * first matrix has an odd row pointer (the two-matrix stream form needs even_rows), 4 a row of both matrices together
- * above the cap.  Device and stream of the handle; 0, 1 or a negative error code. */
+ * above the cap, 5 (NSK_DBG_SPMV_STREAM_I16) a run spans 65 536 columns or more.  Device and stream of the handle; 0, 1 or
+ * a negative error code.
+ * NSK_DBG_SPMV_STREAM_I16: the stream kernel on 16-bit column offsets (Csr::build_index16), modes as
+ * NSK_DBG_SPMV_STREAM; NSK_DBG_SPMV_STREAM_I16_F32: the same on the fp32 copy of the values (y = A x only). */
 enum {
   NSK_DBG_SPMV_CSRV = 0, NSK_DBG_SPMV_STREAM = 1, NSK_DBG_SPMV_STREAM_F32 = 2, NSK_DBG_SPMV_BLK22 = 3,
   NSK_DBG_SPMV_BLK21 = 4, NSK_DBG_SPMV_BLK12 = 5, NSK_DBG_SPMV_BLK11 = 6, NSK_DBG_SPMV_BLK22_F32 = 7,
-  NSK_DBG_SPMV_BLK21_EPI = 8, NSK_DBG_SPMV_STREAM2 = 9, NSK_DBG_SPMV_BLK_FUSED = 10
+  NSK_DBG_SPMV_BLK21_EPI = 8, NSK_DBG_SPMV_STREAM2 = 9, NSK_DBG_SPMV_BLK_FUSED = 10, NSK_DBG_SPMV_STREAM_I16 = 11,
+  NSK_DBG_SPMV_STREAM_I16_F32 = 12
 };
 struct nsk_dbg_spmv_mat {
   int32_t n_rows, n_cols, n_own_cols, pad_;
@@ -130,6 +137,10 @@ struct nsk_dbg_spmv_mat {
 int nsk_debug_spmv(struct nsk_handle_s *h, int form, int lpr, int mode, int misalign, int c0, int c1,
                    const struct nsk_dbg_spmv_mat *A, const struct nsk_dbg_spmv_mat *B, double *y, const double *z,
                    const double *d, const double *dinv, int32_t *rowblk_out, int rowblk_cap, int32_t *info16);
+/* Which index width the scalar stream kernels of block b (NSK_BLK_S or NSK_BLK_MP) run on after the set-up: out3 = {the
+ * block's SpMV, the lower half of its triangular factor, the upper half}; 16: 16-bit offsets, 32: int32 column ids, 0: that
+ * operation does not go through the scalar stream kernels on this handle. */
+int nsk_debug_index_width(struct nsk_handle_s *h, int b, int32_t *out3);
 #ifdef __cplusplus
 }
 #endif

@@ -53,12 +53,16 @@ constexpr int kStreamNnz = 2048;
 constexpr int kStreamRows = 64;  // rows per run = workgroup size / lanes per row in the reduce phase
 // The stream launchers return the VEC of the kernel they launched (2: aligned pairs, 3: unaligned pairs; 0: nothing
 // launched) — what the test hook nsk_debug_spmv reports.
+// off16 / colbase (null: A.col): 16-bit column offsets, off16[k] = A.col[k] - colbase[b] for every entry k of
+// run b, colbase[b] the smallest column of the run — built by Csr::build_index16 when every run spans < 65 536 columns.
+// colbase runs beside rowblk: a launch of a sub-range moves both pointers.  Same lanes, same sums, same bits.
 int spmv_stream(hipStream_t s, const CsrView &A, const int *rowblk, int nblk, int even_rows, const double *x_own,
-                const double *x_ghost, double *y, int mode, const double *z);
+                const double *x_ghost, double *y, int mode, const double *z, const unsigned short *off16 = nullptr,
+                const int *colbase = nullptr);
 // fp32 values (y = A x only): the same plan, lane decomposition and summation order as the double launch, so the result
 // has the bits of the double kernel run on the values rounded to float beforehand
 int spmv_stream(hipStream_t s, const CsrView32 &A, const int *rowblk, int nblk, int even_rows, const double *x_own,
-                const double *x_ghost, double *y);
+                const double *x_ghost, double *y, const unsigned short *off16 = nullptr, const int *colbase = nullptr);
 int spmv2_stream(hipStream_t s, const CsrView &A, const double *xa_own, const double *xa_ghost, const CsrView &B,
                  const double *xb_own, const double *xb_ghost, const int *rowblk, int nblk, double *y);
 
@@ -187,6 +191,10 @@ struct TriHalfT {
   const int *col;
   const V *val;
   const int4 *desc;  // per workgroup: {first row, end row, first nnz, end nnz} — one load instead of a chain
+  // 16-bit column offsets (null: col): off16[k] = column - base[b] for the entries of workgroup b, base beside
+  // desc in the same order.  col may then be null.
+  const unsigned short *off16 = nullptr;
+  const int *base = nullptr;
 };
 using TriHalf = TriHalfT<double>;
 using TriHalf32 = TriHalfT<float>;
@@ -334,6 +342,13 @@ void setup_blk_fill(hipStream_t s, int nn, const int *prp, const int *pcol, cons
 // scalar split (no line groups): strict-lower / strict-upper CSR halves, column ids in the caller's numbering, sorted
 void setup_csr_fill(hipStream_t s, int n, const int *prp, const int *pcol, const int *pdiag, const int *perm, int max_row,
                     const int *lrp, const int *urp, int *lcol, int *lsrc, int *ucol, int *usrc);
+// 16-bit column offsets of the stream kernels.  Runs of entries: desc[b].z .. desc[b].w, or (desc null)
+// rowptr[rowblk[b]] .. rowptr[rowblk[b + 1]].  base[b] = smallest column of run b (0: no entries), *wide = 1 when a run
+// spans more than 65 535 columns (the 16-bit form then does not apply); off[k] = col[k] - base[b].
+void setup_run_col_base(hipStream_t s, int nb, const int4 *desc, const int *rowblk, const int *rowptr, const int *col,
+                        int *base, int *wide);
+void setup_run_col_offsets(hipStream_t s, int nb, const int4 *desc, const int *rowblk, const int *rowptr, const int *col,
+                           const int *base, unsigned short *off);
 
 // ---- halo pack ----
 void halo_pack(hipStream_t s, int n, const int *idx, const double *x, double *buf);

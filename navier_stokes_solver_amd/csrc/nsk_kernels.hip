@@ -100,10 +100,31 @@ constexpr int RG = 4;  // lanes cooperating on one row in the reduce phase
 __device__ __forceinline__ double2 widen2(double2 v) { return v; }
 __device__ __forceinline__ double2 widen2(float2 v) { return make_double2((double)v.x, (double)v.y); }
 
-template <class V, int VEC>
-__device__ __forceinline__ void stream_products(const int *__restrict__ col, const V *__restrict__ val, int k0,
+// I = unsigned short (16-bit column offsets): col holds `column - base` of the run, base its smallest column;
+// a pair of offsets is ONE 4-byte load (2-byte aligned for VEC == 3), the gather address base + offset.  I = int: base = 0.
+template <class I>
+struct IdxPair;
+template <>
+struct IdxPair<int> {
+  typedef int v2 __attribute__((ext_vector_type(2)));
+  typedef v2 unaligned __attribute__((aligned(4)));
+  typedef v2 aligned2;
+  int a, b;
+  __device__ __forceinline__ IdxPair(v2 q, int) : a(q[0]), b(q[1]) {}
+};
+template <>
+struct IdxPair<unsigned short> {
+  typedef unsigned v2;
+  typedef unsigned unaligned __attribute__((aligned(2)));
+  typedef unsigned aligned2;
+  int a, b;
+  __device__ __forceinline__ IdxPair(unsigned q, int base) : a(base + (int)(q & 0xffffu)), b(base + (int)(q >> 16)) {}
+};
+
+template <class V, int VEC, class I = int>
+__device__ __forceinline__ void stream_products(const I *__restrict__ col, const V *__restrict__ val, int k0,
                                                 int k1, int n_own, const double *__restrict__ xo,
-                                                const double *__restrict__ xg, double *prod) {
+                                                const double *__restrict__ xg, double *prod, int base = 0) {
   if (VEC == 3) {
     // pairs of consecutive entries through one 8-byte index load and one 16-byte value load, lanes on CONSECUTIVE pairs
     // (as VEC == 2, which needs every row pointer even; here the loads are only 4- / 8-byte aligned).  Half the
@@ -111,10 +132,7 @@ __device__ __forceinline__ void stream_products(const int *__restrict__ col, con
     // four 16-byte value loads — were measured on the triangular kernel and are SLOWER, 0.46 -> 0.64 ms per ILU(S)
     // apply: an instruction whose lanes sit 64 bytes apart touches 32 lines instead of 8.)
     constexpr int U = kStreamNnz / (2 * BLK);
-    typedef int vi2 __attribute__((ext_vector_type(2)));
-    typedef double vd2 __attribute__((ext_vector_type(2)));
     typedef V vv2 __attribute__((ext_vector_type(2)));
-    typedef vi2 vi2u __attribute__((aligned(4)));
     typedef vv2 vd2u __attribute__((aligned(sizeof(V))));
     int c0[U], c1[U];
     double v0[U], v1[U], x0[U], x1[U];
@@ -122,12 +140,12 @@ __device__ __forceinline__ void stream_products(const int *__restrict__ col, con
     for (int u = 0; u < U; ++u) {
       const int k = k0 + 2 * ((int)threadIdx.x + u * BLK);
       if (k + 1 < k1) {
-        const vi2 ci = *reinterpret_cast<const vi2u *>(col + k);
+        const IdxPair<I> ci(*reinterpret_cast<const typename IdxPair<I>::unaligned *>(col + k), base);
         const vv2 vi = *reinterpret_cast<const vd2u *>(val + k);
-        c0[u] = ci[0]; c1[u] = ci[1]; v0[u] = (double)vi[0]; v1[u] = (double)vi[1];
+        c0[u] = ci.a; c1[u] = ci.b; v0[u] = (double)vi[0]; v1[u] = (double)vi[1];
       } else {   // the run's odd last entry (nothing may be read behind it), or nothing
         const bool ok = k < k1;
-        c0[u] = ok ? col[k] : 0; v0[u] = ok ? (double)val[k] : 0.0; c1[u] = 0; v1[u] = 0.0;
+        c0[u] = ok ? base + (int)col[k] : 0; v0[u] = ok ? (double)val[k] : 0.0; c1[u] = 0; v1[u] = 0.0;
       }
     }
 #pragma unroll
@@ -150,7 +168,10 @@ __device__ __forceinline__ void stream_products(const int *__restrict__ col, con
     for (int u = 0; u < U; ++u) {
       const int k = k0 + 2 * ((int)threadIdx.x + u * BLK);
       const bool ok = k < k1;
-      c[u] = ok ? *reinterpret_cast<const int2 *>(col + k) : make_int2(0, 0);
+      if (ok) {
+        const IdxPair<I> ci(*reinterpret_cast<const typename IdxPair<I>::aligned2 *>(col + k), base);
+        c[u] = make_int2(ci.a, ci.b);
+      } else c[u] = make_int2(0, 0);
       v[u] = ok ? widen2(*reinterpret_cast<const V2 *>(val + k)) : make_double2(0.0, 0.0);
     }
     double x0[U], x1[U];
@@ -172,7 +193,7 @@ __device__ __forceinline__ void stream_products(const int *__restrict__ col, con
     for (int u = 0; u < U; ++u) {
       const int k = k0 + (int)threadIdx.x + u * BLK;
       const bool ok = k < k1;
-      c[u] = ok ? col[k] : 0;
+      c[u] = ok ? base + (int)col[k] : 0;
       v[u] = ok ? (double)val[k] : 0.0;
     }
 #pragma unroll
@@ -203,13 +224,18 @@ __device__ __forceinline__ double row_sum_lds(const double *prod, int b, int e, 
 // A run holds at most kStreamRows = BLK/RG rows, so the reduce phase is ONE pass: lane group t/RG owns
 // row r0 + t/RG, and its row bounds (and, in the triangular kernels, perm / rhs / diagonal) are
 // loaded BEFORE the streaming phase so their latency hides behind it.
-template <class V, int VEC, int MODE>
+// I = unsigned short: off16 / colbase (one base per run, read beside rowblk) replace A.col
+template <class V, int VEC, int MODE, class I = int>
 __global__ __launch_bounds__(BLK) void spmv_stream_kernel(CsrViewT<V> A, const int *__restrict__ rowblk,
                                                           const double *__restrict__ xo,
                                                           const double *__restrict__ xg, double *__restrict__ y,
-                                                          const double *__restrict__ z) {
+                                                          const double *__restrict__ z,
+                                                          const unsigned short *__restrict__ off16 = nullptr,
+                                                          const int *__restrict__ colbase = nullptr) {
   __shared__ double prod[kStreamNnz];
   const int r0 = rowblk[blockIdx.x], r1 = rowblk[blockIdx.x + 1];
+  constexpr bool I16 = std::is_same<I, unsigned short>::value;
+  const int base = I16 ? colbase[blockIdx.x] : 0;
   const int k0 = A.rowptr[r0], k1 = A.rowptr[r1];
   const int r = r0 + (int)threadIdx.x / RG, lane = threadIdx.x % RG;
   const bool have = r < r1;
@@ -221,7 +247,8 @@ __global__ __launch_bounds__(BLK) void spmv_stream_kernel(CsrViewT<V> A, const i
     if (MODE == 1) zv = z ? z[r] : y[r];
     if (MODE == 2) zv = z[r];
   }
-  stream_products<V, VEC>(A.col, A.val, k0, k1, A.n_own_cols, xo, xg, prod);
+  if constexpr (I16) stream_products<V, VEC, unsigned short>(off16, A.val, k0, k1, A.n_own_cols, xo, xg, prod, base);
+  else stream_products<V, VEC>(A.col, A.val, k0, k1, A.n_own_cols, xo, xg, prod);
   __syncthreads();
   const double sum = row_sum_lds(prod, jb, je, lane);
   if (have && lane == 0) {
@@ -378,7 +405,7 @@ __global__ __launch_bounds__(BLK) void spmv_blk_fused_kernel(BlkView A, const do
 
 // Streamed level of a triangular solve on split CSR halves (scalar factors): rows of the level are contiguous in the
 // permuted (colour) order, the solution vector w and the column ids stay in the caller's numbering (i = perm[r]).
-template <class V, int LOWER, int KIND, int NNZ>
+template <class V, int LOWER, int KIND, int NNZ, int I16 = 0>
 __global__ __launch_bounds__(BLK) void tri_stream_kernel(TriHalfT<V> M, int b0, int nb, const double *__restrict__ dinv,
                                                          const int *__restrict__ perm,
                                                          const double *__restrict__ rhs, double *__restrict__ w) {
@@ -391,6 +418,7 @@ __global__ __launch_bounds__(BLK) void tri_stream_kernel(TriHalfT<V> M, int b0, 
   if (mapped >= nb) return;
   const int4 d = M.desc[b0 + mapped];
   const int r0 = d.x, r1 = d.y, k0 = d.z, k1 = d.w;
+  const int base = I16 ? M.base[b0 + mapped] : 0;   // 16-bit offsets: the run's smallest column (M.base runs beside M.desc)
   const int r = r0 + (int)threadIdx.x / RG, lane = threadIdx.x % RG;
   const bool have = r < r1;
   int jb = 0, je = 0, i = 0;
@@ -412,7 +440,8 @@ __global__ __launch_bounds__(BLK) void tri_stream_kernel(TriHalfT<V> M, int b0, 
     for (int u = 0; u < U; ++u) {
       const int k = k0 + (int)threadIdx.x + u * BLK;
       const bool ok = k < k1;
-      c[u] = ok ? __builtin_nontemporal_load(M.col + k) : 0;
+      if (I16) c[u] = ok ? base + (int)__builtin_nontemporal_load(M.off16 + k) : 0;
+      else c[u] = ok ? __builtin_nontemporal_load(M.col + k) : 0;
       v[u] = ok ? (double)__builtin_nontemporal_load(M.val + k) : 0.0;   // (float halves: widened here)
     }
 #pragma unroll
@@ -564,8 +593,11 @@ __device__ __forceinline__ double sf_wait(const double *p, unsigned long long fi
 // loads): ILU(S) apply 0.459 -> 0.637 ms at 1200x400, lanes 32 / 64 bytes apart touch four times the lines per instruction.
 // V = float (factor stored in single precision): a pair is one 8-byte value load, still lane-contiguous; values are widened
 // to double as they land in registers.
-template <class V, int LOWER, int KIND, int NNZ, int GMAX>
-__global__ __launch_bounds__(BLK, 8) void tri_stream_sf_kernel(TriHalfT<V> M, const int4 *__restrict__ desc, int nb, int wrong_order,
+// I16 = 1: 16-bit column offsets (M.off16) on top of one base per run (`base`, beside `desc`, a scalar load like it): a
+// pair of offsets is one 4-byte load, 2-byte aligned where a run starts at an odd entry.
+template <class V, int LOWER, int KIND, int NNZ, int GMAX, int I16 = 0>
+__global__ __launch_bounds__(BLK, 8) void tri_stream_sf_kernel(TriHalfT<V> M, const int4 *__restrict__ desc,
+                                                            const int *__restrict__ base, int nb, int wrong_order,
                                                             const double *__restrict__ dinv,
                                                             const int *__restrict__ perm,
                                                             const double *__restrict__ rhs,
@@ -585,8 +617,10 @@ __global__ __launch_bounds__(BLK, 8) void tri_stream_sf_kernel(TriHalfT<V> M, co
   // wrong_order (test hook): walk the list backwards, i.e. consumers before their producers, to exercise
   // the bounded-spin / fallback path
   // (desc == M.desc, handed over as a read-only pointer of its own: the uniform load becomes a scalar load)
-  const int4 d = desc[wrong_order ? nb - 1 - (int)blockIdx.x : (int)blockIdx.x];
+  const int bid = wrong_order ? nb - 1 - (int)blockIdx.x : (int)blockIdx.x;
+  const int4 d = desc[bid];
   const int r0 = d.x, r1 = d.y, k0 = d.z, k1 = d.w;
+  const unsigned base8 = I16 ? (unsigned)base[bid] << 3 : 0u;   // byte offset of the run's smallest column
   if (r0 == r1) return;  // padding run
   if (dbg && threadIdx.x == 0) dbg[(size_t)blockIdx.x * 16 + 9] = (long long)__builtin_amdgcn_s_memrealtime() + (r0 & 0);   // descriptor has arrived
   const int r = r0 + (int)threadIdx.x / RG, lane = threadIdx.x % RG;
@@ -598,6 +632,8 @@ __global__ __launch_bounds__(BLK, 8) void tri_stream_sf_kernel(TriHalfT<V> M, co
     const bool any = k0 < k1;   // (uniform) false: rows without entries; every lane then reads valid stand-in words
     const int kz = any ? k0 : 0;
     const int *colp = any ? M.col : M.rowptr;
+    // (16-bit offsets: the stand-in is rowptr[0] = 0, two zero offsets on top of base 0 of a run without entries)
+    const unsigned short *offp = any ? M.off16 : reinterpret_cast<const unsigned short *>(M.rowptr);
     const V *valp = any ? M.val : reinterpret_cast<const V *>(w);   // (stand-in of the value type: never used)
     unsigned o[U];   // byte offset of the gathered entry (32 bits on top of the uniform base)
     unsigned open = 0;   // bit u: entry u still shows the sentinel
@@ -616,9 +652,17 @@ __global__ __launch_bounds__(BLK, 8) void tri_stream_sf_kernel(TriHalfT<V> M, co
 #pragma unroll
       for (int c = 0; c < U / 2; ++c) {
         const int k = k0 + 2 * (tb + c * BLK), kk = (any && k < k1) ? k : kz;   // (the arrays end with spare entries)
-        const vi2 q = __builtin_nontemporal_load(reinterpret_cast<const vi2u *>(colp + kk));
         const vd2 t = __builtin_nontemporal_load(reinterpret_cast<const vd2u *>(valp + kk));
-        o[2 * c] = (unsigned)q[0]; o[2 * c + 1] = (unsigned)q[1];
+        if (I16) {
+          typedef unsigned u32h __attribute__((aligned(2)));
+          const unsigned q = __builtin_nontemporal_load(reinterpret_cast<const u32h *>(offp + kk));
+          // the word behind a run's odd last entry is another run's offset: base + that may lie outside w, so it is dropped
+          // (the first entry of a pair is always the run's own: a pair outside the run re-reads its first one, kk = kz)
+          o[2 * c] = q & 0xffffu; o[2 * c + 1] = kk + 1 < k1 ? q >> 16 : 0u;
+        } else {
+          const vi2 q = __builtin_nontemporal_load(reinterpret_cast<const vi2u *>(colp + kk));
+          o[2 * c] = (unsigned)q[0]; o[2 * c + 1] = (unsigned)q[1];
+        }
         v[2 * c] = t[0]; v[2 * c + 1] = t[1];
       }
       // row bounds, perm and the row's own right-hand side (which hangs on perm[r]) are asked for AFTER the streaming
@@ -639,7 +683,7 @@ __global__ __launch_bounds__(BLK, 8) void tri_stream_sf_kernel(TriHalfT<V> M, co
       }
 #pragma unroll
       for (int u = 0; u < U; ++u) {
-        o[u] <<= 3;
+        o[u] = (o[u] << 3) + base8;
         g[u] = sf_peek(reinterpret_cast<const double *>(wb + o[u]));
       }
       // first look done: the product of every entry whose value was there goes to LDS now; an open entry parks its
@@ -1392,9 +1436,13 @@ int spmv(hipStream_t s, const CsrView &A, int lpr, const double *xo, const doubl
 }
 
 int spmv_stream(hipStream_t s, const CsrView &A, const int *rowblk, int nblk, int even_rows, const double *xo,
-                const double *xg, double *y, int mode, const double *z) {
+                const double *xg, double *y, int mode, const double *z, const unsigned short *off16, const int *colbase) {
   if (nblk <= 0) return 0;
-#define NSK_SS(V, M) hipLaunchKernelGGL((spmv_stream_kernel<double, V, M>), dim3(nblk), dim3(BLK), 0, s, A, rowblk, xo, xg, y, z)
+#define NSK_SS(V, M)                                                                                                                   \
+  do {                                                                                                                                 \
+    if (off16) hipLaunchKernelGGL((spmv_stream_kernel<double, V, M, unsigned short>), dim3(nblk), dim3(BLK), 0, s, A, rowblk, xo, xg, y, z, off16, colbase); \
+    else hipLaunchKernelGGL((spmv_stream_kernel<double, V, M, int>), dim3(nblk), dim3(BLK), 0, s, A, rowblk, xo, xg, y, z, off16, colbase); \
+  } while (0)
   // pairs of entries per lane: 16-byte aligned where every row pointer is even, 4- / 8-byte aligned loads otherwise
   // (S: 0.271 -> 0.264 ms at 1200x400 against one entry per load)
   if (even_rows) {
@@ -1407,11 +1455,15 @@ int spmv_stream(hipStream_t s, const CsrView &A, const int *rowblk, int nblk, in
 }
 
 int spmv_stream(hipStream_t s, const CsrView32 &A, const int *rowblk, int nblk, int even_rows, const double *xo,
-                const double *xg, double *y) {
+                const double *xg, double *y, const unsigned short *off16, const int *colbase) {
   if (nblk <= 0) return 0;
   // the double launcher's choice of pair loads: the same lanes sum the same entries
   const double *z = nullptr;
-#define NSK_SS(V) hipLaunchKernelGGL((spmv_stream_kernel<float, V, 0>), dim3(nblk), dim3(BLK), 0, s, A, rowblk, xo, xg, y, z)
+#define NSK_SS(V)                                                                                                                      \
+  do {                                                                                                                                 \
+    if (off16) hipLaunchKernelGGL((spmv_stream_kernel<float, V, 0, unsigned short>), dim3(nblk), dim3(BLK), 0, s, A, rowblk, xo, xg, y, z, off16, colbase); \
+    else hipLaunchKernelGGL((spmv_stream_kernel<float, V, 0, int>), dim3(nblk), dim3(BLK), 0, s, A, rowblk, xo, xg, y, z, off16, colbase); \
+  } while (0)
   if (even_rows) { NSK_SS(2); return 2; }
   NSK_SS(3);
   return 3;
@@ -1479,9 +1531,11 @@ static void tri_stream_level_t(hipStream_t s, const TriHalfT<V> &M, int b0, int 
   if (nb <= 0) return;
   const int grid = ((nb + 7) / 8) * 8;
 #define NSK_TS(L, K, N) hipLaunchKernelGGL((tri_stream_kernel<V, L, K, N>), dim3(grid), dim3(BLK), 0, s, M, b0, nb, dinv, perm, rhs, w)
+  // 16-bit offsets: one instantiation per half and kind (the run cap only sizes the LDS array and the trip count)
 #define NSK_TSN(L, K)                                            \
   do {                                                           \
-    if (run_nnz <= 512) NSK_TS(L, K, 512);                       \
+    if (M.off16) hipLaunchKernelGGL((tri_stream_kernel<V, L, K, 2048, 1>), dim3(grid), dim3(BLK), 0, s, M, b0, nb, dinv, perm, rhs, w); \
+    else if (run_nnz <= 512) NSK_TS(L, K, 512);                  \
     else if (run_nnz <= 1024) NSK_TS(L, K, 1024);                \
     else NSK_TS(L, K, 2048);                                     \
   } while (0)
@@ -1580,18 +1634,20 @@ static void tri_stream_syncfree_t(hipStream_t s, const TriHalfT<V> &M, int nb, i
                                   int wrong_order, const double *dinv, const int *perm, const double *rhs, const double *own,
                                   double *w, double *reset, int *err, long long *dbg, TriChainT<V> ch) {
   if (nb <= 0) return;
-#define NSK_SF(L, K, N, G) hipLaunchKernelGGL((tri_stream_sf_kernel<V, L, K, N, G>), dim3(nb), dim3(BLK), 0, s, M, M.desc, nb, wrong_order, dinv, perm, rhs, own, w, reset, err, dbg, ch.chain, ch.cpl)
-#define NSK_SFG(L, K, N)                                   \
+#define NSK_SF(L, K, N, G, I) hipLaunchKernelGGL((tri_stream_sf_kernel<V, L, K, N, G, I>), dim3(nb), dim3(BLK), 0, s, M, M.desc, M.base, nb, wrong_order, dinv, perm, rhs, own, w, reset, err, dbg, ch.chain, ch.cpl)
+#define NSK_SFG(L, K, N, I)                                \
   do {                                                     \
-    if (ch.gmax <= 1) NSK_SF(L, K, N, 1);                  \
-    else if (ch.gmax == 2) NSK_SF(L, K, N, 2);             \
-    else NSK_SF(L, K, N, 3);                               \
+    if (ch.gmax <= 1) NSK_SF(L, K, N, 1, I);               \
+    else if (ch.gmax == 2) NSK_SF(L, K, N, 2, I);          \
+    else NSK_SF(L, K, N, 3, I);                            \
   } while (0)
+  // 16-bit offsets: the kStreamNnz instantiation whatever the run cap (it only sizes the LDS array and the trip count)
 #define NSK_SFN(L, K)                                      \
   do {                                                     \
-    if (run_nnz <= 512) NSK_SFG(L, K, 512);                \
-    else if (run_nnz <= 1024) NSK_SFG(L, K, 1024);         \
-    else NSK_SFG(L, K, 2048);                              \
+    if (M.off16) NSK_SFG(L, K, 2048, 1);                   \
+    else if (run_nnz <= 512) NSK_SFG(L, K, 512, 0);        \
+    else if (run_nnz <= 1024) NSK_SFG(L, K, 1024, 0);      \
+    else NSK_SFG(L, K, 2048, 0);                           \
   } while (0)
   if (lower) { if (kind == 0) NSK_SFN(1, 0); else NSK_SFN(1, 1); }
   else { if (kind == 0) NSK_SFN(0, 0); else NSK_SFN(0, 1); }

@@ -128,7 +128,53 @@ __global__ __launch_bounds__(SBLK) void csr_split_kernel(int n, const int *__res
     (low ? lsrc : usrc)[w] = b + k;
   }
 }
+
+// 16-bit column offsets of the stream kernels.  One workgroup per run b of entries [k0, k1) — desc[b].z / .w, or
+// rowptr[rowblk[b]] / rowptr[rowblk[b + 1]] when desc is null.  FILL = 0: base[b] = the run's smallest column (0 for a run
+// without entries), *wide = 1 when a run spans more than 65 535 columns; FILL = 1: off[k] = col[k] - base[b].
+template <int FILL>
+__global__ __launch_bounds__(SBLK) void run_index16_kernel(int nb, const int4 *__restrict__ desc, const int *__restrict__ rowblk,
+                                                           const int *__restrict__ rowptr, const int *__restrict__ col,
+                                                           int *base, unsigned short *__restrict__ off, int *wide) {
+  __shared__ int lo[SBLK / 64], hi[SBLK / 64];
+  const int b = (int)blockIdx.x;
+  if (b >= nb) return;
+  const int k0 = desc ? desc[b].z : rowptr[rowblk[b]], k1 = desc ? desc[b].w : rowptr[rowblk[b + 1]];
+  if (FILL) {
+    const int bs = base[b];
+    for (int k = k0 + (int)threadIdx.x; k < k1; k += SBLK) off[k] = (unsigned short)(col[k] - bs);
+    return;
+  }
+  int mn = INT32_MAX, mx = INT32_MIN;
+  for (int k = k0 + (int)threadIdx.x; k < k1; k += SBLK) {
+    const int c = col[k];
+    mn = min(mn, c);
+    mx = max(mx, c);
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    mn = min(mn, __shfl_down(mn, o, 64));
+    mx = max(mx, __shfl_down(mx, o, 64));
+  }
+  if (threadIdx.x % 64 == 0) { lo[threadIdx.x / 64] = mn; hi[threadIdx.x / 64] = mx; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < SBLK / 64; ++w) { mn = min(mn, lo[w]); mx = max(mx, hi[w]); }
+    base[b] = k0 < k1 ? mn : 0;
+    if (k0 < k1 && (long long)mx - (long long)mn > 65535) *wide = 1;
+  }
+}
 }  // namespace
+
+void setup_run_col_base(hipStream_t s, int nb, const int4 *desc, const int *rowblk, const int *rowptr, const int *col,
+                        int *base, int *wide) {
+  if (nb <= 0) return;
+  hipLaunchKernelGGL((run_index16_kernel<0>), dim3(nb), dim3(SBLK), 0, s, nb, desc, rowblk, rowptr, col, base, nullptr, wide);
+}
+void setup_run_col_offsets(hipStream_t s, int nb, const int4 *desc, const int *rowblk, const int *rowptr, const int *col,
+                           const int *base, unsigned short *off) {
+  if (nb <= 0) return;
+  hipLaunchKernelGGL((run_index16_kernel<1>), dim3(nb), dim3(SBLK), 0, s, nb, desc, rowblk, rowptr, col, const_cast<int *>(base), off, nullptr);
+}
 
 void setup_permute_rows(hipStream_t s, int n, const int *a_rowptr, const int *a_col, const int *perm, const int *iperm,
                         const int *prp, int *pcol, int *psrc, int *pdiag, int max_row, int *err) {

@@ -788,6 +788,23 @@ void TriSolve::analyze(Ctx *c, const Csr &A, int kind_, int ordering_, const std
       }
       stream_ready = true;
       alloc_halves();
+      // the offsets are written against the bases of ld / ud and read by the single-launch kernels against bases of
+      // their own, taken over lsf / usf: the same numbers only because the dispatch order permutes (and pads) the SAME runs
+      auto same_runs = [](std::vector<int4> a, std::vector<int4> b) {
+        auto entries = [](std::vector<int4> &d) {
+          d.erase(std::remove_if(d.begin(), d.end(), [](const int4 &r) { return r.z == r.w; }), d.end());
+          std::sort(d.begin(), d.end(), [](const int4 &x, const int4 &y) { return x.z < y.z; });
+        };
+        entries(a);
+        entries(b);
+        if (a.size() != b.size()) return false;
+        for (size_t k = 0; k < a.size(); ++k)
+          if (a[k].z != b[k].z || a[k].w != b[k].w) return false;
+        return true;
+      };
+      if (want_index16 && !(same_runs(ld, lsf) && same_runs(ud, usf)))
+        throw Error(-34, "triangular factor: the dispatch-order runs are not the per-colour runs (16-bit column offsets)");
+      build_index16();
       ctx->sync();
     }
   }
@@ -970,6 +987,44 @@ void TriSolve::alloc_halves() {
   }
 }
 
+// 16-bit column offsets of the scalar halves: per run its smallest column (in the order of Ldesc and in the dispatch
+// order of Lsf), per entry the distance to it; all on the device, from the int32 columns, which are released afterwards
+void TriSolve::build_index16() {
+  for (DBuf<unsigned short> *b : {&Loff16, &Uoff16}) b->release();
+  for (DBuf<int> *b : {&Lbase, &Ubase, &Lsfbase, &Usfbase}) b->release();
+  if (!want_index16 || !stream_ready || !Lcol.p || !Ucol.p) return;
+  hipStream_t s = ctx->stream;
+  DBuf<int> wide;
+  wide.alloc(1);
+  NSK_HIP(hipMemsetAsync(wide.p, 0, sizeof(int), s));
+  const int nl = (int)Ldesc.n, nu = (int)Udesc.n;
+  Lbase.alloc((size_t)nl); Ubase.alloc((size_t)nu); Lsfbase.alloc((size_t)n_Lsf); Usfbase.alloc((size_t)n_Usf);
+  setup_run_col_base(s, nl, Ldesc.p, nullptr, nullptr, Lcol.p, Lbase.p, wide.p);
+  setup_run_col_base(s, nu, Udesc.p, nullptr, nullptr, Ucol.p, Ubase.p, wide.p);
+  setup_run_col_base(s, n_Lsf, Lsf.p, nullptr, nullptr, Lcol.p, Lsfbase.p, wide.p);
+  setup_run_col_base(s, n_Usf, Usf.p, nullptr, nullptr, Ucol.p, Usfbase.p, wide.p);
+  int w = 0;
+  NSK_HIP(hipMemcpyAsync(&w, wide.p, sizeof(int), hipMemcpyDeviceToHost, s));
+  ctx->sync();
+  if (w) {   // a run spans 65 536 columns or more: this factor keeps its int32 columns
+    for (DBuf<int> *b : {&Lbase, &Ubase, &Lsfbase, &Usfbase}) b->release();
+    static const bool chatty = [] { const char *e = getenv("NSK_VERBOSE"); return e && atoi(e) != 0; }();   // (as analyze())
+    if (chatty) fprintf(stderr, "[nsk] triangular factor (n = %d): a run spans 65 536 columns or more — int32 column ids\n", n);
+    return;
+  }
+  // (8 spare entries, as behind the int32 columns: the pair loads of the single-launch kernels may take the word behind a
+  //  run's last entry along)
+  Loff16.alloc((size_t)nnzL + 8);
+  Uoff16.alloc((size_t)nnzU + 8);
+  NSK_HIP(hipMemsetAsync(Loff16.p + nnzL, 0, 8 * sizeof(unsigned short), s));
+  NSK_HIP(hipMemsetAsync(Uoff16.p + nnzU, 0, 8 * sizeof(unsigned short), s));
+  setup_run_col_offsets(s, nl, Ldesc.p, nullptr, nullptr, Lcol.p, Lbase.p, Loff16.p);
+  setup_run_col_offsets(s, nu, Udesc.p, nullptr, nullptr, Ucol.p, Ubase.p, Uoff16.p);
+  ctx->sync();
+  Lcol.release();
+  Ucol.release();
+}
+
 bool TriSolve::halves_in_use() const {   // (the decisions of apply(), in its order)
   const bool tiny = (double)nnz * 12.0 < tiny_bytes && !schedL.empty();
   if (!use_stream || tiny || !(stream_ready || block2_ready)) return false;
@@ -980,7 +1035,7 @@ double TriSolve::format_bytes() const {
   // (values: 8 bytes each, 4 when the halves in use are single precision)
   const double vb = value_bytes();
   if (stream_ready)   // CSR halves + per run: descriptor; per row: rowptr x2, perm x2, rhs, dinv, y (store + load), x (fill + store)
-    return (4.0 + vb) * (double)(nnzL + nnzU) + 16.0 * (double)(n_Lsf + n_Usf) + (8.0 + 8.0 + 8.0 + 8.0 + 16.0 + 16.0 + 16.0) * (double)n;
+    return ((Loff16.p ? 2.0 : 4.0) + vb) * (double)(nnzL + nnzU) + (Loff16.p ? 20.0 : 16.0) * (double)(n_Lsf + n_Usf) + (8.0 + 8.0 + 8.0 + 8.0 + 16.0 + 16.0 + 16.0) * (double)n;
   if (block2_ready)   // 2x2 blocks with one int32 block column + per node row: descriptor share, intra, rhs, y, x
     return (4.0 + 4.0 * vb) * (double)(nnzL + nnzU) / 4.0 + 8.0 * (double)(n / 2) + (32.0 + 4.0 + 48.0) * (double)(n / 2);
   return (double)apply_bytes();
@@ -1049,9 +1104,9 @@ void TriSolve::apply(const double *b, double *x) {
       tri_stream_syncfree(s, U, n_Usf, 0, kind, kStreamNnz, sf_fault ? 1 : 0, dinv.p, d_perm.p, nullptr, y.p, x, y.p, sf_err.p,
                           sf_dbg ? sf_dbg + (size_t)n_Lsf * 16 : nullptr, cu);
     };
-    if (f32) run(TriHalf32{Lrp.p, Lcol.p, Lval32.p, Lsf.p}, TriHalf32{Urp.p, Ucol.p, Uval32.p, Usf.p},
+    if (f32) run(half(true, Lval32.p, true), half(false, Uval32.p, true),
                  TriChain32{gmax, chain.p, Lcpl32.p}, TriChain32{gmax, chain.p, Ucpl32.p});
-    else run(TriHalf{Lrp.p, Lcol.p, Lval.p, Lsf.p}, TriHalf{Urp.p, Ucol.p, Uval.p, Usf.p},
+    else run(half(true, Lval.p, true), half(false, Uval.p, true),
              TriChain{gmax, chain.p, Lcpl.p}, TriChain{gmax, chain.p, Ucpl.p});
     ++ctx->st.tri_applies;
     ctx->st.tri_bytes += (double)apply_bytes();
@@ -1063,8 +1118,8 @@ void TriSolve::apply(const double *b, double *x) {
       for (int c = 0; c < n_colors; ++c) tri_stream_level(s, L, LB[c], LB[c + 1], 1, kind, kStreamNnz, dinv.p, d_perm.p, b, x);
       for (int c = n_colors - 1; c >= 0; --c) tri_stream_level(s, U, UB[c], UB[c + 1], 0, kind, kStreamNnz, dinv.p, d_perm.p, nullptr, x);
     };
-    if (f32) run(TriHalf32{Lrp.p, Lcol.p, Lval32.p, Ldesc.p}, TriHalf32{Urp.p, Ucol.p, Uval32.p, Udesc.p});
-    else run(TriHalf{Lrp.p, Lcol.p, Lval.p, Ldesc.p}, TriHalf{Urp.p, Ucol.p, Uval.p, Udesc.p});
+    if (f32) run(half(true, Lval32.p, false), half(false, Uval32.p, false));
+    else run(half(true, Lval.p, false), half(false, Uval.p, false));
     ++ctx->st.tri_applies;
     ctx->st.tri_bytes += (double)apply_bytes();
     return;

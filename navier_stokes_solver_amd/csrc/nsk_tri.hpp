@@ -73,6 +73,19 @@ struct TriSolve {
   DBuf<int4> Ldesc, Udesc;
   DBuf<int4> Lsf, Usf;     // the same runs in the dispatch order of the single-launch kernels
   int n_Lsf = 0, n_Usf = 0;
+  // 16-bit column offsets of the scalar halves (NSK_IOPT_INDEX16): Loff16[k] = Lcol[k] - (smallest column of the
+  // run k lies in); the bases beside Ldesc (Lbase) and beside Lsf (Lsfbase, dispatch order; padding runs: 0).  Built in
+  // analyze() when every run of BOTH halves spans fewer than 65 536 columns; Lcol / Ucol are then released (only the
+  // stream kernels read them).  numeric() never touches any of this.
+  bool want_index16 = false;   // (the handle asks for it on S and M_p)
+  DBuf<unsigned short> Loff16, Uoff16;
+  DBuf<int> Lbase, Ubase, Lsfbase, Usfbase;
+  void build_index16();
+  template <class V>
+  TriHalfT<V> half(bool lower, const V *v, bool sf) const {
+    return lower ? TriHalfT<V>{Lrp.p, Lcol.p, v, sf ? Lsf.p : Ldesc.p, Loff16.p, Loff16.p ? (sf ? Lsfbase.p : Lbase.p) : nullptr}
+                 : TriHalfT<V>{Urp.p, Ucol.p, v, sf ? Usf.p : Udesc.p, Uoff16.p, Uoff16.p ? (sf ? Usfbase.p : Ubase.p) : nullptr};
+  }
   DBuf<double> Lval, Uval, dinv;
   // Single-precision storage of the off-diagonal values of the split halves (NSK_OPT_FACTOR_PRECISION = 32): Lval32 / Uval32
   // (and Lcpl32 / Ucpl32) replace Lval / Uval (Lcpl / Ucpl), which are then not allocated.  The combined factor `val`, the

@@ -39,6 +39,7 @@ OPT_INNER_MATRIX_PRECISION = 17  # 64 (default) / 32: inner solves multiply by f
 TIMEOP_INNER_SPMV = 50     # time_op(TIMEOP_INNER_SPMV + blk): the inner solves' SpMV of F, M_p or S
 IOPT_FUSED_MGS, IOPT_OVERLAP_HALO = 106, 107
 IOPT_TIMEOP_BETWEEN = 109  # time_op: SpMV of this block between two repetitions, outside the timed brackets (-1: back to back)
+IOPT_INDEX16 = 110         # 1 (default): 16-bit column offsets in the scalar stream kernels of S and M_p where every run qualifies; 0: int32
 IOPT_HOST_ANALYSIS = 108   # 1: symbolic set-up of the multicolour factors on the host (A/B, tests); default: on the device
 ORDER_NATURAL, ORDER_MULTICOLOR = 0, 1
 
@@ -394,6 +395,14 @@ class LinearSolver:
         b = C.c_int32(0)
         self._ck(self.L.nsk_inner_value_bytes(self.h, blk, C.byref(b)))
         return b.value
+
+    def index_width(self, blk):
+        """(SpMV, lower half, upper half) of BLK_S or BLK_MP in the current set-up: 16 where the scalar stream kernel reads
+        16-bit column offsets, 32 where it reads int32 column ids, 0 where the operation takes another kernel."""
+        w = np.zeros(3, np.int32)
+        self.L.nsk_debug_index_width.argtypes = [C.c_void_p, C.c_int, C.c_void_p]   # (nsk_internal.h: not in EXPORTS)
+        self._ck(self.L.nsk_debug_index_width(self.h, blk, w.ctypes.data))
+        return tuple(int(v) for v in w)
 
     def inner_spmv(self, blk, x):
         """y = A x with the values, kernel and row runs the inner solves use (BLK_F, BLK_S or BLK_MP); collective."""
