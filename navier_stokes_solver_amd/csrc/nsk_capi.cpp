@@ -1178,6 +1178,10 @@ int nsk_set_option(nsk_handle h, int opt, double v) {
       (opt == NSK_IOPT_GROUP_U ? h->group_u : h->group_p) = (int)v;
       break;
     case NSK_IOPT_FUSED_MGS: h->ctx.fused_mgs = v != 0.0; break;
+    case NSK_IOPT_GS_ONE_LAUNCH:
+      if (v != 0.0 && v != 1.0 && v != 2.0) throw Error(-61, "one-launch Gram-Schmidt sweeps: 0, 1 or 2");
+      h->ctx.gs_one_launch = (int)v;
+      break;
     case NSK_IOPT_OVERLAP_HALO: h->overlap_halo = v != 0.0; break;
     case NSK_IOPT_TINY_BYTES: h->tF.tiny_bytes = h->tMp.tiny_bytes = h->tS.tiny_bytes = v; break;
     case NSK_OPT_BSR_VELOCITY: h->use_bsr = v != 0.0; break;
@@ -1778,10 +1782,11 @@ int nsk_debug_krylov(nsk_handle h, int op, int n, int m, int offset, const doubl
   NSK_TRY(h)
   (void)hipSetDevice(h->ctx.device);
   Ctx &c = h->ctx;
-  static const int kVecs[] = {2, 1, 3, 2, 4, -1, -1, -1, 3, 0, 6, 4, 3};   // vectors per op (-1: m + 1)
-  if (op < NSK_DBG_KRY_DOT || op > NSK_DBG_KRY_DENSE_MV) throw Error(-65, "nsk_debug_krylov: unknown op");
+  static const int kVecs[] = {2, 1, 3, 2, 4, -1, -1, -1, 3, 0, 6, 4, 3, -1, -1, -1};   // vectors per op (-1: m + 1)
+  if (op < NSK_DBG_KRY_DOT || op > NSK_DBG_KRY_MULTI_ADD) throw Error(-65, "nsk_debug_krylov: unknown op");
   const bool multi = kVecs[op] < 0;
-  if (multi && (m < 1 || m > (op == NSK_DBG_KRY_GS_COLUMN ? kMgsMaxVecs : 8))) throw Error(-61, "nsk_debug_krylov: m");
+  const bool chunk = op == NSK_DBG_KRY_MULTI_DOT || op == NSK_DBG_KRY_MULTI_AXPY;   // (one launch of the chunked kernels)
+  if (multi && (m < 1 || m > (chunk ? 8 : kMgsMaxVecs))) throw Error(-61, "nsk_debug_krylov: m");
   if (n < 1 || (offset != 0 && offset != 1) || n_vec != (multi ? m + 1 : kVecs[op]))
     throw Error(-61, "nsk_debug_krylov: n, offset or number of vectors");
   for (int k = 0; k < n_vec; ++k)
@@ -1810,6 +1815,7 @@ int nsk_debug_krylov(nsk_handle h, int op, int n, int m, int offset, const doubl
     NSK_HIP(hipMemcpyAsync(c.slot(so), par, sizeof(double) * (size_t)count, hipMemcpyHostToDevice, st));
   };
   c.red_paths = 0;
+  const long gs_launches = c.gs_launches;
   int path = -1;
   switch (op) {
     case NSK_DBG_KRY_DOT: c.dot(n, d[0], d[1], so); break;
@@ -1845,6 +1851,15 @@ int nsk_debug_krylov(nsk_handle h, int op, int n, int m, int offset, const doubl
       break;
     case NSK_DBG_KRY_CHEBY: vec_cheby_step(st, n, par[0], par[1], d[0], d[1], d[2], d[3], (int)par[2]); break;
     case NSK_DBG_KRY_DENSE_MV: dense_mv(st, n, d[0], d[1], d[2]); break;
+    case NSK_DBG_KRY_MULTI_DOT_ALL:
+      c.multi_dot_all(n, d[0], d.data() + 1, m, so);
+      c.allreduce_slots(so, m);
+      break;
+    case NSK_DBG_KRY_MULTI_AXPY_ALL:
+      set_slots(m);
+      c.multi_axpy_all(n, d[0], d.data() + 1, m, so, par[m] != 0.0 ? so + m : -1);
+      break;
+    case NSK_DBG_KRY_MULTI_ADD: c.multi_add(n, d[0], d.data() + 1, par, m); break;
   }
   int bad_guards = 0;
   std::vector<double> all;
@@ -1867,7 +1882,8 @@ int nsk_debug_krylov(nsk_handle h, int op, int n, int m, int offset, const doubl
   info8[1] = path;
   info8[2] = std::min(c.n_cu, kMgsThreads);
   info8[3] = bad_guards;
-  for (int k = 4; k < 8; ++k) info8[k] = 0;
+  info8[4] = (int32_t)(c.gs_launches - gs_launches);
+  for (int k = 5; k < 8; ++k) info8[k] = 0;
   return 0;
   NSK_CATCH(h)
 }
@@ -2395,6 +2411,27 @@ int nsk_time_op(nsk_handle h, int op, int reps, double *avg_ms, double *bytes) {
       if (op == 33) h->ctx.multi_dot(n, (*vs)[8], vs->data(), 8, cs, true);
       else h->ctx.multi_axpy(n, (*vs)[8], vs->data(), 8, cs, -1);
     };
+    for (double *p : *vs) h->pool_u.put(p);   // (stay valid until the pool hands them out again: not during this call)
+  } else if (op >= 35 && op <= 37) {
+    // the same sweeps over a whole basis of 30 (Ctx::multi_dot_all / multi_axpy_all with the norm) and the cycle-end update
+    // of 29 terms (Ctx::multi_add), as NSK_IOPT_GS_ONE_LAUNCH launches them; bytes: what the chosen form moves
+    const int n = h->n_u(), m = op == 37 ? 29 : 30;
+    auto vs = std::make_shared<std::vector<double *>>();
+    for (int k = 0; k <= m; ++k) {
+      vs->push_back(h->pool_u.get(true));
+      vec_set(h->s(), n, vs->back(), 1.0 / (k + 1));
+    }
+    const int cs = h->ctx.alloc_slots(m + 2);
+    NSK_HIP(hipMemsetAsync(h->ctx.slot(cs), 0, sizeof(double) * (m + 2), h->s()));   // (update: coefficients 0, w stays put)
+    auto yz = std::make_shared<std::vector<double>>((size_t)m, 1e-9);
+    f = [=]() {
+      if (op == 35) h->ctx.multi_dot_all(n, (*vs)[m], vs->data(), m, cs);
+      else if (op == 36) h->ctx.multi_axpy_all(n, (*vs)[m], vs->data(), m, cs, cs + m);
+      else h->ctx.multi_add(n, (*vs)[m], vs->data(), yz->data(), m);
+    };
+    const double b0 = h->ctx.st.blas1_bytes;
+    f();
+    by = h->ctx.st.blas1_bytes - b0;
     for (double *p : *vs) h->pool_u.put(p);   // (stay valid until the pool hands them out again: not during this call)
   } else if (op == 40 || op == 41) {
     // host round trip of one device scalar (what every Krylov iteration pays for its SolverControl check): wall time

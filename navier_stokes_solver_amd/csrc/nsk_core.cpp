@@ -464,6 +464,62 @@ void Ctx::multi_axpy(int n, double *w, double *const *v, int m, int coef_slot, i
   st.blas1_bytes += 8.0 * n * (m + 2);
 }
 
+void Ctx::multi_dot_all(int n, const double *w, double *const *v, int m, int so) {
+  const int cap = gs_one_launch == 1 ? kMgsMaxVecs : gs_one_launch == 2 ? 16 : 8;
+  for (int i0 = 0; i0 < m; i0 += cap) {
+    const int mc = std::min(cap, m - i0);
+    VecPackAll P{};
+    for (int k = 0; k < mc; ++k) P.v[k] = v[i0 + k];
+    const int ran = vec_multi_dot_all(stream, ws, n, w, P, mc, slot(so + i0));   // (0: mc <= 8 or the pair form does not apply)
+    if (ran) {
+      red_paths |= ran;
+      st.blas1_bytes += 8.0 * n * (mc + 1);
+      ++gs_launches;
+    } else {
+      for (int c0 = 0; c0 < mc; c0 += 8, ++gs_launches) multi_dot(n, w, v + i0 + c0, std::min(8, mc - c0), so + i0 + c0, true);
+    }
+  }
+}
+void Ctx::multi_axpy_all(int n, double *w, double *const *v, int m, int coef_slot, int norm_slot) {
+  const int cap = gs_one_launch == 1 ? kMgsMaxVecs : gs_one_launch == 2 ? 16 : 8;
+  for (int i0 = 0; i0 < m; i0 += cap) {
+    const int mc = std::min(cap, m - i0);
+    const int ns = i0 + mc == m ? norm_slot : -1;   // the norm belongs to the launch that stores the final w
+    VecPackAll P{};
+    for (int k = 0; k < mc; ++k) P.v[k] = v[i0 + k];
+    const int ran = vec_multi_axpy_all(stream, ws, n, w, P, mc, slot(coef_slot + i0), ns >= 0 ? slot(ns) : nullptr);
+    if (ran) {
+      red_paths |= ran;
+      if (ns >= 0 && comm.active()) {
+        comm.allreduce_sum(slot(ns), 1, stream);
+        scalar_sqrt(stream, slot(ns), slot(ns) + 1);
+      }
+      if (ns >= 0) ++st.reductions;
+      st.blas1_bytes += 8.0 * n * (mc + 2);
+      ++gs_launches;
+    } else {
+      for (int c0 = 0; c0 < mc; c0 += 8, ++gs_launches)
+        multi_axpy(n, w, v + i0 + c0, std::min(8, mc - c0), coef_slot + i0 + c0, c0 + 8 >= mc ? ns : -1);
+    }
+  }
+}
+void Ctx::multi_add(int n, double *x, double *const *z, const double *y, int m) {
+  const int cap = gs_one_launch == 1 ? kMgsMaxVecs : gs_one_launch == 2 ? 16 : 1;
+  for (int i0 = 0; i0 < m; i0 += cap) {
+    const int mc = std::min(cap, m - i0);
+    VecPackAll Z{};
+    CoefPack Y{};
+    for (int k = 0; k < mc; ++k) { Z.v[k] = z[i0 + k]; Y.y[k] = y[i0 + k]; }
+    if (gs_one_launch && vec_multi_add(stream, n, x, Z, Y, mc)) {
+      st.blas1_bytes += 8.0 * n * (mc + 2);
+      ++gs_launches;
+    } else {
+      for (int k = 0; k < mc; ++k, ++gs_launches) vec_axpy(stream, n, sref(y[i0 + k]), z[i0 + k], x);
+      st.blas1_bytes += 24.0 * n * mc;
+    }
+  }
+}
+
 bool Ctx::mgs_applicable(int n, int nv) const {
   if (!fused_mgs || comm.active() || nv < 1 || nv > kMgsMaxVecs) return false;
   const int G = std::min(n_cu, kMgsThreads);

@@ -289,6 +289,17 @@ struct Ctx {
   void multi_dot(int n, const double *w, double *const *v, int m, int slot_out, bool defer = false);
   void allreduce_slots(int first, int count);
   void multi_axpy(int n, double *w, double *const *v, int m, int coef_slot, int norm_slot);
+  // The same two sweeps over a whole basis of m <= kMgsMaxVecs vectors, and FGMRES' cycle-end update.
+  // gs_one_launch (NSK_IOPT_GS_ONE_LAUNCH) and m > 8: ONE launch each where the pair kernels apply — at most gs_cap
+  // vectors per launch — else the chunks of eight above, one launch per chunk.  Same bits either way.
+  //   multi_dot_all : slots[so .. so + m) = w . v[k], the cross-rank sum left to the caller's allreduce_slots
+  //   multi_axpy_all: w -= sum_k slot[coef + k] v[k]; norm_slot >= 0: |w|^2 and |w| there (formed by the last launch)
+  //   multi_add     : x += sum_j y[j] z[j] (y on the host), the terms in j order, each as vec_axpy adds it
+  void multi_dot_all(int n, const double *w, double *const *v, int m, int slot_out);
+  void multi_axpy_all(int n, double *w, double *const *v, int m, int coef_slot, int norm_slot);
+  void multi_add(int n, double *x, double *const *z, const double *y, int m);
+  int gs_one_launch = 1;    // NSK_IOPT_GS_ONE_LAUNCH: 0 chunks of eight, 1 (default) the whole basis, 2 at most 16 per launch
+  long gs_launches = 0;     // launches of the three calls above (test hook nsk_debug_krylov)
   void cg_update(int n, SRef a, const double *d, const double *h, double *x, double *g, int slot_out);
   void dot3(int n, const double *r, const double *u, const double *w, int slot_out);   // r.u, w.u, r.r: one pass, one all-reduce
   // the whole modified Gram-Schmidt chain of one Arnoldi step in one launch (single rank, vector short enough to sit

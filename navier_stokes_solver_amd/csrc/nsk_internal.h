@@ -25,6 +25,10 @@ enum {
   NSK_IOPT_INDEX16 = 110,       // 1 (default): the scalar stream kernels of S and M_p — SpMV, split ILU / SGS halves — read 16-bit
                                 // column offsets on top of one base per run wherever every run of the plan spans fewer than
                                 // 65 536 columns (same bits, 2 bytes per entry less); 0: int32 column ids everywhere
+  NSK_IOPT_GS_ONE_LAUNCH = 111, // 1 (default): the two fused Gram-Schmidt sweeps of an Arnoldi step (NSK_OPT_INNER_FUSED_GS 1 / 2) and
+                                // FGMRES' cycle-end update x += sum y_j z_j run ONE launch each over the whole basis where the pair
+                                // kernels apply; 0: one launch per eight basis vectors and one per term, as before;
+                                // 2: at most 16 vectors per launch (the measured alternative).  Same bits in all three
   NSK_IOPT_FUSED_MGS = 106      // 1 (default): the modified Gram-Schmidt chain of an Arnoldi step in ONE launch when the
                                 // vector fits the registers of the co-resident grid (single rank); 0: one launch per link
 };
@@ -87,14 +91,19 @@ int nsk_debug_schur_at_offset(int n_p, int n_u, const int32_t *b_rp, const int32
  *   CG_FUSED_UPDATE u, w, p, s, x, r    par sc_0 .. sc_6: vec_cg_fused_update with slots [0..7) = sc
  *   CHEBY      dinv, r, w, x            par c1, c2, set_x: vec_cheby_step
  *   DENSE_MV   M (n x n), b, x          x = M b
+ *   MULTI_DOT_ALL  w, v_0 .. v_{m-1}    Ctx::multi_dot_all: [k] = w.v_k           (m = 1 .. 32; NSK_IOPT_GS_ONE_LAUNCH chooses
+ *   MULTI_AXPY_ALL w, v_0 .. v_{m-1}    Ctx::multi_axpy_all, par and slots as MULTI_AXPY       one launch or chunks of eight)
+ *   MULTI_ADD  x, z_0 .. z_{m-1}        par y_0 .. y_{m-1}: Ctx::multi_add, x += sum_j y_j z_j (m = 1 .. 32)
  * info8: [0] reduction kernels that ran (bit 0: 8-byte-per-lane form, bit 1: pair form), [1] modified Gram-Schmidt path
  * of GS_COLUMN (4 / 8 / 12: the one-launch sweep with that many entries per thread, 0 the chain of launches, -1 not that
- * path), [2] the sweep's grid (co-resident workgroups), [3] guard words that changed (writes outside the vectors).
+ * path), [2] the sweep's grid (co-resident workgroups), [3] guard words that changed (writes outside the vectors), [4] kernel
+ * launches of MULTI_DOT_ALL / MULTI_AXPY_ALL / MULTI_ADD / the fused sweeps of GS_COLUMN.
  * Device and stream of the handle; 0 or a negative error code. */
 enum {
   NSK_DBG_KRY_DOT = 0, NSK_DBG_KRY_NORM2 = 1, NSK_DBG_KRY_AXPY_DOT = 2, NSK_DBG_KRY_AXPY_NORM2 = 3, NSK_DBG_KRY_CG_UPDATE = 4,
   NSK_DBG_KRY_MULTI_DOT = 5, NSK_DBG_KRY_MULTI_AXPY = 6, NSK_DBG_KRY_GS_COLUMN = 7, NSK_DBG_KRY_DOT3 = 8,
-  NSK_DBG_KRY_CG_SCALARS = 9, NSK_DBG_KRY_CG_FUSED_UPDATE = 10, NSK_DBG_KRY_CHEBY = 11, NSK_DBG_KRY_DENSE_MV = 12
+  NSK_DBG_KRY_CG_SCALARS = 9, NSK_DBG_KRY_CG_FUSED_UPDATE = 10, NSK_DBG_KRY_CHEBY = 11, NSK_DBG_KRY_DENSE_MV = 12,
+  NSK_DBG_KRY_MULTI_DOT_ALL = 13, NSK_DBG_KRY_MULTI_AXPY_ALL = 14, NSK_DBG_KRY_MULTI_ADD = 15
 };
 int nsk_debug_krylov(struct nsk_handle_s *h, int op, int n, int m, int offset, const double *par, int n_vec,
                      double *const *vec, const int64_t *len, double *slots64, int32_t *info8);

@@ -25,7 +25,7 @@ struct ReduceWs {
   int pairs;          // host side only: 1 = reductions read pairs of entries through 16-byte loads (NSK_OPT_BLAS1_PAIRS)
 };
 constexpr int kMaxReduceBlocks = 512;
-constexpr int kMaxReduceOut = 8;
+constexpr int kMaxReduceOut = 32;   // (the whole-basis coefficient sweep: kMgsMaxVecs outputs from one launch)
 
 // ---- CSR SpMV: y = A x | y += A x.  Columns >= n_own read x_ghost[col - n_own]. ----
 // V: the type the values are stored in — double, or float for the fp32 copies the preconditioner's inner solves read
@@ -135,6 +135,24 @@ int vec_multi_axpy(hipStream_t s, const ReduceWs &ws, int n, double *w, const Ve
 // all rows (each sweep arms the other one for its successor).  Returns the entries per thread of the kernel that ran (4, 8
 // or 12), or 0 (nothing launched) when the vector is too long for G co-resident workgroups to keep in registers.
 constexpr int kMgsThreads = 1024, kMgsMaxVecs = 32;
+// The same two sweeps over the WHOLE basis in one launch each (8 < m <= kMgsMaxVecs, pair forms only): w is read
+// once per sweep (and stored once by the update), the basis is walked in chunks of eight with w's pairs in registers, one
+// ticket chain.  Grid, trips and the order of the operations per accumulator / per entry are those of the chunked launches
+// above, so every coefficient, the norm and w come out bit for bit the same.  Return kRedPairs, or 0 (nothing launched:
+// m outside 9 .. kMgsMaxVecs, the 8-byte forms, n < 2 or a vector that is not 16-byte aligned — the caller chunks).
+struct VecPackAll {
+  const double *v[kMgsMaxVecs];
+};
+int vec_multi_dot_all(hipStream_t s, const ReduceWs &ws, int n, const double *w, const VecPackAll &P, int m, double *out);
+int vec_multi_axpy_all(hipStream_t s, const ReduceWs &ws, int n, double *w, const VecPackAll &P, int m, const double *h,
+                       double *norm_out);
+// x += sum_{j < m} y[j] z[j] in one launch (the cycle-end update of FGMRES): per entry the terms are added in j order, each
+// with vec_axpy's expression, so the bits are those of m vec_axpy launches.  1 <= m <= kMgsMaxVecs; returns 0 (nothing
+// launched) for n < 2 or a vector that is not 16-byte aligned.
+struct CoefPack {
+  double y[kMgsMaxVecs];
+};
+int vec_multi_add(hipStream_t s, int n, double *x, const VecPackAll &Z, const CoefPack &Y, int m);
 struct MgsArgs {
   int n, nv;
   const double *v[kMgsMaxVecs];

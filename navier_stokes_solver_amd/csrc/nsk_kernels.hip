@@ -906,18 +906,15 @@ __device__ __forceinline__ void reduce_finish(double (&v)[NOUT], ReduceWs ws, do
   __syncthreads();
   if (is_last) {
     __threadfence();  // agent-scope acquire
-    double acc[NOUT];
+    // (wsum is free again: thread 0 read it before the barrier above.  One output at a time, so that NOUT = 32 — the
+    // whole-basis coefficient sweep — keeps no array of sums alive across the loop: no scratch.)
 #pragma unroll
     for (int o = 0; o < NOUT; ++o) {
-      acc[o] = 0.0;
+      double a = 0.0;
       for (int i = threadIdx.x; i < (int)gridDim.x; i += RBLK)
-        acc[o] += __hip_atomic_load(&ws.partials[o * kMaxReduceBlocks + i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      acc[o] = subwave_sum<64>(acc[o]);
-    }
-    __syncthreads();
-    if (lane == 0) {
-#pragma unroll
-      for (int o = 0; o < NOUT; ++o) wsum[o][w] = acc[o];
+        a += __hip_atomic_load(&ws.partials[o * kMaxReduceBlocks + i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      a = subwave_sum<64>(a);
+      if (lane == 0) wsum[o][w] = a;
     }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -1040,6 +1037,159 @@ __global__ __launch_bounds__(RBLK) void multi_axpy2_kernel(int n, double *__rest
     if (NORM) acc[0] += wi * wi;
   }
   if (NORM) reduce_finish<1>(acc, ws, out, 1);
+}
+
+// The two sweeps over the WHOLE basis in one launch each (8 < M <= kMgsMaxVecs).  A thread keeps w's pairs of a
+// trip in registers and walks the basis in chunks of eight — the nine streams of multi_dot2_kernel<8> open at a time —
+// into acc[chunk * 8 + k].  Grid, trip pairing and the order of the four adds per accumulator are those of the chunked
+// launches, and reduce_finish folds every output's partials in its own fixed order: the coefficients are the same bits,
+// from one read of w, one ticket chain and one launch.  TWO: both trips' loads of a chunk in flight (2 x 8 16-byte loads,
+// as multi_dot2_kernel<8>); M > 16 accumulators leave room for one trip's only (1024 threads: 128 registers; the compiler
+// still runs the next chunk's loads ahead of this chunk's sums where registers are left).
+template <int M, bool TWO>
+__global__ __launch_bounds__(RBLK) void multi_dot2_all_kernel(int n, const double *__restrict__ w, VecPackAll P,
+                                                             ReduceWs ws, double *out) {
+  double acc[M];
+#pragma unroll
+  for (int k = 0; k < M; ++k) acc[k] = 0.0;
+  const long np = n >> 1, stride = (long)gridDim.x * RBLK;
+  long i = (long)blockIdx.x * RBLK + threadIdx.x;
+  for (; i + stride < np; i += 2 * stride) {
+    if (TWO) {
+      const double2 wa = reinterpret_cast<const double2 *>(w)[i], wb = reinterpret_cast<const double2 *>(w)[i + stride];
+#pragma unroll
+      for (int c = 0; c < M; c += 8) {
+        double2 va[8], vb[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k)
+          if (c + k < M) {
+            va[k] = reinterpret_cast<const double2 *>(P.v[c + k])[i];
+            vb[k] = reinterpret_cast<const double2 *>(P.v[c + k])[i + stride];
+          }
+#pragma unroll
+        for (int k = 0; k < 8; ++k)
+          if (c + k < M) {
+            acc[c + k] += wa.x * va[k].x;
+            acc[c + k] += wa.y * va[k].y;
+            acc[c + k] += wb.x * vb[k].x;
+            acc[c + k] += wb.y * vb[k].y;
+          }
+      }
+    } else {
+      // the first trip over all chunks, then the second: per accumulator still a.x, a.y, b.x, b.y
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        const long it = t ? i + stride : i;
+        const double2 wt = reinterpret_cast<const double2 *>(w)[it];
+#pragma unroll
+        for (int c = 0; c < M; c += 8) {
+          double2 vt[8];
+#pragma unroll
+          for (int k = 0; k < 8; ++k)
+            if (c + k < M) vt[k] = reinterpret_cast<const double2 *>(P.v[c + k])[it];
+#pragma unroll
+          for (int k = 0; k < 8; ++k)
+            if (c + k < M) {
+              acc[c + k] += wt.x * vt[k].x;
+              acc[c + k] += wt.y * vt[k].y;
+            }
+        }
+      }
+    }
+  }
+  // At most one single trip is left.  The scheduling barriers keep its chunks (and the entries of the odd tail) apart: left
+  // to itself the compiler runs all their loads ahead with 2 M accumulator registers live — scratch from M = 23 on — or, with
+  // the trips in one loop, issues one load at a time.
+  if (i < np) {
+    const double2 wi = reinterpret_cast<const double2 *>(w)[i];
+#pragma unroll
+    for (int c = 0; c < M; c += 8) {
+      double2 vt[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k)
+        if (c + k < M) vt[k] = reinterpret_cast<const double2 *>(P.v[c + k])[i];
+#pragma unroll
+      for (int k = 0; k < 8; ++k)
+        if (c + k < M) {
+          acc[c + k] += wi.x * vt[k].x;
+          acc[c + k] += wi.y * vt[k].y;
+        }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  }
+  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+#pragma unroll
+    for (int k = 0; k < M; ++k) {
+      acc[k] += w[n - 1] * P.v[k][n - 1];
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  }
+  reduce_finish<M>(acc, ws, out, 0);
+}
+
+// w -= sum_k h[k] v[k] over the whole basis: w's pair stays in registers across the chunks, the subtractions run in index
+// order, one store; the norm from the stored value, as multi_axpy2_kernel's last chunk forms it.
+template <int M, bool NORM>
+__global__ __launch_bounds__(RBLK) void multi_axpy2_all_kernel(int n, double *__restrict__ w, VecPackAll P,
+                                                              const double *__restrict__ h, ReduceWs ws, double *out) {
+  double acc[1] = {0.0};
+  const long np = n >> 1;
+  for (long i = (long)blockIdx.x * RBLK + threadIdx.x; i < np; i += (long)gridDim.x * RBLK) {
+    double2 wi = reinterpret_cast<double2 *>(w)[i];
+#pragma unroll
+    for (int c = 0; c < M; c += 8) {
+      double2 vt[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k)
+        if (c + k < M) vt[k] = reinterpret_cast<const double2 *>(P.v[c + k])[i];
+#pragma unroll
+      for (int k = 0; k < 8; ++k)
+        if (c + k < M) {
+          const double hk = h[c + k];
+          wi.x -= hk * vt[k].x;
+          wi.y -= hk * vt[k].y;
+        }
+    }
+    reinterpret_cast<double2 *>(w)[i] = wi;
+    if (NORM) { acc[0] += wi.x * wi.x; acc[0] += wi.y * wi.y; }
+  }
+  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+    double wi = w[n - 1];
+#pragma unroll
+    for (int k = 0; k < M; ++k) wi -= h[k] * P.v[k][n - 1];
+    w[n - 1] = wi;
+    if (NORM) acc[0] += wi * wi;
+  }
+  if (NORM) reduce_finish<1>(acc, ws, out, 1);
+}
+
+// x += sum_j y[j] z[j]: the terms in j order, each `x += y * z` as vec_axpy forms it; x read and stored once.
+template <int M>
+__global__ __launch_bounds__(BLK) void multi_add2_kernel(int n, double *__restrict__ x, VecPackAll Z, CoefPack Y) {
+  const long np = n >> 1;
+  for (long i = (long)blockIdx.x * BLK + threadIdx.x; i < np; i += (long)gridDim.x * BLK) {
+    double2 xi = reinterpret_cast<double2 *>(x)[i];
+#pragma unroll
+    for (int c = 0; c < M; c += 8) {
+      double2 zt[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k)
+        if (c + k < M) zt[k] = reinterpret_cast<const double2 *>(Z.v[c + k])[i];
+#pragma unroll
+      for (int k = 0; k < 8; ++k)
+        if (c + k < M) {
+          xi.x += Y.y[c + k] * zt[k].x;
+          xi.y += Y.y[c + k] * zt[k].y;
+        }
+    }
+    reinterpret_cast<double2 *>(x)[i] = xi;
+  }
+  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+    double xi = x[n - 1];
+#pragma unroll
+    for (int k = 0; k < M; ++k) xi += Y.y[k] * Z.v[k][n - 1];
+    x[n - 1] = xi;
+  }
 }
 
 template <int M>
@@ -2046,6 +2196,52 @@ int vec_multi_axpy(hipStream_t s, const ReduceWs &ws, int n, double *w, const Ve
 #undef NSK_MA
   return kRedScalar;
 }
+
+namespace {
+bool pack_aligned16(const double *w, const VecPackAll &P, int m) {
+  uintptr_t a = (uintptr_t)w;
+  for (int k = 0; k < m; ++k) a |= (uintptr_t)P.v[k];
+  return (a & 15u) == 0;
+}
+}  // namespace
+#define NSK_ALL_9_16(X) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16)
+#define NSK_ALL_17_32(X) X(17) X(18) X(19) X(20) X(21) X(22) X(23) X(24) X(25) X(26) X(27) X(28) X(29) X(30) X(31) X(32)
+int vec_multi_dot_all(hipStream_t s, const ReduceWs &ws, int n, const double *w, const VecPackAll &P, int m, double *out) {
+  if (m <= 8 || m > kMgsMaxVecs || !ws.pairs || n < 2 || !pack_aligned16(w, P, m)) return 0;
+  const dim3 grid(red_grid_pairs(n, 256));
+#define NSK_MD2(M) case M: hipLaunchKernelGGL((multi_dot2_all_kernel<M, true>), grid, dim3(RBLK), 0, s, n, w, P, ws, out); break;
+#define NSK_MD1(M) case M: hipLaunchKernelGGL((multi_dot2_all_kernel<M, false>), grid, dim3(RBLK), 0, s, n, w, P, ws, out); break;
+  switch (m) { NSK_ALL_9_16(NSK_MD2) NSK_ALL_17_32(NSK_MD1) default: break; }
+#undef NSK_MD2
+#undef NSK_MD1
+  return kRedPairs;
+}
+int vec_multi_axpy_all(hipStream_t s, const ReduceWs &ws, int n, double *w, const VecPackAll &P, int m, const double *h,
+                       double *norm_out) {
+  if (m <= 8 || m > kMgsMaxVecs || !ws.pairs || n < 2 || !pack_aligned16(w, P, m)) return 0;
+  const dim3 grid(red_grid_pairs(n, 256));
+#define NSK_MA(M)                                                                                                   \
+  case M:                                                                                                           \
+    if (norm_out) hipLaunchKernelGGL((multi_axpy2_all_kernel<M, true>), grid, dim3(RBLK), 0, s, n, w, P, h, ws, norm_out); \
+    else hipLaunchKernelGGL((multi_axpy2_all_kernel<M, false>), grid, dim3(RBLK), 0, s, n, w, P, h, ws, norm_out);         \
+    break;
+  switch (m) { NSK_ALL_9_16(NSK_MA) NSK_ALL_17_32(NSK_MA) default: break; }
+#undef NSK_MA
+  return kRedPairs;
+}
+int vec_multi_add(hipStream_t s, int n, double *x, const VecPackAll &Z, const CoefPack &Y, int m) {
+  if (m < 1 || m > kMgsMaxVecs || n < 2 || !pack_aligned16(x, Z, m)) return 0;
+  const dim3 grid((unsigned)std::min<long>(((long)(n >> 1) + BLK - 1) / BLK, 2048));   // one pair per thread and trip
+#define NSK_AD(M) case M: hipLaunchKernelGGL((multi_add2_kernel<M>), grid, dim3(BLK), 0, s, n, x, Z, Y); break;
+  switch (m) {
+    NSK_AD(1) NSK_AD(2) NSK_AD(3) NSK_AD(4) NSK_AD(5) NSK_AD(6) NSK_AD(7) NSK_AD(8)
+    NSK_ALL_9_16(NSK_AD) NSK_ALL_17_32(NSK_AD) default: break;
+  }
+#undef NSK_AD
+  return 1;
+}
+#undef NSK_ALL_9_16
+#undef NSK_ALL_17_32
 
 void tri_ring(hipStream_t s, const RingHalf &R, int lower, int kind, const double *own, double *dst) {
   if (R.n_pass <= 0) return;

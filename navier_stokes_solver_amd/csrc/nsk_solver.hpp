@@ -195,9 +195,10 @@ inline double lsq_householder(int rows, int cols, const double *H, int ld, doubl
 // h_i in slots HS + i (i < m), |w|^2 in HS + m and |w| in HS + m + 1.  fused_gs (NSK_OPT_INNER_FUSED_GS):
 //   0  modified Gram-Schmidt: the one-launch sweep (Ctx::mgs_sweep) when it applies, else the chain of dot / add_and_dot
 //      launches; a sweep whose wait ran out is redone link by link on the w that `redo` forms again;
-//   1  classical Gram-Schmidt in two fused sweeps: all h_i from one read of w (8 basis vectors per pass), then
-//      w -= sum h_i v_i and |w|.  Same Arnoldi relation as deal.II's modified Gram-Schmidt in exact arithmetic; ~2.5x
-//      fewer bytes and 4 launches instead of m + 1 (the passes' partial sums land in consecutive slots: one all-reduce);
+//   1  classical Gram-Schmidt in two fused sweeps: all h_i from one read of w, then w -= sum h_i v_i and |w| — one launch
+//      each over the whole basis (Ctx::multi_dot_all / multi_axpy_all; 8 basis vectors per launch where the pair kernels
+//      do not apply or NSK_IOPT_GS_ONE_LAUNCH = 0: same bits).  Same Arnoldi relation as deal.II's modified Gram-Schmidt
+//      in exact arithmetic; ~2.5x fewer bytes than the chain (the sums land in consecutive slots: one all-reduce);
 //   2  the same with |w|^2 = w.w - sum h_i^2 (w.w rides in the coefficient pass): one cross-rank reduction, not two.
 // m <= kMgsMaxVecs.  Returns the host copy of slots HS .. HS + m + 2 (the last one is the sweep's "timed out" word, and
 // only meaningful when the sweep ran).  Shared with the test hook nsk_debug_krylov.
@@ -211,11 +212,10 @@ const double *arnoldi_column(Ctx &ctx, int n, double *w, double *const *v, int m
     for (int i = 0; i <= j; ++i) vv[i] = v[i];
     vv[j + 1] = w;   // one_red: w.w as one more "coefficient" of the same pass
     const int mm = j + 1 + (one_red ? 1 : 0);
-    for (int i0 = 0; i0 < mm; i0 += 8) ctx.multi_dot(n, w, &vv[i0], std::min(8, mm - i0), HS + i0, true);
+    ctx.multi_dot_all(n, w, vv, mm, HS);
     ctx.allreduce_slots(HS, mm);
     if (one_red) gs_pythagoras(ctx.stream, ctx.slot(HS), j + 1);
-    for (int i0 = 0; i0 <= j; i0 += 8)
-      ctx.multi_axpy(n, w, &v[i0], std::min(8, j + 1 - i0), HS + i0, (!one_red && i0 + 8 > j) ? HS + j + 1 : -1);
+    ctx.multi_axpy_all(n, w, v, j + 1, HS, one_red ? -1 : HS + j + 1);
   } else if (ctx.mgs_sweep(n, w, v, j + 1, HS)) {
     // modified Gram-Schmidt, the whole chain in one launch (Ctx::mgs_sweep)
     mgs_flag = HS + j + 3;
@@ -298,7 +298,7 @@ struct SolverFGMRES : SolverBase {
           if (state != SolverControl::iterate) break;
         }
       }
-      for (int j = 0; j < ylen; ++j) vec_axpy(s(), n, sref(y[j]), z[j], x.own);
+      ctx.multi_add(n, x.own, z.data(), y, ylen);   // x += sum y_j z_j
     } while (state == SolverControl::iterate);
     iterations = accumulated;
     if (state != SolverControl::success) throw NoConvergence(1, accumulated, res);

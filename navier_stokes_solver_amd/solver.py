@@ -40,6 +40,7 @@ TIMEOP_INNER_SPMV = 50     # time_op(TIMEOP_INNER_SPMV + blk): the inner solves'
 IOPT_FUSED_MGS, IOPT_OVERLAP_HALO = 106, 107
 IOPT_TIMEOP_BETWEEN = 109  # time_op: SpMV of this block between two repetitions, outside the timed brackets (-1: back to back)
 IOPT_INDEX16 = 110         # 1 (default): 16-bit column offsets in the scalar stream kernels of S and M_p where every run qualifies; 0: int32
+IOPT_GS_ONE_LAUNCH = 111   # 1 (default): the fused Gram-Schmidt sweeps and FGMRES' cycle-end update in one launch each; 0: chunks of eight; 2: of 16
 IOPT_HOST_ANALYSIS = 108   # 1: symbolic set-up of the multicolour factors on the host (A/B, tests); default: on the device
 ORDER_NATURAL, ORDER_MULTICOLOR = 0, 1
 
