@@ -166,6 +166,13 @@ typedef struct {
   double cur_residual;         /* ... and the residual SolverControl saw last (readable from another thread) */
   int64_t overlapped_spmvs;    /* SpMVs whose interior rows ran while the halo exchange was in flight (nranks > 1) */
   int64_t ring_applies;        /* triangular applies in the caller's order that went through the LDS-ring kernel */
+  int64_t columns_skipped;     /* FGMRES basis columns that no iterate reads — the one in front of the check that ends a solve,
+                                  the last one of a full restart cycle — and that were therefore not built, outer and inner
+                                  solves together.  prec_applies, inner_*_its, tri_applies and spmv_calls count work done, so
+                                  they do not contain these columns.  Results are the bits of the reference order, with one
+                                  exception: stationary aSIMPLE, two solves with new matrix values but NO new
+                                  nsk_setup_preconditioner in between — the preconditioner application the first solve did
+                                  not need runs in front of the second solve's first one, on the new values */
 } nsk_stats;
 
 /* 128-byte RCCL unique id, produced on rank 0 and distributed by the caller (e.g. MPI_Bcast). */

@@ -185,6 +185,22 @@ struct nsk_handle_s {
   std::vector<double> history;          // residuals the outer SolverControl saw in the last solve (nsk_get_history)
   long inner_u = 0, inner_p = 0, prec_applies = 0, outer_iters = 0;
   double setup_ms = 0, solve_ms = 0;
+  // NSK_IOPT_FGMRES_SKIP_UNUSED.  The outer FGMRES does not run the preconditioner application in front of the
+  // check that ends a solve: no iterate reads its result.  Stationary aSIMPLE carries state from one application to the
+  // next (delta_p, the CG's starting guess), so that application is kept — source and destination, two pool_b vectors
+  // — and runs in front of the next one, whoever asks for it (a second solve on this set-up, nsk_precond_vmult).  It is
+  // dropped wherever delta_p starts from zero again: every set-up (the sync-free fallback's included), nsk_destroy.
+  bool skip_unused = true;
+  SolverFGMRES::Pending pending;
+  void drop_pending() {
+    if (pending.v) pool_b.put(pending.v);
+    if (pending.z) pool_b.put(pending.z);
+    pending = SolverFGMRES::Pending{};
+  }
+  // policy of the inner FGMRES on F: its preconditioner — the ILU(0) / SGS apply, or the V-cycle (Amg::apply: the first
+  // smoother step of every level and the coarse solve SET x, so x is never read before it is written) — overwrites dst
+  // from src and keeps nothing from call to call
+  int inner_skip() const { return skip_unused ? SolverFGMRES::stateless : SolverFGMRES::reference; }
 
   // ---- device assembly and Newton state (nsk_assembly_*, nsk_state_*, nsk_assemble) ----
   struct AsmData {
@@ -505,6 +521,7 @@ void H::schur_symbolic() {
 void H::setup(int type, int variant_, double alpha_) {
   if (type < 0 || type > 2) throw Error(-44, "Invalid preconditioner type. Use 0: blockDiagonal, 1: blockTriangular, 2: aSIMPLE.");
   ensure_pools();
+  drop_pending();   // a fresh preconditioner object: the application the last solve left over fed the old one's state
   ctx.ws.pairs = blas1_pairs < 0 ? (variant_ == 0) : blas1_pairs;   // NSK_OPT_BLAS1_PAIRS
   tMp.sync_free = tS.sync_free = sync_free_mode >= 1;
   tMp.want_index16 = tS.want_index16 = index16;
@@ -669,6 +686,14 @@ void H::setup(int type, int variant_, double alpha_) {
 }
 
 void H::prec_vmult(DVec &dst, const DVec &src) {
+  if (pending.v) {
+    // the application the last solve did not need: this one starts from the state it leaves (counted as work done)
+    const SolverFGMRES::Pending p = pending;
+    pending = SolverFGMRES::Pending{};
+    struct Put { VecPool &pool; double *v, *z; ~Put() { pool.put(v); pool.put(z); } } put{pool_b, p.v, p.z};
+    DVec pz = bb(p.z);
+    prec_vmult(pz, bb(p.v));
+  }
   ++prec_applies;
   Csr &F = blk[NSK_BLK_F], &B = blk[NSK_BLK_B], &Bt = blk[NSK_BLK_BT];
   DVec du = ub(dst.own), dp = pb(dst.own);
@@ -700,6 +725,7 @@ void H::prec_vmult(DVec &dst, const DVec &src) {
     try {
       SolverFGMRES sv(ctx, pool_u, cu);
       sv.fused_gs = inner_fused_gs;
+      sv.skip_unused = inner_skip();
       sv.solve(A_F, du, su, P_F);
       inner_u += cu.last_step();
       if (prec_type == 0) {
@@ -729,6 +755,7 @@ void H::prec_vmult(DVec &dst, const DVec &src) {
       SolverControl cF(100000, 1e-1 * norm_of(su.own, nu));
       SolverFGMRES sF(ctx, pool_u, cF);
       sF.fused_gs = inner_fused_gs;
+      sF.skip_unused = inner_skip();
       sF.solve(A_F, du, su, P_F);                       // F u~ = src_u
       inner_u += cF.last_step();
       halo(0, du);
@@ -783,9 +810,26 @@ int H::solve_once(int solver, double tol, int max_iter, int *iters, double *fina
   const DVec b = bb(rhs_b);
   int rc = 0;
   const int slot_mark = ctx.slot_top;
+  SolverFGMRES::Pending left_over;   // (handed over only where the solve ends at a check: never together with an older one)
+  struct Keep {
+    H &h; SolverFGMRES::Pending &p;
+    ~Keep() { if (p.v) { h.drop_pending(); h.pending = p; } }
+  } keep{*this, left_over};
   try {
     if (solver == 0) { SolverGMRES sv(ctx, pool_b, control); sv.solve(A, x, b, P); }
-    else if (solver == 1) { SolverFGMRES sv(ctx, pool_b, control); sv.fused_gs = outer_fused_gs ? 1 : 0; sv.solve(A, x, b, P); }
+    else if (solver == 1) {
+      SolverFGMRES sv(ctx, pool_b, control);
+      sv.fused_gs = outer_fused_gs ? 1 : 0;
+      if (skip_unused) {
+        // unsteady aSIMPLE is two triangular applies that overwrite dst.  The block preconditioners start their inner
+        // solves from dst and keep nothing else: the application at a cycle's end feeds the next cycle's z_j, the one at
+        // the solve's end nothing (z_j goes back to the pool).  Stationary aSIMPLE also keeps delta_p: see `pending`
+        const bool asimple = prec_type == 2;
+        sv.skip_unused = asimple && variant != 0 ? SolverFGMRES::stateless : SolverFGMRES::defer;
+        if (asimple && variant == 0) sv.pending = &left_over;
+      }
+      sv.solve(A, x, b, P);
+    }
     else { SolverBicgstab sv(ctx, pool_b, control); sv.solve(A, x, b, P); }
   } catch (NoConvergence &e) {
     rc = e.code;
@@ -1018,6 +1062,7 @@ void nsk_destroy(nsk_handle h) {
   if (!h) return;
   (void)hipSetDevice(h->ctx.device);
   (void)hipStreamSynchronize(h->ctx.stream);
+  h->drop_pending();
   h->pool_u.destroy();
   h->pool_p.destroy();
   h->pool_b.destroy();
@@ -1181,6 +1226,10 @@ int nsk_set_option(nsk_handle h, int opt, double v) {
     case NSK_IOPT_GS_ONE_LAUNCH:
       if (v != 0.0 && v != 1.0 && v != 2.0) throw Error(-61, "one-launch Gram-Schmidt sweeps: 0, 1 or 2");
       h->ctx.gs_one_launch = (int)v;
+      break;
+    case NSK_IOPT_FGMRES_SKIP_UNUSED:
+      if (v != 0.0 && v != 1.0) throw Error(-61, "NSK_IOPT_FGMRES_SKIP_UNUSED: 0 or 1");
+      h->skip_unused = v != 0.0;
       break;
     case NSK_IOPT_OVERLAP_HALO: h->overlap_halo = v != 0.0; break;
     case NSK_IOPT_TINY_BYTES: h->tF.tiny_bytes = h->tMp.tiny_bytes = h->tS.tiny_bytes = v; break;
@@ -2249,6 +2298,7 @@ int nsk_get_stats(nsk_handle h, nsk_stats *o) {
   o->cur_residual = h->progress_value;
   o->overlapped_spmvs = h->overlapped_spmvs;
   o->ring_applies = h->ctx.st.ring_applies;
+  o->columns_skipped = st.columns_skipped;
   return 0;
   NSK_CATCH(h)
 }

@@ -243,7 +243,8 @@ int abort_local_group(const void *unique_id);
 struct Stats {
   double setup_ms = 0, solve_ms = 0;
   long outer_iters = 0, inner_u_its = 0, inner_p_its = 0, prec_applies = 0, spmv_calls = 0, tri_applies = 0,
-       reductions = 0, host_syncs = 0, ring_applies = 0;
+       reductions = 0, host_syncs = 0, ring_applies = 0,
+       columns_skipped = 0;   // FGMRES basis columns no iterate reads that were not built (SolverFGMRES::skip_unused)
   double spmv_bytes = 0, tri_bytes = 0, blas1_bytes = 0;
 };
 

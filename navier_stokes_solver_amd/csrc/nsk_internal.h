@@ -29,6 +29,15 @@ enum {
                                 // FGMRES' cycle-end update x += sum y_j z_j run ONE launch each over the whole basis where the pair
                                 // kernels apply; 0: one launch per eight basis vectors and one per term, as before;
                                 // 2: at most 16 vectors per launch (the measured alternative).  Same bits in all three
+  NSK_IOPT_FGMRES_SKIP_UNUSED = 112, // 1 (default): FGMRES checks before it builds a basis column and does not build the one no
+                                // iterate reads — in front of the check that ends a solve, the last one of a full restart
+                                // cycle (SolverFGMRES::skip_unused): the inner solves on F skip it outright, the
+                                // outer solve keeps the preconditioner application a later one depends on.  Same bits;
+                                // 0: deal.II's order everywhere (A/B runs, tests).  ONE sequence is not the bits of 0:
+                                // stationary aSIMPLE, solve, nsk_update_values (or nsk_assemble) WITHOUT a new
+                                // nsk_setup_preconditioner, solve — the application the first solve left over then runs
+                                // on the new values, where the reference order ran it on the old ones (either way a
+                                // stale preconditioner; nsk_setup_preconditioner between the solves drops it)
   NSK_IOPT_FUSED_MGS = 106      // 1 (default): the modified Gram-Schmidt chain of an Arnoldi step in ONE launch when the
                                 // vector fits the registers of the co-resident grid (single rank); 0: one launch per link
 };

@@ -248,6 +248,22 @@ struct SolverFGMRES : SolverBase {
                      // vector's norm from |w|^2 - sum h_i^2 (w.w rides in the coefficient pass): ONE cross-rank
                      // reduction per iteration instead of two (NSK_OPT_INNER_FUSED_GS = 2, for several GPUs).  See
                      // arnoldi_column
+  // The check at basis index j (the least-squares problem on columns 0 .. j - 1) does not read column j, so it is made
+  // BEFORE that column is built.  Column j is never read by anything when the check ends the solve (the update takes
+  // ylen = j terms) or when j = kBasis - 1 (the cycle's update takes kBasis - 1 terms and the next cycle starts over).
+  // What happens to it then is the caller's choice (NSK_IOPT_FGMRES_SKIP_UNUSED):
+  //   reference  deal.II's order: the column is built all the same;
+  //   stateless  P overwrites dst from src and carries nothing from call to call: nothing of the column is formed;
+  //   defer      P carries state (dst as a starting guess, stationary aSIMPLE's delta_p): at a cycle's end P(z_j, v_j)
+  //              still runs, A z_j and the Gram-Schmidt chain do not; at the solve's end P does not run either — v_j as
+  //              formed and z_j as it was are handed to `pending` (their owner from then on), so that the caller can run
+  //              that application before the next one.  Without `pending` nothing of the column is formed.
+  // x, the residuals SolverControl sees and the step of the break are the same bits in all three.  Every rank sees the
+  // same all-reduced check values, so every rank skips the same collectives; the `redo` of the one-launch modified
+  // Gram-Schmidt and `cancel` only ever act on columns that are built.
+  enum { reference = 0, stateless = 1, defer = 2 };
+  int skip_unused = reference;
+  struct Pending { double *v = nullptr, *z = nullptr; } *pending = nullptr;
   void solve(const MatVec &A, DVec &x, const DVec &b, const PrecVmult &P) {
     std::vector<double *> v(kBasis, nullptr), z(kBasis, nullptr);
     double *auxp = pool.get(false);
@@ -280,23 +296,40 @@ struct SolverFGMRES : SolverBase {
       int a_slot = SB + 1;
       ylen = 0;
       for (int j = 0; j < kBasis; ++j) {
+        if (j > 0) {   // columns 0 .. j - 1 are complete: check before column j costs anything
+          res = lsq_householder(j + 1, j, H, kBasis, beta, y);
+          ylen = j;
+          state = control.check(++accumulated, res);
+        }
+        const bool ended = state != SolverControl::iterate;
+        const bool unused = ended || j == kBasis - 1;   // no iterate reads column j
+        if (unused && (skip_unused == stateless || (skip_unused == defer && ended && !pending))) {
+          ++ctx.st.columns_skipped;
+          break;
+        }
         if (!v[j]) v[j] = pool.get(false);
         if (!z[j]) z[j] = pool.get(true);  // zero on first use, stale (previous cycle) afterwards
         DVec vj = pool.view(v[j]), zj = pool.view(z[j]);
         if (a != 0.0 && std::isfinite(1.0 / a)) vec_equ(s(), n, sref(1.0, nullptr, ctx.slot(a_slot)), aux.own, vj.own);
         else vec_set(s(), n, vj.own, 0.0);
+        if (unused && skip_unused == defer) {
+          ++ctx.st.columns_skipped;
+          if (ended) {   // the caller's to run before its next application, or to drop with the state it would feed
+            pending->v = v[j];
+            pending->z = z[j];
+            v[j] = z[j] = nullptr;
+          } else {
+            P(zj, vj);   // its state feeds the next cycle
+          }
+          break;
+        }
         P(zj, vj);
         A(zj, aux.own);
         const double *h = arnoldi_column(ctx, n, aux.own, v.data(), j + 1, HS, fused_gs, [&] { A(zj, aux.own); });
         for (int i = 0; i <= j; ++i) H[i * kBasis + j] = h[i];
         H[(j + 1) * kBasis + j] = a = h[j + 2];
         a_slot = HS + j + 2;
-        if (j > 0) {
-          res = lsq_householder(j + 1, j, H, kBasis, beta, y);
-          ylen = j;
-          state = control.check(++accumulated, res);
-          if (state != SolverControl::iterate) break;
-        }
+        if (ended) break;   // reference order: the column was built for nothing
       }
       ctx.multi_add(n, x.own, z.data(), y, ylen);   // x += sum y_j z_j
     } while (state == SolverControl::iterate);

@@ -41,6 +41,7 @@ IOPT_FUSED_MGS, IOPT_OVERLAP_HALO = 106, 107
 IOPT_TIMEOP_BETWEEN = 109  # time_op: SpMV of this block between two repetitions, outside the timed brackets (-1: back to back)
 IOPT_INDEX16 = 110         # 1 (default): 16-bit column offsets in the scalar stream kernels of S and M_p where every run qualifies; 0: int32
 IOPT_GS_ONE_LAUNCH = 111   # 1 (default): the fused Gram-Schmidt sweeps and FGMRES' cycle-end update in one launch each; 0: chunks of eight; 2: of 16
+IOPT_FGMRES_SKIP_UNUSED = 112  # 1 (default): FGMRES does not build the basis column no iterate reads (same bits); 0: deal.II's order
 IOPT_HOST_ANALYSIS = 108   # 1: symbolic set-up of the multicolour factors on the host (A/B, tests); default: on the device
 ORDER_NATURAL, ORDER_MULTICOLOR = 0, 1
 
@@ -64,7 +65,7 @@ class Stats(C.Structure):
                 ("n_colors_u", C.c_int32), ("n_levels_u", C.c_int32), ("n_colors_p", C.c_int32),
                 ("n_levels_p", C.c_int32), ("nnz_s", C.c_int64), ("sync_free_fallbacks", C.c_int64),
                 ("cur_outer_iters", C.c_int64), ("cur_residual", C.c_double), ("overlapped_spmvs", C.c_int64),
-                ("ring_applies", C.c_int64)]
+                ("ring_applies", C.c_int64), ("columns_skipped", C.c_int64)]
 
 
 class NoConvergence(RuntimeError):
