@@ -135,7 +135,7 @@ enum {
                                  whose Ifpack factors are double: the outer FGMRES stays double and checks the true residual,
                                  the preconditioner alone is perturbed.  Other values: -61.  NSK_FACTOR_PRECISION=32 / 64 in
                                  the environment overrides the option for every handle (A/B runs; other values ignored) */
-  NSK_OPT_INNER_MATRIX_PRECISION = 17 /* storage precision of the matrix values the preconditioner's INNER solves multiply by:
+  NSK_OPT_INNER_MATRIX_PRECISION = 17, /* storage precision of the matrix values the preconditioner's INNER solves multiply by:
                                  the inner FGMRES on F and the inner CG on S (stationary aSIMPLE) or M_p (blockDiagonal,
                                  blockTriangular).  64 (default): double, as today.  32: they read copies of F, S and M_p
                                  rounded to float (F's 2x2 node-block copy, gathered from the double values; S and M_p
@@ -153,6 +153,23 @@ enum {
                                  so only the preconditioner is perturbed.  Other values: -61.  NSK_INNER_MATRIX_PRECISION=32
                                  / 64 in the environment overrides the option for every handle (A/B runs; other values
                                  ignored).  Independent of NSK_OPT_FACTOR_PRECISION; the velocity AMG keeps double */
+  NSK_OPT_INNER_BASIS_PRECISION = 18 /* storage precision of the Krylov basis V of the INNER FGMRES on F, which the two fused
+                                 Gram-Schmidt sweeps read once each per inner iteration.  64 (default): double, as today and
+                                 the same bits.  32: basis vector j IS the rounded vector, v_j = fl32(w / |w|) (owned entries
+                                 only), stored by the kernel that also writes it, widened, into ONE double working vector —
+                                 the preconditioner reads that, so z_j = M^-1 v_j comes from exactly the stored values and
+                                 A Z_m = V_{m+1} H holds to double rounding; V is normalised and orthogonal to ~6e-8 only.
+                                 What stays double: w, every coefficient and partial sum, the slots and the all-reduce,
+                                 the Householder least squares and the residual estimate, the Z basis and the cycle-end
+                                 update.  Takes effect at the next nsk_setup_preconditioner.  The inner solve keeps the
+                                 double basis with NSK_OPT_INNER_FUSED_GS = 0 (modified Gram-Schmidt) and with the 8-byte
+                                 reduction forms (effective NSK_OPT_BLAS1_PAIRS = 0: the unsteady variant's default) —
+                                 nsk_inner_basis_bytes reports what the inner solve reads.  The outer FGMRES basis, GMRES,
+                                 BiCGStab and CG are not touched.  A LABELLED DEVIATION from the reference, whose basis is
+                                 double: the inner solve stops at a loose tolerance and the outer FGMRES stays double and
+                                 checks the true residual, so only the preconditioner is perturbed.  Other values: -61.
+                                 NSK_INNER_BASIS_PRECISION=32 / 64 in the environment overrides the option for every handle
+                                 (A/B runs; other values ignored).  Independent of the two options above */
 };
 
 typedef struct {
@@ -259,6 +276,10 @@ int nsk_tri_get_value_bytes(nsk_handle h, int which, int32_t *bytes);
  * no inner solve on that block (S under types 0 / 1, M_p under aSIMPLE, every block under the unsteady aSIMPLE); -62 for
  * other blocks */
 int nsk_inner_value_bytes(nsk_handle h, int blk, int32_t *bytes);
+/* bytes per entry of the Krylov basis the inner FGMRES on F of the current set-up reads: 4 (NSK_OPT_INNER_BASIS_PRECISION
+ * = 32 with the fused Gram-Schmidt sweeps in their pair forms), 8 (double), 0 when this set-up runs no inner FGMRES on F
+ * (the unsteady aSIMPLE) */
+int nsk_inner_basis_bytes(nsk_handle h, int32_t *bytes);
 /* y = A x for blk = NSK_BLK_F, NSK_BLK_S or NSK_BLK_MP with exactly the values, kernel and row runs of the inner solves
  * of the current set-up (same bits as nsk_spmv(.., add = 0) when they read double).  Conventions of nsk_spmv: owned x,
  * ghosts imported, collective when nranks > 1 (the interior rows overlap the halo exchange as in the inner solves). */

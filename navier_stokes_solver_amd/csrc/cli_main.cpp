@@ -86,21 +86,26 @@ struct NewtonDriver {
   int solve_system() {
     check(h, nsk_setup_preconditioner(h, preconditioner, NSK_UNSTEADY ? NSK_VARIANT_UNSTEADY : NSK_VARIANT_STATIONARY, 0.5),
           "nsk_setup_preconditioner");
-    // NSK_FACTOR_PRECISION=32 / NSK_INNER_MATRIX_PRECISION=32 (read by the library): LABELLED DEVIATIONS from the
-    // reference.  (On lines of their own: the Newton line in front of this call is still open.)
+    // NSK_FACTOR_PRECISION=32 / NSK_INNER_MATRIX_PRECISION=32 / NSK_INNER_BASIS_PRECISION=32 (read by the library):
+    // LABELLED DEVIATIONS from the reference.  (On lines of their own: the Newton line in front of this call is still open.)
     if (!precision_reported) {
       precision_reported = true;
-      int32_t bu = 0, bp = 0, bf = 0;
+      int32_t bu = 0, bp = 0, bf = 0, bv = 0;
       check(h, nsk_tri_get_value_bytes(h, NSK_TRI_VELOCITY, &bu), "nsk_tri_get_value_bytes");
       check(h, nsk_tri_get_value_bytes(h, NSK_TRI_PRESSURE, &bp), "nsk_tri_get_value_bytes");
       check(h, nsk_inner_value_bytes(h, NSK_BLK_F, &bf), "nsk_inner_value_bytes");
+      check(h, nsk_inner_basis_bytes(h, &bv), "nsk_inner_basis_bytes");
       const char *nl = "\n";
       if (bu == 4 || bp == 4) {
         std::printf("%s[nsk] NSK_FACTOR_PRECISION=32: ILU/SGS factors stored in fp32 (deviation from the reference)\n", nl);
         nl = "";
       }
-      if (bf == 4)
+      if (bf == 4) {
         std::printf("%s[nsk] NSK_INNER_MATRIX_PRECISION=32: inner-solve matrices stored in fp32 (deviation from the reference)\n", nl);
+        nl = "";
+      }
+      if (bv == 4)
+        std::printf("%s[nsk] NSK_INNER_BASIS_PRECISION=32: inner FGMRES basis on F stored in fp32 (deviation from the reference)\n", nl);
     }
     int iters = 0;
     double res = 0.0;

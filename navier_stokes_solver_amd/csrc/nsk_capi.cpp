@@ -147,6 +147,20 @@ struct nsk_handle_s {
   int blas1_pairs = -1;     // NSK_OPT_BLAS1_PAIRS: -1 by variant (stationary on, unsteady off), 0, 1
   int factor_precision = 64;   // NSK_OPT_FACTOR_PRECISION: 64, or 32 (single-precision off-diagonal values of the split halves)
   int inner_matrix_precision = 64;   // NSK_OPT_INNER_MATRIX_PRECISION: 64, or 32 (fp32 values of F, S, M_p in the inner solves)
+  int inner_basis_precision = 64;    // NSK_OPT_INNER_BASIS_PRECISION: 64, or 32 (fp32 Krylov basis of the inner FGMRES on F)
+  // what the last set-up took of it (the option or NSK_INNER_BASIS_PRECISION), and the fp32 vectors, kept from solve to
+  // solve.  Whether a solve reads them is SolverFGMRES::reads_f32_basis: the fused sweeps in their pair forms
+  bool basis32_wanted = false;
+  BasisPool32 basis32_u;
+  int inner_basis_width() const {
+    if (!inner_solve_on(NSK_BLK_F)) return 0;
+    return basis32_wanted && ctx.f32_basis_applies(inner_fused_gs) ? 4 : 8;
+  }
+  void inner_fgmres_options(SolverFGMRES &sv) {
+    sv.fused_gs = inner_fused_gs;
+    sv.skip_unused = inner_skip();
+    sv.basis32 = basis32_wanted ? &basis32_u : nullptr;
+  }
   // pressure_mass does not depend on the state: its values only change when the caller hands over new ones, and a
   // factor of the same values under the same analysis is the same factor — it is kept (the natural-order ILU(0) of M_p
   // at 600x200 takes 0.47 s per set-up, one workgroup walking 4 001 levels: 8.5 s of config 5's first time level)
@@ -682,6 +696,15 @@ void H::setup(int type, int variant_, double alpha_) {
                            names[b] + " are finite in fp64 but outside the range of fp32");
     }
   }
+  // fp32 basis of the inner FGMRES on F; NSK_INNER_BASIS_PRECISION=32 / 64 overrides the option (A/B measurements with
+  // unchanged callers), any other value is ignored.  A set-up that does not want the vectors frees them.
+  static const int env_basis = [] {
+    const char *e = std::getenv("NSK_INNER_BASIS_PRECISION");
+    const int v = e ? std::atoi(e) : 0;
+    return v == 32 || v == 64 ? v : 0;
+  }();
+  basis32_wanted = (env_basis ? env_basis : inner_basis_precision) == 32;
+  if (inner_basis_width() != 4) basis32_u.destroy();
   setup_ms = wall_ms() - t0;
 }
 
@@ -724,8 +747,7 @@ void H::prec_vmult(DVec &dst, const DVec &src) {
     SolverControl cu(max_u, tol_u), cp(max_p, tol_p);
     try {
       SolverFGMRES sv(ctx, pool_u, cu);
-      sv.fused_gs = inner_fused_gs;
-      sv.skip_unused = inner_skip();
+      inner_fgmres_options(sv);
       sv.solve(A_F, du, su, P_F);
       inner_u += cu.last_step();
       if (prec_type == 0) {
@@ -754,8 +776,7 @@ void H::prec_vmult(DVec &dst, const DVec &src) {
     try {
       SolverControl cF(100000, 1e-1 * norm_of(su.own, nu));
       SolverFGMRES sF(ctx, pool_u, cF);
-      sF.fused_gs = inner_fused_gs;
-      sF.skip_unused = inner_skip();
+      inner_fgmres_options(sF);
       sF.solve(A_F, du, su, P_F);                       // F u~ = src_u
       inner_u += cF.last_step();
       halo(0, du);
@@ -1063,6 +1084,7 @@ void nsk_destroy(nsk_handle h) {
   (void)hipSetDevice(h->ctx.device);
   (void)hipStreamSynchronize(h->ctx.stream);
   h->drop_pending();
+  h->basis32_u.destroy();
   h->pool_u.destroy();
   h->pool_p.destroy();
   h->pool_b.destroy();
@@ -1265,6 +1287,10 @@ int nsk_set_option(nsk_handle h, int opt, double v) {
     case NSK_OPT_INNER_MATRIX_PRECISION:
       if (v != 64.0 && v != 32.0) throw Error(-61, "NSK_OPT_INNER_MATRIX_PRECISION: 64 or 32");
       h->inner_matrix_precision = (int)v;
+      break;
+    case NSK_OPT_INNER_BASIS_PRECISION:
+      if (v != 64.0 && v != 32.0) throw Error(-61, "NSK_OPT_INNER_BASIS_PRECISION: 64 or 32");
+      h->inner_basis_precision = (int)v;
       break;
     case NSK_IOPT_TRI_X_LAYOUT:
       h->x_layout_mode = v == 0.0 ? 0 : 2;
@@ -1831,8 +1857,12 @@ int nsk_debug_krylov(nsk_handle h, int op, int n, int m, int offset, const doubl
   NSK_TRY(h)
   (void)hipSetDevice(h->ctx.device);
   Ctx &c = h->ctx;
-  static const int kVecs[] = {2, 1, 3, 2, 4, -1, -1, -1, 3, 0, 6, 4, 3, -1, -1, -1};   // vectors per op (-1: m + 1)
-  if (op < NSK_DBG_KRY_DOT || op > NSK_DBG_KRY_MULTI_ADD) throw Error(-65, "nsk_debug_krylov: unknown op");
+  static const int kVecs[] = {2, 1, 3, 2, 4, -1, -1, -1, 3, 0, 6, 4, 3, -1, -1, -1, -1, -1, -1, 2, 3};   // vectors per op (-1: m + 1)
+  if (op < NSK_DBG_KRY_DOT || op > NSK_DBG_KRY_EQU_F32) throw Error(-65, "nsk_debug_krylov: unknown op");
+  // the ops on an fp32 basis: vec[k] of the basis (k >= 1; EQU_F32: vec[1]) lives on the device as floats, in an allocation
+  // of its own behind which kGuardF guard floats sit; the caller's doubles must be fp32 values, and come back widened
+  const bool f32_basis = op >= NSK_DBG_KRY_MULTI_DOT_ALL_F32 && op <= NSK_DBG_KRY_GS_COLUMN_F32;
+  auto is_float = [&](int k) { return (f32_basis && k >= 1) || (op == NSK_DBG_KRY_EQU_F32 && k == 1); };
   const bool multi = kVecs[op] < 0;
   const bool chunk = op == NSK_DBG_KRY_MULTI_DOT || op == NSK_DBG_KRY_MULTI_AXPY;   // (one launch of the chunked kernels)
   if (multi && (m < 1 || m > (chunk ? 8 : kMgsMaxVecs))) throw Error(-61, "nsk_debug_krylov: m");
@@ -1844,9 +1874,27 @@ int nsk_debug_krylov(nsk_handle h, int op, int n, int m, int offset, const doubl
   // every vector in an allocation of its own: `offset` guard words in front, kGuard behind, all holding NaN (all bits set)
   constexpr int kGuard = 4;
   hipStream_t st = h->s();
+  constexpr int kGuardF = 8;
   std::vector<DBuf<double>> buf((size_t)n_vec);
   std::vector<double *> d((size_t)n_vec);
+  std::vector<DBuf<float>> fbuf((size_t)n_vec);
+  std::vector<float *> f((size_t)n_vec, nullptr);
+  std::vector<float> hf;
   for (int k = 0; k < n_vec; ++k) {
+    if (is_float(k)) {
+      hf.resize((size_t)len[k]);
+      for (int64_t i = 0; i < len[k]; ++i) {
+        hf[(size_t)i] = (float)vec[k][i];
+        if ((double)hf[(size_t)i] != vec[k][i]) throw Error(-61, "nsk_debug_krylov: a basis entry is no fp32 value");
+      }
+      fbuf[k].alloc((size_t)len[k] + kGuardF);
+      NSK_HIP(hipMemsetAsync(fbuf[k].p, 0xFF, sizeof(float) * fbuf[k].n, st));
+      f[k] = fbuf[k].p;
+      NSK_HIP(hipMemcpyAsync(f[k], hf.data(), sizeof(float) * (size_t)len[k], hipMemcpyHostToDevice, st));
+      NSK_HIP(hipStreamSynchronize(st));   // (hf is filled again for the next vector)
+      d[k] = nullptr;
+      continue;
+    }
     const size_t tot = (size_t)len[k] + offset + kGuard;
     buf[k].alloc(tot);
     NSK_HIP(hipMemsetAsync(buf[k].p, 0xFF, sizeof(double) * tot, st));
@@ -1909,10 +1957,47 @@ int nsk_debug_krylov(nsk_handle h, int op, int n, int m, int offset, const doubl
       c.multi_axpy_all(n, d[0], d.data() + 1, m, so, par[m] != 0.0 ? so + m : -1);
       break;
     case NSK_DBG_KRY_MULTI_ADD: c.multi_add(n, d[0], d.data() + 1, par, m); break;
+    case NSK_DBG_KRY_MULTI_DOT_ALL_F32: {
+      const bool rider = par[0] != 0.0;
+      c.multi_dot_all_f32(n, d[0], f.data() + 1, m, rider, so);
+      c.allreduce_slots(so, m + (rider ? 1 : 0));
+      break;
+    }
+    case NSK_DBG_KRY_MULTI_AXPY_ALL_F32:
+      set_slots(m);
+      c.multi_axpy_all_f32(n, d[0], f.data() + 1, m, so, par[m] != 0.0 ? so + m : -1);
+      break;
+    case NSK_DBG_KRY_GS_COLUMN_F32: {
+      const int mode = (int)par[0];
+      if (mode < 1 || mode > 2) throw Error(-61, "nsk_debug_krylov: fp32 basis: Gram-Schmidt mode 1 or 2");
+      if (!c.f32_basis_applies(mode)) throw Error(-61, "nsk_debug_krylov: fp32 basis: the pair forms only");
+      arnoldi_column(c, n, d[0], (double *const *)nullptr, m, so, mode, [] {}, f.data() + 1);
+      break;
+    }
+    case NSK_DBG_KRY_EQU:
+      set_slots(1);
+      vec_equ(st, n, sref(1.0, nullptr, c.slot(so)), d[0], d[1]);
+      break;
+    case NSK_DBG_KRY_EQU_F32:
+      set_slots(1);
+      vec_equ_f32(st, n, sref(1.0, nullptr, c.slot(so)), d[0], f[1], d[2]);
+      break;
   }
   int bad_guards = 0;
   std::vector<double> all;
   for (int k = 0; k < n_vec; ++k) {
+    if (is_float(k)) {
+      hf.resize(fbuf[k].n);
+      NSK_HIP(hipMemcpyAsync(hf.data(), fbuf[k].p, sizeof(float) * hf.size(), hipMemcpyDeviceToHost, st));
+      c.sync();
+      for (int64_t i = 0; i < len[k]; ++i) vec[k][i] = (double)hf[(size_t)i];
+      for (size_t i = (size_t)len[k]; i < hf.size(); ++i) {
+        uint32_t bits;
+        memcpy(&bits, &hf[i], 4);
+        bad_guards += bits != ~0u;
+      }
+      continue;
+    }
     all.resize(buf[k].n);
     NSK_HIP(hipMemcpyAsync(all.data(), buf[k].p, sizeof(double) * all.size(), hipMemcpyDeviceToHost, st));
     c.sync();
@@ -2190,6 +2275,14 @@ int nsk_inner_value_bytes(nsk_handle h, int b, int32_t *bytes) {
   if (b != NSK_BLK_F && b != NSK_BLK_S && b != NSK_BLK_MP) throw Error(-62, "nsk_inner_value_bytes: F, S or M_p");
   if (h->prec_type < 0) throw Error(-46, "call nsk_setup_preconditioner first");
   *bytes = h->inner_solve_on(b) ? h->inner_width(h->blk[b]) : 0;
+  return 0;
+  NSK_CATCH(h)
+}
+
+int nsk_inner_basis_bytes(nsk_handle h, int32_t *bytes) {
+  NSK_TRY(h)
+  if (h->prec_type < 0) throw Error(-46, "call nsk_setup_preconditioner first");
+  *bytes = h->inner_basis_width();
   return 0;
   NSK_CATCH(h)
 }

@@ -503,6 +503,41 @@ void Ctx::multi_axpy_all(int n, double *w, double *const *v, int m, int coef_slo
     }
   }
 }
+void Ctx::multi_dot_all_f32(int n, const double *w, float *const *v, int m, bool rider, int so) {
+  const int cap = gs_one_launch == 1 ? kMgsMaxVecs : gs_one_launch == 2 ? 16 : 8;
+  bool rode = !rider;
+  for (int i0 = 0; i0 < m || !rode; i0 += cap) {
+    const int mc = std::max(0, std::min(cap, m - i0));
+    const bool ride = !rode && i0 + mc == m && mc < cap;   // w . w takes the last piece's spare output, else a launch of its own
+    VecPack32 P{};
+    for (int k = 0; k < mc; ++k) P.v[k] = v[i0 + k];
+    const int ran = vec_multi_dot_f32(stream, ws, n, w, P, mc, ride, slot(so + i0));
+    if (!ran) throw Error(-61, "fp32 basis: the coefficient sweep needs 16-byte aligned vectors");
+    red_paths |= ran;
+    rode = rode || ride;
+    st.blas1_bytes += 4.0 * n * mc + 8.0 * n;
+    ++gs_launches;
+  }
+}
+void Ctx::multi_axpy_all_f32(int n, double *w, float *const *v, int m, int coef_slot, int norm_slot) {
+  const int cap = gs_one_launch == 1 ? kMgsMaxVecs : gs_one_launch == 2 ? 16 : 8;
+  for (int i0 = 0; i0 < m; i0 += cap) {
+    const int mc = std::min(cap, m - i0);
+    const int ns = i0 + mc == m ? norm_slot : -1;   // the norm belongs to the launch that stores the final w
+    VecPack32 P{};
+    for (int k = 0; k < mc; ++k) P.v[k] = v[i0 + k];
+    const int ran = vec_multi_axpy_f32(stream, ws, n, w, P, mc, slot(coef_slot + i0), ns >= 0 ? slot(ns) : nullptr);
+    if (!ran) throw Error(-61, "fp32 basis: the update sweep needs 16-byte aligned vectors");
+    red_paths |= ran;
+    if (ns >= 0 && comm.active()) {
+      comm.allreduce_sum(slot(ns), 1, stream);
+      scalar_sqrt(stream, slot(ns), slot(ns) + 1);
+    }
+    if (ns >= 0) ++st.reductions;
+    st.blas1_bytes += 4.0 * n * mc + 16.0 * n;
+    ++gs_launches;
+  }
+}
 void Ctx::multi_add(int n, double *x, double *const *z, const double *y, int m) {
   const int cap = gs_one_launch == 1 ? kMgsMaxVecs : gs_one_launch == 2 ? 16 : 1;
   for (int i0 = 0; i0 < m; i0 += cap) {
@@ -790,6 +825,19 @@ void VecPool::destroy() {
   for (double *p : all) (void)hipFree(p);
   all.clear();
   free_list.clear();
+}
+
+float *BasisPool32::get(int j, int n_) {
+  if (n_ != n) { destroy(); n = n_; }
+  if ((size_t)j >= v.size()) v.resize((size_t)j + 1, nullptr);
+  if (!v[j]) NSK_HIP(hipMalloc((void **)&v[j], sizeof(float) * (((size_t)n + 3) / 4 * 4 + 4)));   // whole quads
+  return v[j];
+}
+
+void BasisPool32::destroy() {
+  for (float *p : v) if (p) (void)hipFree(p);
+  v.clear();
+  n = 0;
 }
 
 }  // namespace nsk

@@ -299,6 +299,12 @@ struct Ctx {
   void multi_dot_all(int n, const double *w, double *const *v, int m, int slot_out);
   void multi_axpy_all(int n, double *w, double *const *v, int m, int coef_slot, int norm_slot);
   void multi_add(int n, double *x, double *const *z, const double *y, int m);
+  // The two sweeps on a basis stored in fp32: at most 32 / 16 / 8 vectors per launch by gs_one_launch, same
+  // bits in all three.  rider: slot so + m = w . w, from the launch of the last piece where it has an output left, else
+  // from a launch of its own.  Pair forms only (f32_basis_applies); a vector that is not 16-byte aligned is an Error.
+  void multi_dot_all_f32(int n, const double *w, float *const *v, int m, bool rider, int slot_out);
+  void multi_axpy_all_f32(int n, double *w, float *const *v, int m, int coef_slot, int norm_slot);
+  bool f32_basis_applies(int fused_gs) const { return fused_gs != 0 && ws.pairs != 0; }
   int gs_one_launch = 1;    // NSK_IOPT_GS_ONE_LAUNCH: 0 chunks of eight, 1 (default) the whole basis, 2 at most 16 per launch
   long gs_launches = 0;     // launches of the three calls above (test hook nsk_debug_krylov)
   void cg_update(int n, SRef a, const double *d, const double *h, double *x, double *g, int slot_out);
@@ -336,6 +342,15 @@ struct VecPool {
   void put(double *p) { free_list.push_back(p); }
   void destroy();
   DVec view(double *p) const { return DVec{p, p + n, n}; }
+};
+
+// fp32 basis vectors of the inner FGMRES on F (NSK_OPT_INNER_BASIS_PRECISION = 32): n owned entries each — the
+// Gram-Schmidt sweeps never read ghosts — allocated on first use and kept from solve to solve.
+struct BasisPool32 {
+  int n = 0;
+  std::vector<float *> v;
+  float *get(int j, int n_);   // vector j of length n_ (a new length releases the old vectors)
+  void destroy();
 };
 
 }  // namespace nsk

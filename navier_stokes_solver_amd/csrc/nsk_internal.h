@@ -103,16 +103,27 @@ int nsk_debug_schur_at_offset(int n_p, int n_u, const int32_t *b_rp, const int32
  *   MULTI_DOT_ALL  w, v_0 .. v_{m-1}    Ctx::multi_dot_all: [k] = w.v_k           (m = 1 .. 32; NSK_IOPT_GS_ONE_LAUNCH chooses
  *   MULTI_AXPY_ALL w, v_0 .. v_{m-1}    Ctx::multi_axpy_all, par and slots as MULTI_AXPY       one launch or chunks of eight)
  *   MULTI_ADD  x, z_0 .. z_{m-1}        par y_0 .. y_{m-1}: Ctx::multi_add, x += sum_j y_j z_j (m = 1 .. 32)
+ * The kernels of the fp32 inner basis.  The basis vectors v_k are given as doubles that hold fp32 values (-61
+ * otherwise), live on the device as floats — each in an allocation of its own with guard floats behind it — and come
+ * back widened; w stays double.  offset = 1 (w not 16-byte aligned) and NSK_OPT_BLAS1_PAIRS = 0 have no fp32 form: -61.
+ *   MULTI_DOT_ALL_F32  w, v_0 .. v_{m-1}  par rider: Ctx::multi_dot_all_f32: [k] = w.v_k, rider != 0: [m] = w.w
+ *                                         (m = 1 .. 32)
+ *   MULTI_AXPY_ALL_F32 w, v_0 .. v_{m-1}  Ctx::multi_axpy_all_f32, par and slots as MULTI_AXPY (m = 1 .. 32)
+ *   GS_COLUMN_F32      w, v_0 .. v_{m-1}  par mode (1 / 2): arnoldi_column on the fp32 basis, slots as GS_COLUMN
+ *   EQU        x, y                       par a: slot [0] = a ; y = x / a, vec_equ as SolverFGMRES normalises a basis vector
+ *   EQU_F32    x, v, vw                   par a: slot [0] = a ; vec_equ_f32: v = fl32(x / a) (comes back widened), vw = v
  * info8: [0] reduction kernels that ran (bit 0: 8-byte-per-lane form, bit 1: pair form), [1] modified Gram-Schmidt path
  * of GS_COLUMN (4 / 8 / 12: the one-launch sweep with that many entries per thread, 0 the chain of launches, -1 not that
  * path), [2] the sweep's grid (co-resident workgroups), [3] guard words that changed (writes outside the vectors), [4] kernel
- * launches of MULTI_DOT_ALL / MULTI_AXPY_ALL / MULTI_ADD / the fused sweeps of GS_COLUMN.
+ * launches of MULTI_DOT_ALL / MULTI_AXPY_ALL / MULTI_ADD / the fused sweeps of GS_COLUMN / the fp32 sweeps.
  * Device and stream of the handle; 0 or a negative error code. */
 enum {
   NSK_DBG_KRY_DOT = 0, NSK_DBG_KRY_NORM2 = 1, NSK_DBG_KRY_AXPY_DOT = 2, NSK_DBG_KRY_AXPY_NORM2 = 3, NSK_DBG_KRY_CG_UPDATE = 4,
   NSK_DBG_KRY_MULTI_DOT = 5, NSK_DBG_KRY_MULTI_AXPY = 6, NSK_DBG_KRY_GS_COLUMN = 7, NSK_DBG_KRY_DOT3 = 8,
   NSK_DBG_KRY_CG_SCALARS = 9, NSK_DBG_KRY_CG_FUSED_UPDATE = 10, NSK_DBG_KRY_CHEBY = 11, NSK_DBG_KRY_DENSE_MV = 12,
-  NSK_DBG_KRY_MULTI_DOT_ALL = 13, NSK_DBG_KRY_MULTI_AXPY_ALL = 14, NSK_DBG_KRY_MULTI_ADD = 15
+  NSK_DBG_KRY_MULTI_DOT_ALL = 13, NSK_DBG_KRY_MULTI_AXPY_ALL = 14, NSK_DBG_KRY_MULTI_ADD = 15,
+  NSK_DBG_KRY_MULTI_DOT_ALL_F32 = 16, NSK_DBG_KRY_MULTI_AXPY_ALL_F32 = 17, NSK_DBG_KRY_GS_COLUMN_F32 = 18,
+  NSK_DBG_KRY_EQU = 19, NSK_DBG_KRY_EQU_F32 = 20
 };
 int nsk_debug_krylov(struct nsk_handle_s *h, int op, int n, int m, int offset, const double *par, int n_vec,
                      double *const *vec, const int64_t *len, double *slots64, int32_t *info8);

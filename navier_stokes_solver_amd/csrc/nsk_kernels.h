@@ -153,6 +153,26 @@ struct CoefPack {
   double y[kMgsMaxVecs];
 };
 int vec_multi_add(hipStream_t s, int n, double *x, const VecPackAll &Z, const CoefPack &Y, int m);
+// The two sweeps on a basis stored in fp32 (NSK_OPT_INNER_BASIS_PRECISION = 32): w, the coefficients and every
+// sum stay double, a basis value is widened as it lands.  A thread takes FOUR consecutive entries per trip — two 16-byte
+// loads of w, ONE 16-byte load of four floats per basis vector — and adds them in index order, one fused multiply-add
+// each; entries behind the last whole quad go to thread 0 of workgroup 0 after its quads.  The grid depends on n alone
+// and every accumulator / entry sees the same operations in the same order whatever m is, so the launches of a basis cut
+// into pieces give the bits of one launch.
+//   multi_dot_f32 : out[k] = w . v[k] (k < m); rider: out[m] = w . w from the w in registers.  0 <= m, 1 <= m + rider <= 32
+//   multi_axpy_f32: w -= sum_k h[k] v[k] (k in order); norm_out: norm_out[0] = w.w, norm_out[1] = sqrt.  1 <= m <= 32
+// Return kRedPairs, or 0 (nothing launched: m out of range, w or a basis vector not 16-byte aligned).
+struct VecPack32 {
+  const float *v[kMgsMaxVecs];
+};
+int vec_multi_dot_f32(hipStream_t s, const ReduceWs &ws, int n, const double *w, const VecPack32 &P, int m, int rider,
+                      double *out);
+int vec_multi_axpy_f32(hipStream_t s, const ReduceWs &ws, int n, double *w, const VecPack32 &P, int m, const double *h,
+                       double *norm_out);
+int red_grid_quads(int n);   // workgroups of the two sweeps above (the tests' error bounds count the trips from it)
+// v = fl32(a x), vw = that float widened: the fp32 basis vector and the double working vector the preconditioner reads,
+// from one pass over x.  a x is vec_equ's product, so v is the rounded (to nearest even) value of what vec_equ stores.
+void vec_equ_f32(hipStream_t s, int n, SRef a, const double *x, float *v, double *vw);
 struct MgsArgs {
   int n, nv;
   const double *v[kMgsMaxVecs];

@@ -1192,6 +1192,106 @@ __global__ __launch_bounds__(BLK) void multi_add2_kernel(int n, double *__restri
   }
 }
 
+// The coefficient sweep on an fp32 basis: out[k] = w . v[k], k < M; RIDER: out[M] = w . w.  A thread holds the
+// four entries of w of a trip (two 16-byte loads) and takes one 16-byte load of four floats per basis vector, eight
+// vectors' loads open at a time; an accumulator adds its four products in index order, one fma each, trip after trip.
+template <int M, bool RIDER>
+__global__ __launch_bounds__(RBLK) void multi_dot_f32_kernel(int n, const double *__restrict__ w, VecPack32 P,
+                                                            ReduceWs ws, double *out) {
+  constexpr int NOUT = M + (RIDER ? 1 : 0);
+  double acc[NOUT];
+#pragma unroll
+  for (int k = 0; k < NOUT; ++k) acc[k] = 0.0;
+  const long nq = n >> 2, stride = (long)gridDim.x * RBLK;
+  for (long i = (long)blockIdx.x * RBLK + threadIdx.x; i < nq; i += stride) {
+    const double2 wa = reinterpret_cast<const double2 *>(w)[2 * i], wb = reinterpret_cast<const double2 *>(w)[2 * i + 1];
+#pragma unroll
+    for (int c = 0; c < M; c += 8) {
+      float4 vt[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k)
+        if (c + k < M) vt[k] = reinterpret_cast<const float4 *>(P.v[c + k])[i];
+#pragma unroll
+      for (int k = 0; k < 8; ++k)
+        if (c + k < M) {
+          acc[c + k] = fma(wa.x, (double)vt[k].x, acc[c + k]);
+          acc[c + k] = fma(wa.y, (double)vt[k].y, acc[c + k]);
+          acc[c + k] = fma(wb.x, (double)vt[k].z, acc[c + k]);
+          acc[c + k] = fma(wb.y, (double)vt[k].w, acc[c + k]);
+        }
+      // (left to itself the compiler runs the later chunks' loads ahead over 2 NOUT live accumulator registers: scratch
+      // at NOUT = 19 and 20)
+      if (NOUT > 16) __builtin_amdgcn_sched_barrier(0);
+    }
+    if (RIDER) {
+      acc[NOUT - 1] = fma(wa.x, wa.x, acc[NOUT - 1]);
+      acc[NOUT - 1] = fma(wa.y, wa.y, acc[NOUT - 1]);
+      acc[NOUT - 1] = fma(wb.x, wb.x, acc[NOUT - 1]);
+      acc[NOUT - 1] = fma(wb.y, wb.y, acc[NOUT - 1]);
+    }
+  }
+  // the up to three entries behind the last quad (the scheduling barriers keep the vectors' loads apart: see
+  // multi_dot2_all_kernel)
+  if ((n & 3) && blockIdx.x == 0 && threadIdx.x == 0) {
+    for (int e = n & ~3; e < n; ++e) {
+      const double we = w[e];
+#pragma unroll
+      for (int k = 0; k < M; ++k) {
+        acc[k] = fma(we, (double)P.v[k][e], acc[k]);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      if (RIDER) acc[NOUT - 1] = fma(we, we, acc[NOUT - 1]);
+    }
+  }
+  reduce_finish<NOUT>(acc, ws, out, 0);
+}
+
+// The update sweep on an fp32 basis: w -= sum_k h[k] v[k], per entry in k order, one fma each; one load and one store of
+// w; the norm from the stored values, four consecutive entries per trip in index order.
+template <int M, bool NORM>
+__global__ __launch_bounds__(RBLK) void multi_axpy_f32_kernel(int n, double *__restrict__ w, VecPack32 P,
+                                                             const double *__restrict__ h, ReduceWs ws, double *out) {
+  double acc[1] = {0.0};
+  const long nq = n >> 2;
+  for (long i = (long)blockIdx.x * RBLK + threadIdx.x; i < nq; i += (long)gridDim.x * RBLK) {
+    double2 wa = reinterpret_cast<double2 *>(w)[2 * i], wb = reinterpret_cast<double2 *>(w)[2 * i + 1];
+#pragma unroll
+    for (int c = 0; c < M; c += 8) {
+      float4 vt[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k)
+        if (c + k < M) vt[k] = reinterpret_cast<const float4 *>(P.v[c + k])[i];
+#pragma unroll
+      for (int k = 0; k < 8; ++k)
+        if (c + k < M) {
+          const double mh = -h[c + k];
+          wa.x = fma(mh, (double)vt[k].x, wa.x);
+          wa.y = fma(mh, (double)vt[k].y, wa.y);
+          wb.x = fma(mh, (double)vt[k].z, wb.x);
+          wb.y = fma(mh, (double)vt[k].w, wb.y);
+        }
+    }
+    reinterpret_cast<double2 *>(w)[2 * i] = wa;
+    reinterpret_cast<double2 *>(w)[2 * i + 1] = wb;
+    if (NORM) {
+      acc[0] = fma(wa.x, wa.x, acc[0]);
+      acc[0] = fma(wa.y, wa.y, acc[0]);
+      acc[0] = fma(wb.x, wb.x, acc[0]);
+      acc[0] = fma(wb.y, wb.y, acc[0]);
+    }
+  }
+  if ((n & 3) && blockIdx.x == 0 && threadIdx.x == 0) {
+    for (int e = n & ~3; e < n; ++e) {
+      double we = w[e];
+#pragma unroll
+      for (int k = 0; k < M; ++k) we = fma(-h[k], (double)P.v[k][e], we);
+      w[e] = we;
+      if (NORM) acc[0] = fma(we, we, acc[0]);
+    }
+  }
+  if (NORM) reduce_finish<1>(acc, ws, out, 1);
+}
+
 template <int M>
 __global__ __launch_bounds__(RBLK) void multi_dot_kernel(int n, const double *__restrict__ w, VecPack P, ReduceWs ws,
                                                         double *out) {
@@ -2239,6 +2339,56 @@ int vec_multi_add(hipStream_t s, int n, double *x, const VecPackAll &Z, const Co
   }
 #undef NSK_AD
   return 1;
+}
+
+// ---- the sweeps on an fp32 basis ----
+int red_grid_quads(int n) {
+  long b = (((long)n >> 2) + RBLK * 4 - 1) / (RBLK * 4);
+  if (b < 1) b = 1;
+  if (b > 256) b = 256;
+  return (int)b;
+}
+namespace {
+bool pack_aligned16(const double *w, const VecPack32 &P, int m) {
+  uintptr_t a = (uintptr_t)w;
+  for (int k = 0; k < m; ++k) a |= (uintptr_t)P.v[k];
+  return (a & 15u) == 0;
+}
+}  // namespace
+#define NSK_ALL_1_8(X) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8)
+int vec_multi_dot_f32(hipStream_t s, const ReduceWs &ws, int n, const double *w, const VecPack32 &P, int m, int rider,
+                      double *out) {
+  const int nout = m + (rider ? 1 : 0);
+  if (m < 0 || nout < 1 || nout > kMaxReduceOut || n < 1 || !pack_aligned16(w, P, m)) return 0;
+  const dim3 grid(red_grid_quads(n));
+#define NSK_MD(M) case M: hipLaunchKernelGGL((multi_dot_f32_kernel<M, false>), grid, dim3(RBLK), 0, s, n, w, P, ws, out); break;
+#define NSK_MR(M) case M: hipLaunchKernelGGL((multi_dot_f32_kernel<M - 1, true>), grid, dim3(RBLK), 0, s, n, w, P, ws, out); break;
+  if (rider) switch (nout) { NSK_ALL_1_8(NSK_MR) NSK_ALL_9_16(NSK_MR) NSK_ALL_17_32(NSK_MR) default: break; }
+  else switch (nout) { NSK_ALL_1_8(NSK_MD) NSK_ALL_9_16(NSK_MD) NSK_ALL_17_32(NSK_MD) default: break; }
+#undef NSK_MD
+#undef NSK_MR
+  return kRedPairs;
+}
+int vec_multi_axpy_f32(hipStream_t s, const ReduceWs &ws, int n, double *w, const VecPack32 &P, int m, const double *h,
+                       double *norm_out) {
+  if (m < 1 || m > kMgsMaxVecs || n < 1 || !pack_aligned16(w, P, m)) return 0;
+  const dim3 grid(red_grid_quads(n));
+#define NSK_MA(M)                                                                                                  \
+  case M:                                                                                                          \
+    if (norm_out) hipLaunchKernelGGL((multi_axpy_f32_kernel<M, true>), grid, dim3(RBLK), 0, s, n, w, P, h, ws, norm_out); \
+    else hipLaunchKernelGGL((multi_axpy_f32_kernel<M, false>), grid, dim3(RBLK), 0, s, n, w, P, h, ws, norm_out);         \
+    break;
+  switch (m) { NSK_ALL_1_8(NSK_MA) NSK_ALL_9_16(NSK_MA) NSK_ALL_17_32(NSK_MA) default: break; }
+#undef NSK_MA
+  return kRedPairs;
+}
+#undef NSK_ALL_1_8
+void vec_equ_f32(hipStream_t s, int n, SRef a, const double *x, float *v, double *vw) {
+  NSK_EW(n, [=] __device__(int i) {
+    const float f = (float)(sval(a) * x[i]);
+    v[i] = f;
+    vw[i] = (double)f;
+  });
 }
 #undef NSK_ALL_9_16
 #undef NSK_ALL_17_32

@@ -202,11 +202,21 @@ inline double lsq_householder(int rows, int cols, const double *H, int ld, doubl
 //   2  the same with |w|^2 = w.w - sum h_i^2 (w.w rides in the coefficient pass): one cross-rank reduction, not two.
 // m <= kMgsMaxVecs.  Returns the host copy of slots HS .. HS + m + 2 (the last one is the sweep's "timed out" word, and
 // only meaningful when the sweep ran).  Shared with the test hook nsk_debug_krylov.
+// v32 (fused_gs 1 / 2 only; v is not read then): the basis is stored in fp32 — the same two sweeps through
+// Ctx::multi_dot_all_f32 / multi_axpy_all_f32; w.w of mode 2 is taken from the w the coefficient sweep holds.
 template <class Redo>
-const double *arnoldi_column(Ctx &ctx, int n, double *w, double *const *v, int m, int HS, int fused_gs, Redo &&redo) {
+const double *arnoldi_column(Ctx &ctx, int n, double *w, double *const *v, int m, int HS, int fused_gs, Redo &&redo,
+                             float *const *v32 = nullptr) {
   const int j = m - 1;
   int mgs_flag = -1;
-  if (fused_gs) {
+  if (fused_gs && v32) {
+    const bool one_red = fused_gs == 2;
+    const int mm = j + 1 + (one_red ? 1 : 0);
+    ctx.multi_dot_all_f32(n, w, v32, j + 1, one_red, HS);
+    ctx.allreduce_slots(HS, mm);
+    if (one_red) gs_pythagoras(ctx.stream, ctx.slot(HS), j + 1);
+    ctx.multi_axpy_all_f32(n, w, v32, j + 1, HS, one_red ? -1 : HS + j + 1);
+  } else if (fused_gs) {
     const bool one_red = fused_gs == 2;
     double *vv[kMgsMaxVecs + 1];
     for (int i = 0; i <= j; ++i) vv[i] = v[i];
@@ -264,20 +274,32 @@ struct SolverFGMRES : SolverBase {
   enum { reference = 0, stateless = 1, defer = 2 };
   int skip_unused = reference;
   struct Pending { double *v = nullptr, *z = nullptr; } *pending = nullptr;
+  // NSK_OPT_INNER_BASIS_PRECISION = 32 (the inner instance on F only): the basis vectors live here, in fp32.
+  // Basis vector j IS the rounded vector, v_j = fl32(aux / a): the kernel that forms it stores the float and, widened,
+  // ONE double working vector that P reads, so z_j = P v_j comes from exactly the stored values and A Z_m = V_{m+1} H
+  // holds to double rounding with the fp32 V.  aux, the coefficients, H, the least squares and Z stay double.  Applies
+  // with the fused sweeps in their pair forms (Ctx::f32_basis_applies) and a policy that hands no basis vector on
+  // (not `defer`); otherwise the basis stays double.
+  BasisPool32 *basis32 = nullptr;
+  bool reads_f32_basis() const { return basis32 && ctx.f32_basis_applies(fused_gs) && skip_unused != defer; }
   void solve(const MatVec &A, DVec &x, const DVec &b, const PrecVmult &P) {
     std::vector<double *> v(kBasis, nullptr), z(kBasis, nullptr);
     double *auxp = pool.get(false);
     DVec aux = pool.view(auxp);
+    const bool f32 = reads_f32_basis();
+    std::vector<float *> v32(f32 ? kBasis : 0, nullptr);
+    double *vwp = f32 ? pool.get(false) : nullptr;   // the working vector: the newest basis vector, widened
     const int sl = ctx.alloc_slots(kBasis + 8);
     struct Release {
-      SolverFGMRES &S; std::vector<double *> &v, &z; double *aux; int sl;
+      SolverFGMRES &S; std::vector<double *> &v, &z; double *aux, *vw; int sl;
       ~Release() {
         for (double *p : v) if (p) S.pool.put(p);
         for (double *p : z) if (p) S.pool.put(p);
         S.pool.put(aux);
+        if (vw) S.pool.put(vw);
         S.ctx.slot_top = sl;
       }
-    } rel{*this, v, z, auxp, sl};
+    } rel{*this, v, z, auxp, vwp, sl};
     const int SB = sl, HS = sl + 2;  // SB: |r|^2, |r| ; HS..: Gram-Schmidt column
     double H[(kBasis + 1) * kBasis], y[kBasis];
     int ylen = 0, accumulated = 0;
@@ -307,10 +329,18 @@ struct SolverFGMRES : SolverBase {
           ++ctx.st.columns_skipped;
           break;
         }
-        if (!v[j]) v[j] = pool.get(false);
+        if (f32) v32[j] = basis32->get(j, n);
+        else if (!v[j]) v[j] = pool.get(false);
         if (!z[j]) z[j] = pool.get(true);  // zero on first use, stale (previous cycle) afterwards
-        DVec vj = pool.view(v[j]), zj = pool.view(z[j]);
-        if (a != 0.0 && std::isfinite(1.0 / a)) vec_equ(s(), n, sref(1.0, nullptr, ctx.slot(a_slot)), aux.own, vj.own);
+        DVec vj = pool.view(f32 ? vwp : v[j]), zj = pool.view(z[j]);
+        if (f32) {
+          if (a != 0.0 && std::isfinite(1.0 / a)) {
+            vec_equ_f32(s(), n, sref(1.0, nullptr, ctx.slot(a_slot)), aux.own, v32[j], vj.own);
+          } else {
+            NSK_HIP(hipMemsetAsync(v32[j], 0, sizeof(float) * (size_t)n, s()));
+            vec_set(s(), n, vj.own, 0.0);
+          }
+        } else if (a != 0.0 && std::isfinite(1.0 / a)) vec_equ(s(), n, sref(1.0, nullptr, ctx.slot(a_slot)), aux.own, vj.own);
         else vec_set(s(), n, vj.own, 0.0);
         if (unused && skip_unused == defer) {
           ++ctx.st.columns_skipped;
@@ -325,7 +355,8 @@ struct SolverFGMRES : SolverBase {
         }
         P(zj, vj);
         A(zj, aux.own);
-        const double *h = arnoldi_column(ctx, n, aux.own, v.data(), j + 1, HS, fused_gs, [&] { A(zj, aux.own); });
+        const double *h = arnoldi_column(ctx, n, aux.own, v.data(), j + 1, HS, fused_gs, [&] { A(zj, aux.own); },
+                                         f32 ? v32.data() : nullptr);
         for (int i = 0; i <= j; ++i) H[i * kBasis + j] = h[i];
         H[(j + 1) * kBasis + j] = a = h[j + 2];
         a_slot = HS + j + 2;

@@ -22,8 +22,9 @@ RESIDUAL_TOLERANCE = 1e-9    # :654
 
 def report_factor_precision(ls):
     """After a handle's first preconditioner set-up: one line when a triangular factor holds fp32 values
-    (NSK_FACTOR_PRECISION=32), one when the inner solve on F multiplies by fp32 values (NSK_INNER_MATRIX_PRECISION=32);
-    both are read by the library and are labelled deviations from the reference (include/nsk.h)."""
+    (NSK_FACTOR_PRECISION=32), one when the inner solve on F multiplies by fp32 values (NSK_INNER_MATRIX_PRECISION=32),
+    one when its Krylov basis is stored in fp32 (NSK_INNER_BASIS_PRECISION=32); all three are read by the library and
+    are labelled deviations from the reference (include/nsk.h)."""
     if getattr(ls, "_precision_reported", False):
         return
     ls._precision_reported = True
@@ -31,6 +32,8 @@ def report_factor_precision(ls):
         print("[nsk] NSK_FACTOR_PRECISION=32: ILU/SGS factors stored in fp32 (deviation from the reference)")
     if ls.rank == 0 and ls.inner_value_bytes(0) == 4:
         print("[nsk] NSK_INNER_MATRIX_PRECISION=32: inner-solve matrices stored in fp32 (deviation from the reference)")
+    if ls.rank == 0 and ls.inner_basis_bytes() == 4:
+        print("[nsk] NSK_INNER_BASIS_PRECISION=32: inner FGMRES basis on F stored in fp32 (deviation from the reference)")
 
 
 class InletVelocity:

@@ -36,6 +36,7 @@ OPT_BLAS1_PAIRS = 15  # 16-byte loads in the reductions: 1 / 0 / -1 (default: st
 OPT_SCHUR_SIGN = 14   # +1 the reference's S (default); -1: labelled deviation, see include/nsk.h
 OPT_FACTOR_PRECISION = 16  # 64 (default) / 32: off-diagonal factor values stored in fp32 — labelled deviation, see include/nsk.h
 OPT_INNER_MATRIX_PRECISION = 17  # 64 (default) / 32: inner solves multiply by fp32 copies of F, S, M_p — labelled deviation, see include/nsk.h
+OPT_INNER_BASIS_PRECISION = 18  # 64 (default) / 32: the inner FGMRES on F keeps its Krylov basis in fp32 — labelled deviation, see include/nsk.h
 TIMEOP_INNER_SPMV = 50     # time_op(TIMEOP_INNER_SPMV + blk): the inner solves' SpMV of F, M_p or S
 IOPT_FUSED_MGS, IOPT_OVERLAP_HALO = 106, 107
 IOPT_TIMEOP_BETWEEN = 109  # time_op: SpMV of this block between two repetitions, outside the timed brackets (-1: back to back)
@@ -50,7 +51,7 @@ EXPORTS = [
     "nsk_set_support_points",
     "nsk_set_block_csr", "nsk_update_values", "nsk_set_option", "nsk_setup_preconditioner", "nsk_solve",
     "nsk_upload_system", "nsk_solve_resident", "nsk_download_solution", "nsk_spmv", "nsk_jacobian_vmult", "nsk_dot", "nsk_vec_op",
-    "nsk_tri_apply", "nsk_amg_info", "nsk_tri_get_perm", "nsk_tri_get_value_bytes", "nsk_inner_value_bytes", "nsk_inner_spmv", "nsk_precond_vmult", "nsk_block_nnz", "nsk_get_block", "nsk_get_stats",
+    "nsk_tri_apply", "nsk_amg_info", "nsk_tri_get_perm", "nsk_tri_get_value_bytes", "nsk_inner_value_bytes", "nsk_inner_basis_bytes", "nsk_inner_spmv", "nsk_precond_vmult", "nsk_block_nnz", "nsk_get_block", "nsk_get_stats",
     "nsk_reset_stats", "nsk_get_history", "nsk_cancel", "nsk_abort_group", "nsk_assembly_set_cells", "nsk_assembly_set_simplex", "nsk_assembly_set_dirichlet", "nsk_state_set", "nsk_state_get",
     "nsk_state_save", "nsk_state_save_old", "nsk_state_update", "nsk_assemble", "nsk_scale_values", "nsk_download_rhs", "nsk_time_assemble", "nsk_time_op", "nsk_profile_begin", "nsk_profile_read", "nsk_profile_end",
 ]
@@ -137,6 +138,7 @@ def lib() -> C.CDLL:
         L.nsk_tri_get_perm.argtypes = [vp, C.c_int, i32p]
         L.nsk_tri_get_value_bytes.argtypes = [vp, C.c_int, C.POINTER(C.c_int32)]
         L.nsk_inner_value_bytes.argtypes = [vp, C.c_int, C.POINTER(C.c_int32)]
+        L.nsk_inner_basis_bytes.argtypes = [vp, C.POINTER(C.c_int32)]
         L.nsk_inner_spmv.argtypes = [vp, C.c_int, f64p, f64p]
         L.nsk_precond_vmult.argtypes = [vp, f64p, f64p, f64p, f64p, C.c_int]
         L.nsk_block_nnz.restype = C.c_int64
@@ -396,6 +398,14 @@ class LinearSolver:
         OPT_INNER_MATRIX_PRECISION = 32), 8 (fp64), 0 when the set-up runs no inner solve on that block."""
         b = C.c_int32(0)
         self._ck(self.L.nsk_inner_value_bytes(self.h, blk, C.byref(b)))
+        return b.value
+
+    def inner_basis_bytes(self):
+        """Bytes per entry of the Krylov basis the inner FGMRES on F of the current set-up reads: 4 (fp32 basis,
+        OPT_INNER_BASIS_PRECISION = 32 with the fused sweeps in their pair forms), 8 (fp64), 0 when the set-up runs no
+        inner FGMRES on F."""
+        b = C.c_int32(0)
+        self._ck(self.L.nsk_inner_basis_bytes(self.h, C.byref(b)))
         return b.value
 
     def index_width(self, blk):
