@@ -153,7 +153,7 @@ enum {
                                  so only the preconditioner is perturbed.  Other values: -61.  NSK_INNER_MATRIX_PRECISION=32
                                  / 64 in the environment overrides the option for every handle (A/B runs; other values
                                  ignored).  Independent of NSK_OPT_FACTOR_PRECISION; the velocity AMG keeps double */
-  NSK_OPT_INNER_BASIS_PRECISION = 18 /* storage precision of the Krylov basis V of the INNER FGMRES on F, which the two fused
+  NSK_OPT_INNER_BASIS_PRECISION = 18, /* storage precision of the Krylov basis V of the INNER FGMRES on F, which the two fused
                                  Gram-Schmidt sweeps read once each per inner iteration.  64 (default): double, as today and
                                  the same bits.  32: basis vector j IS the rounded vector, v_j = fl32(w / |w|) (owned entries
                                  only), stored by the kernel that also writes it, widened, into ONE double working vector —
@@ -170,6 +170,26 @@ enum {
                                  checks the true residual, so only the preconditioner is perturbed.  Other values: -61.
                                  NSK_INNER_BASIS_PRECISION=32 / 64 in the environment overrides the option for every handle
                                  (A/B runs; other values ignored).  Independent of the two options above */
+  NSK_OPT_INNER_MATRIX_FREE_F = 19 /* how the INNER FGMRES on F multiplies by F on handles that assemble it themselves
+                                 (nsk_assembly_set_cells + nsk_assemble: congruent Q3/Q2 cells).  0 (default): the stored
+                                 block, as today and the same bits.  1: matrix-free — the same operator in double, applied
+                                 from what the last nsk_assemble left on the device (u and grad u at the quadrature points,
+                                 the tabulation of the cell, node -> cells, Dirichlet flags and diagonal) without reading a
+                                 stored value of F; the sums of asm_F_rows taken in another order, so results differ at
+                                 rounding level only.  All three preconditioner types, both variants wherever that solve
+                                 exists, the AMG-preconditioned solve included.  Takes effect at the next
+                                 nsk_setup_preconditioner.  What keeps the assembled double F: the outer J x and the
+                                 true-residual check, nsk_spmv, ILU(0) / SGS, the Schur SpGEMM, the AMG set-up and V-cycle.
+                                 VALID only while F holds the values of the last nsk_assemble (or nsk_time_assemble):
+                                 nsk_update_values / nsk_scale_values / nsk_set_block_csr of F, nsk_assembly_set_cells,
+                                 nsk_assembly_set_dirichlet and nsk_assembly_set_simplex end that, and the next nsk_assemble
+                                 restores it.  While it is not valid — and on P2/P1 simplex handles, handles with
+                                 nranks > 1 and NSK_OPT_SUBDOMAINS > 1, which are not covered — the stored block is
+                                 multiplied and ONE line `[nsk] warning: ...` per handle says so on stderr;
+                                 nsk_inner_matrix_free reports which of the two the next product takes.  With
+                                 NSK_OPT_INNER_MATRIX_PRECISION = 32 no fp32 copy of F is made while the product is
+                                 matrix-free.  Other values: -61.  NSK_INNER_MATRIX_FREE_F=0 / 1 in the environment
+                                 overrides the option for every handle (A/B runs; other values count as unset) */
 };
 
 typedef struct {
@@ -273,17 +293,26 @@ int nsk_tri_get_perm(nsk_handle h, int which, int32_t *perm);
 int nsk_tri_get_value_bytes(nsk_handle h, int which, int32_t *bytes);
 /* bytes per matrix value the inner solves of the current set-up read for blk (NSK_BLK_F, NSK_BLK_S or NSK_BLK_MP): 4
  * (NSK_OPT_INNER_MATRIX_PRECISION = 32 and the block's SpMV takes a stream kernel), 8 (double), 0 when this set-up runs
- * no inner solve on that block (S under types 0 / 1, M_p under aSIMPLE, every block under the unsteady aSIMPLE); -62 for
- * other blocks */
+ * no inner solve on that block (S under types 0 / 1, M_p under aSIMPLE, every block under the unsteady aSIMPLE) and for
+ * F while its inner products are matrix-free (NSK_OPT_INNER_MATRIX_FREE_F = 1 in effect: no stored value is read); -62
+ * for other blocks */
 int nsk_inner_value_bytes(nsk_handle h, int blk, int32_t *bytes);
 /* bytes per entry of the Krylov basis the inner FGMRES on F of the current set-up reads: 4 (NSK_OPT_INNER_BASIS_PRECISION
  * = 32 with the fused Gram-Schmidt sweeps in their pair forms), 8 (double), 0 when this set-up runs no inner FGMRES on F
  * (the unsteady aSIMPLE) */
 int nsk_inner_basis_bytes(nsk_handle h, int32_t *bytes);
 /* y = A x for blk = NSK_BLK_F, NSK_BLK_S or NSK_BLK_MP with exactly the values, kernel and row runs of the inner solves
- * of the current set-up (same bits as nsk_spmv(.., add = 0) when they read double).  Conventions of nsk_spmv: owned x,
+ * of the current set-up (same bits as nsk_spmv(.., add = 0) when they read double; the matrix-free product for F while
+ * NSK_OPT_INNER_MATRIX_FREE_F = 1 is in effect).  Conventions of nsk_spmv: owned x,
  * ghosts imported, collective when nranks > 1 (the interior rows overlap the halo exchange as in the inner solves). */
 int nsk_inner_spmv(nsk_handle h, int blk, const double *x_owned, double *y);
+/* *on = 1 when the next product of the inner FGMRES with F would be matrix-free (NSK_OPT_INNER_MATRIX_FREE_F = 1 taken by
+ * the last set-up, a set-up with that inner solve, a handle of the covered kind and a valid assembly), else 0 */
+int nsk_inner_matrix_free(nsk_handle h, int32_t *on);
+/* y = F x by the matrix-free kernels alone, on the state, nu, inv_dt and phase of the last nsk_assemble, whatever the
+ * option says (one rank, congruent Q3/Q2 cells; owned x).  -66 when block (0,0) does not hold the values of a device
+ * assembly (none yet, or F / the cell data were written since), -65 on simplex handles and with nranks > 1 */
+int nsk_matfree_f(nsk_handle h, const double *x_owned, double *y);
 /* preconditioner.vmult(dst, src), applied `calls` times on the same object; dst is in/out */
 int nsk_precond_vmult(nsk_handle h, const double *src_u, const double *src_p, double *dst_u, double *dst_p,
                       int calls);
@@ -368,9 +397,11 @@ int nsk_reset_stats(nsk_handle h);
 /* Device-side timing of one operation repeated `reps` times between HIP events on the
  * library's stream: op 0..5 = SpMV of block op; 10 = jacobian vmult; 20/21 = velocity /
  * pressure triangular apply; 30 = dot; 31 = axpy; 32 = fused add_and_dot; 50 + blk (50, 53, 55) = the inner
- * solves' SpMV of F, M_p, S (nsk_inner_spmv; needs a set-up).
+ * solves' SpMV of F, M_p, S (nsk_inner_spmv; needs a set-up); 56 = the matrix-free product with F (nsk_matfree_f:
+ * needs a valid assembly, not the option).
  * Returns average milliseconds per repetition and the algorithmic bytes of one repetition — for ops 50 + blk the bytes
- * the stored format really moves (fp32 values: 4 bytes each). */
+ * the stored format really moves (fp32 values: 4 bytes each), for op 56 (and op 50 while matrix-free is in effect) the
+ * bytes the two kernels move: cell data, the cells' shares written and read, node lists, x and y. */
 int nsk_time_op(nsk_handle h, int op, int reps, double *avg_ms, double *bytes);
 
 /* HIP-event sampling of operation classes INSIDE the following solves: every launch of a sampled op

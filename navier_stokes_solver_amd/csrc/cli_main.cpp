@@ -104,8 +104,15 @@ struct NewtonDriver {
         std::printf("%s[nsk] NSK_INNER_MATRIX_PRECISION=32: inner-solve matrices stored in fp32 (deviation from the reference)\n", nl);
         nl = "";
       }
-      if (bv == 4)
+      if (bv == 4) {
         std::printf("%s[nsk] NSK_INNER_BASIS_PRECISION=32: inner FGMRES basis on F stored in fp32 (deviation from the reference)\n", nl);
+        nl = "";
+      }
+      // NSK_INNER_MATRIX_FREE_F=1 (read by the library): the same operator in double, no deviation in storage
+      int32_t mf = 0;
+      check(h, nsk_inner_matrix_free(h, &mf), "nsk_inner_matrix_free");
+      if (mf == 1)
+        std::printf("%s[nsk] NSK_INNER_MATRIX_FREE_F=1: inner FGMRES multiplies by the matrix-free F of the last assembly\n", nl);
     }
     int iters = 0;
     double res = 0.0;

@@ -33,6 +33,13 @@ void asm_F_rows(hipStream_t s, const AsmMesh &M, const double *cq, double nu, do
 void asm_rhs_u(hipStream_t s, const AsmMesh &M, const double *cq, double nu, double inv_dt, double p_out, int stokes,
                const double *d0, const double *bc, double *rhs, double *x0);
 void asm_rhs_p(hipStream_t s, const AsmMesh &M, const double *cq, int stokes, double *rhs);
+// y = jacobian(0,0) x without reading the block: the operator asm_F_rows assembles, applied from cq.
+// x: owned entries and ghost tail ([n_unodes] and the rest of cell_u's numbering, two doubles per node); d0: device
+// pointer to the Dirichlet diagonal of that assembly; wk: kMatfreeCellDoubles per cell; y: owned rows.  Two launches.
+constexpr int kMatfreeCellDoubles = 32;  // the cell's share of its 16 node rows, both components
+void asm_matfree_F(hipStream_t s, const AsmMesh &M, const double *cq, double nu, double inv_dt, int stokes, const double *d0,
+                   const double *x_own, const double *x_ghost, double *wk, double *y);
+double asm_matfree_F_bytes(const AsmMesh &M, int stokes);   // bytes the two kernels move for one product
 
 // ---- P2/P1 on triangles (general cells; the reference's -M path) ----
 struct SimplexMesh {  // device pointers

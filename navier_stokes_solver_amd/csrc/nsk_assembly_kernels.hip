@@ -193,7 +193,126 @@ __global__ __launch_bounds__(BLK) void asm_rhs_p_kernel(AsmMesh M, const double 
   rhs[r] = v;
 }
 
+// ---- matrix-free y = jacobian(0,0) x from the state of the last assembly (NSK_OPT_INNER_MATRIX_FREE_F) ----
+// The rows of asm_F_rows_kernel, summed in another order: with x_c, dx x_c, dy x_c the input interpolated at the
+// quadrature point q of a cell, U and G = grad U from cq, w = JxW[q],
+//   a_c  = w (U0 dx x_c + U1 dy x_c + G[c][0] x_0 + G[c][1] x_1 + inv_dt x_c)      (Stokes phase: the inv_dt term only)
+//   bx_c = w nu dx x_c,   by_c = w nu dy x_c
+//   y[2n+c] = sum_{cells k of n, node_cells order} sum_q phi_n(q) a_c(q) + dphi_n/dx(q) bx_c(q) + dphi_n/dy(q) by_c(q)
+// Two launches, no atomics, every sum in a fixed order.  The cell kernel forms the six fluxes of its 16 points in LDS and
+// contracts them there with the cell's 16 test functions: what leaves the workgroup is the cell's share of its 16
+// node rows (32 doubles) instead of the 96 fluxes, which every one of the 16 nodes would have to read again.
+constexpr int MF_CELLS = BLK / 16;   // cells per workgroup
+constexpr int MF_FL = 98;            // flux stride per cell in LDS (96 + 2: the 4 cells of a wave start in different banks)
+__device__ __forceinline__ double2 mf_load2(const double *__restrict__ own, const double *__restrict__ ghost, int n_own,
+                                            int node) {
+  if (node < n_own) return *reinterpret_cast<const double2 *>(own + 2 * (size_t)node);
+  const double *p = ghost + 2 * (size_t)(node - n_own);   // (the ghost tail of a block vector starts at any word)
+  return make_double2(p[0], p[1]);
+}
+__global__ __launch_bounds__(BLK) void mf_cell_flux_kernel(AsmMesh M, const double *__restrict__ cq, double nu, double inv_dt,
+                                                           int stokes, const double *__restrict__ x_own,
+                                                           const double *__restrict__ x_ghost, double *__restrict__ wk) {
+  __shared__ double tN[3][256];            // phi, dphi/dx, dphi/dy as tabulated: [n][q], lanes q read consecutive words
+  __shared__ double tT[3][256];            // the same transposed to [q][n]: lanes n read consecutive words
+  __shared__ double tjxw[16];
+  __shared__ double xs[MF_CELLS][32];      // the cell's 16 node pairs of x
+  __shared__ double fl[MF_CELLS][MF_FL];   // a_0 a_1 bx_0 bx_1 by_0 by_1, 16 points each
+  {
+    const int i = threadIdx.x, nn = i >> 4, qq = i & 15;   // BLK == 256 == one table
+    const double v0 = M.tables[T_PHI + i], v1 = M.tables[T_DPX + i], v2 = M.tables[T_DPY + i];
+    tN[0][i] = v0; tN[1][i] = v1; tN[2][i] = v2;
+    tT[0][qq * 16 + nn] = v0; tT[1][qq * 16 + nn] = v1; tT[2][qq * 16 + nn] = v2;
+    if (i < 16) tjxw[i] = M.tables[T_JXW + i];
+  }
+  const int lc = threadIdx.x >> 4, l = threadIdx.x & 15;   // l: node m (gather), point q (fluxes), node n (contraction)
+  const long cell = (long)blockIdx.x * MF_CELLS + lc;
+  const bool have = cell < M.n_cells;
+  if (have) {
+    const double2 v = mf_load2(x_own, x_ghost, M.n_unodes, M.cell_u[cell * 16 + l]);
+    xs[lc][2 * l] = v.x; xs[lc][2 * l + 1] = v.y;
+  }
+  __syncthreads();
+  if (have) {
+    const int q = l;
+    double x0 = 0, x1 = 0, dx0 = 0, dx1 = 0, dy0 = 0, dy1 = 0;
+#pragma unroll
+    for (int m = 0; m < 16; ++m) {
+      const double ph = tN[0][m * 16 + q], dx = tN[1][m * 16 + q], dy = tN[2][m * 16 + q];
+      const double a = xs[lc][2 * m], b = xs[lc][2 * m + 1];
+      x0 += a * ph; x1 += b * ph;
+      dx0 += a * dx; dx1 += b * dx;
+      dy0 += a * dy; dy1 += b * dy;
+    }
+    const double w = tjxw[q];
+    double a0 = inv_dt * x0, a1 = inv_dt * x1;
+    if (!stokes) {
+      const double *c = cq + (size_t)cell * CQ + q;
+      const double u0 = c[0], u1 = c[16], g00 = c[32], g01 = c[48], g10 = c[64], g11 = c[80];
+      a0 += u0 * dx0 + u1 * dy0 + g00 * x0 + g01 * x1;
+      a1 += u0 * dx1 + u1 * dy1 + g10 * x0 + g11 * x1;
+    }
+    const double wn = w * nu;
+    double *f = fl[lc];
+    f[q] = w * a0; f[16 + q] = w * a1;
+    f[32 + q] = wn * dx0; f[48 + q] = wn * dx1;
+    f[64 + q] = wn * dy0; f[80 + q] = wn * dy1;
+  }
+  __syncthreads();
+  if (!have) return;
+  const int n = l;
+  const double *f = fl[lc];
+  double r0 = 0, r1 = 0;
+#pragma unroll
+  for (int q = 0; q < 16; ++q) {
+    const double ph = tT[0][q * 16 + n], dx = tT[1][q * 16 + n], dy = tT[2][q * 16 + n];
+    r0 += ph * f[q] + dx * f[32 + q] + dy * f[64 + q];
+    r1 += ph * f[16 + q] + dx * f[48 + q] + dy * f[80 + q];
+  }
+  *reinterpret_cast<double2 *>(wk + (size_t)cell * 32 + 2 * n) = make_double2(r0, r1);
+}
+
+// one thread per owned velocity node: its <= 4 cell shares in node_cells order; Dirichlet rows d0 * x (columns are not
+// eliminated, as in the assembled block: the other rows read x at Dirichlet nodes like anywhere else)
+__global__ __launch_bounds__(BLK) void mf_rows_kernel(AsmMesh M, const double *__restrict__ wk, const double *__restrict__ d0p,
+                                                      const double *__restrict__ x_own, double *__restrict__ y) {
+  const int r = (int)(blockIdx.x * BLK + threadIdx.x);
+  if (r >= M.n_unodes) return;
+  double2 o;
+  if (M.dirichlet[2 * r]) {
+    const double d0 = fabs(*d0p);
+    const double2 v = *reinterpret_cast<const double2 *>(x_own + 2 * (size_t)r);
+    o = make_double2(d0 * v.x, d0 * v.y);
+  } else {
+    const int4 nc = *reinterpret_cast<const int4 *>(M.node_cells + (size_t)r * 4);
+    const int cn[4] = {nc.x, nc.y, nc.z, nc.w};
+    o = make_double2(0.0, 0.0);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      if (cn[k] < 0) continue;
+      const double2 v = *reinterpret_cast<const double2 *>(wk + 2 * (size_t)cn[k]);   // (cell * 16 + n) * 2
+      o.x += v.x; o.y += v.y;
+    }
+  }
+  *reinterpret_cast<double2 *>(y + 2 * (size_t)r) = o;
+}
+
 }  // namespace
+
+void asm_matfree_F(hipStream_t s, const AsmMesh &M, const double *cq, double nu, double inv_dt, int stokes, const double *d0,
+                   const double *x_own, const double *x_ghost, double *wk, double *y) {
+  if (M.n_unodes <= 0) return;
+  if (M.n_cells > 0)
+    hipLaunchKernelGGL(mf_cell_flux_kernel, dim3((unsigned)((M.n_cells + MF_CELLS - 1) / MF_CELLS)), dim3(BLK), 0, s, M, cq, nu,
+                       inv_dt, stokes, x_own, x_ghost, wk);
+  hipLaunchKernelGGL(mf_rows_kernel, dim3((unsigned)((M.n_unodes + BLK - 1) / BLK)), dim3(BLK), 0, s, M, wk, d0, x_own, y);
+}
+double asm_matfree_F_bytes(const AsmMesh &M, int stokes) {
+  // cell kernel: cell_u (64) + cq fields 0-5 (768, not in the Stokes phase) + its share written (256); rows kernel: the
+  // shares read (256 per cell), node_cells (16), one flag, y (16); x once (16 per node) and the tables
+  return (double)M.n_cells * (64.0 + (stokes ? 0.0 : 768.0) + 256.0 + 256.0) + (double)M.n_unodes * (16.0 + 1.0 + 16.0 + 16.0) +
+         8.0 * (3 * 256 + 16);
+}
 
 void asm_cell_state(hipStream_t s, const AsmMesh &M, const double *su, const double *sp, const double *so, double *cq) {
   const long n = (long)M.n_cells * 16;

@@ -234,7 +234,42 @@ struct nsk_handle_s {
     double *old_u = nullptr;  // solution_old of the time loop (velocity part; the pressure is not used)
     bool have_old = false;
     double assemble_ms = 0;
+    // matrix-free F (NSK_OPT_INNER_MATRIX_FREE_F): F.val and cq come from ONE Q3 assembly with these
+    // parameters.  Set by nsk_assemble / nsk_time_assemble, cleared by every other writer of F or of the cell data
+    bool mf_valid = false;
+    double mf_nu = 0, mf_inv_dt = 0;
+    int mf_stokes = 0;
+    DBuf<double> d0, mf_wk;   // the Dirichlet diagonal of that assembly; the cells' shares of their node rows
   } asmd;
+  int matrix_free_f = 0;        // NSK_OPT_INNER_MATRIX_FREE_F
+  bool matfree_wanted = false;  // what the last set-up took of it (the option or NSK_INNER_MATRIX_FREE_F)
+  bool matfree_warned = false;
+  // why a handle that wants the matrix-free product multiplies by the assembled block (nullptr: it does not)
+  const char *matfree_obstacle() const {
+    if (asmd.simplex) return "the handle assembles P2/P1 triangles";
+    if (ctx.comm.nranks > 1) return "the handle is one of several ranks";
+    if (subdomains > 1) return "NSK_OPT_SUBDOMAINS > 1";
+    if (!asmd.ready || !asmd.mf_valid) return "block (0,0) does not hold the values of the last nsk_assemble";
+    return nullptr;
+  }
+  // would the next inner product with F be matrix-free?
+  bool matfree_in_effect() const { return matfree_wanted && inner_solve_on(NSK_BLK_F) && !matfree_obstacle(); }
+  // the kernels alone (nsk_matfree_f, nsk_time_op 56): one rank, Q3 cells, a valid assembly
+  void matfree_check(const char *who) const {
+    if (asmd.simplex || ctx.comm.nranks > 1) throw Error(-65, std::string(who) + ": matrix-free F covers congruent Q3/Q2 cells on one rank only");
+    if (!asmd.ready || !asmd.mf_valid)
+      throw Error(-66, std::string(who) + ": block (0,0) does not hold the values of a device assembly (call nsk_assemble)");
+  }
+  double matfree_bytes() const { return asm_matfree_F_bytes(asm_view(), asmd.mf_stokes); }
+  void matfree_apply(const DVec &x, double *y) {
+    EventSampler::Slot *smp = sampler.want(NSK_BLK_F);
+    if (smp) (void)hipEventRecord(smp->e0[smp->used], s());
+    asm_matfree_F(s(), asm_view(), asmd.cq.p, asmd.mf_nu, asmd.mf_inv_dt, asmd.mf_stokes, asmd.d0.p, x.own, x.ghost,
+                  asmd.mf_wk.p, y);
+    if (smp) (void)hipEventRecord(smp->e1[smp->used++], s());
+    ++ctx.st.spmv_calls;
+    ctx.st.spmv_bytes += matfree_bytes();
+  }
   AsmMesh asm_view() const {
     return AsmMesh{asmd.n_cells, sp[0].n / 2, sp[1].n, asmd.cell_of_dof0, asmd.cell_u.p, asmd.cell_p.p, asmd.cell_flags.p,
                    asmd.node_cells.p, asmd.node_off.p, asmd.node_self.p, asmd.pdof_cells.p, asmd.dirichlet.p,
@@ -314,6 +349,20 @@ struct nsk_handle_s {
   bool overlap_halo = true;   // NSK_IOPT_OVERLAP_HALO
   long overlapped_spmvs = 0;
   void spmv_halo(Csr &A, int space, const DVec &x, double *y) {
+    if (matfree_wanted && &A == &blk[NSK_BLK_F]) {
+      // NSK_OPT_INNER_MATRIX_FREE_F: the same operator from the cell data of the last assembly — or, announced once, the
+      // assembled block where that is not F any more (or the handle is of a kind the kernels do not cover)
+      const char *why = matfree_obstacle();
+      if (!why) {
+        halo(space, x);
+        matfree_apply(x, y);
+        return;
+      }
+      if (!matfree_warned) {
+        matfree_warned = true;
+        fprintf(stderr, "[nsk] warning: NSK_OPT_INNER_MATRIX_FREE_F = 1, but %s: the inner FGMRES multiplies by the assembled F\n", why);
+      }
+    }
     const bool blocked = A.blk_ok && use_stream && use_bsr;
     const bool streamed = !blocked && A.stream_ok && use_stream;
     const bool f32 = inner_width(A) == 4;
@@ -671,10 +720,20 @@ void H::setup(int type, int variant_, double alpha_) {
     return v == 32 || v == 64 ? v : 0;
   }();
   const bool inner32 = (env_inner ? env_inner : inner_matrix_precision) == 32;
+  // matrix-free F in the inner FGMRES; NSK_INNER_MATRIX_FREE_F=0 / 1 overrides the option (A/B runs with
+  // unchanged callers), any other value counts as unset
+  static const int env_matfree = [] {
+    const char *e = std::getenv("NSK_INNER_MATRIX_FREE_F");
+    if (e && e[0] == '0' && !e[1]) return 0;
+    if (e && e[0] == '1' && !e[1]) return 1;
+    return -1;
+  }();
+  matfree_wanted = (env_matfree >= 0 ? env_matfree : matrix_free_f) == 1;
   for (int b : {(int)NSK_BLK_F, (int)NSK_BLK_MP, (int)NSK_BLK_S}) {
     Csr &A = blk[b];
     int mode = 0;
-    if (inner32 && A.present && use_stream && inner_solve_on(b)) {
+    // (F while its products are matrix-free: no stored value is read, so no copy is made)
+    if (inner32 && A.present && use_stream && inner_solve_on(b) && !(b == NSK_BLK_F && matfree_in_effect())) {
       if (b == NSK_BLK_F) mode = use_bsr && A.blk_ok && A.blk_R == 2 && A.blk_C == 2 ? 1 : 0;
       else mode = A.stream_ok && !A.blk_ok ? 2 : 0;
     }
@@ -1177,6 +1236,7 @@ int nsk_set_block_csr(nsk_handle h, int b, int n_rows, int n_cols, const int32_t
   if (b == NSK_BLK_MP) ++h->mp_values_version;
   ++A.values_version;
   A.release_f32();   // (a new pattern: the next set-up converts again)
+  if (b == NSK_BLK_F) h->asmd.mf_valid = false;   // (values from outside: not the last assembly's any more)
   A.lpr = pick_lpr(nnz, n_rows);
   A.present = true;
   A.build_stream_plan(h->s());
@@ -1205,6 +1265,7 @@ int nsk_update_values(nsk_handle h, int b, const double *val) {
   Csr &A = h->blk[b];
   NSK_HIP(hipMemcpyAsync(A.val.p, val, sizeof(double) * (size_t)A.nnz, hipMemcpyHostToDevice, h->s()));
   if (b == NSK_BLK_MP) ++h->mp_values_version;
+  if (b == NSK_BLK_F) h->asmd.mf_valid = false;
   ++A.values_version;
   A.refresh_blocked(h->s());
   h->ctx.sync();
@@ -1291,6 +1352,10 @@ int nsk_set_option(nsk_handle h, int opt, double v) {
     case NSK_OPT_INNER_BASIS_PRECISION:
       if (v != 64.0 && v != 32.0) throw Error(-61, "NSK_OPT_INNER_BASIS_PRECISION: 64 or 32");
       h->inner_basis_precision = (int)v;
+      break;
+    case NSK_OPT_INNER_MATRIX_FREE_F:
+      if (v != 0.0 && v != 1.0) throw Error(-61, "NSK_OPT_INNER_MATRIX_FREE_F: 0 or 1");
+      h->matrix_free_f = (int)v;
       break;
     case NSK_IOPT_TRI_X_LAYOUT:
       h->x_layout_mode = v == 0.0 ? 0 : 2;
@@ -1537,6 +1602,9 @@ int nsk_assembly_set_cells(nsk_handle h, int64_t n_cells, const int32_t *cell_u_
   A.pdof_cells.upload(pdof_cells, s);
   A.tables.upload(tab, s);
   A.cq.alloc((size_t)n_cells * kAsmCellDoubles);
+  A.mf_wk.alloc((size_t)n_cells * kMatfreeCellDoubles);
+  A.d0.alloc(1);
+  A.mf_valid = false;   // (cq of another mesh)
   if (!A.sol_u) {
     A.sol_u = h->pool_u.get(true); A.eval_u = h->pool_u.get(true); A.old_u = h->pool_u.get(true);
     A.sol_p = h->pool_p.get(true); A.eval_p = h->pool_p.get(true);
@@ -1555,6 +1623,7 @@ int nsk_assembly_set_dirichlet(nsk_handle h, const uint8_t *dirichlet_u, const d
   for (int r = 0; r + 1 < h->n_u(); r += 2)
     if ((dirichlet_u[r] != 0) != (dirichlet_u[r + 1] != 0)) throw Error(-65, "assembly: Dirichlet flags must cover both components of a node");
   h->asmd.dirichlet.upload(dirichlet_u, (size_t)h->n_u(), h->s());
+  h->asmd.mf_valid = false;   // (rows of F were cleared under other flags)
   h->asmd.have_bc = bc_u != nullptr;
   if (bc_u) h->asmd.bc.upload(bc_u, (size_t)h->n_u(), h->s());
   h->ctx.sync();
@@ -1687,6 +1756,7 @@ int nsk_assembly_set_simplex(nsk_handle h, int64_t n_cells, const int32_t *cell_
     A.sol_p = h->pool_p.get(true); A.eval_p = h->pool_p.get(true);
   }
   h->ctx.sync();
+  A.mf_valid = false;
   A.simplex = true;
   A.ready = true;
   return 0;
@@ -1724,12 +1794,16 @@ int nsk_assemble(nsk_handle h, int stokes, double nu, double inv_dt, double p_ou
     return 0;
   }
   const AsmMesh M = h->asm_view();
+  A.mf_valid = false;
   asm_cell_state(s, M, A.sol_u, A.sol_p, A.have_old ? A.old_u : nullptr, A.cq.p);
   stokes = stokes != 0;
   asm_d0(s, M, A.cq.p, nu, inv_dt, stokes, h->ctx.slot(sl));
   h->ctx.comm.allreduce_sum(h->ctx.slot(sl), 1, s);   // the rank owning global DoF 0 wrote it, the others 0
+  vec_copy(s, 1, h->ctx.slot(sl), A.d0.p);            // (the slot is handed out again; the matrix-free F reads this copy)
   asm_F_rows(s, M, A.cq.p, nu, inv_dt, stokes, h->ctx.slot(sl), F.rowptr.p, F.val.p);
   ++F.values_version;
+  A.mf_valid = true;   // F.val and cq: one state, these parameters
+  A.mf_nu = nu; A.mf_inv_dt = inv_dt; A.mf_stokes = stokes;
   F.refresh_blocked(s);
   // the time term of the residual needs solution_old (nsk_state_save_old); without one it is left out
   asm_rhs_u(s, M, A.cq.p, nu, A.have_old ? inv_dt : 0.0, p_out, stokes, h->ctx.slot(sl),
@@ -1750,6 +1824,7 @@ int nsk_scale_values(nsk_handle h, int blk, double factor) {
   Csr &A = h->blk[blk];
   vec_scale(h->s(), (int)A.nnz, sref(factor), A.val.p);
   if (blk == NSK_BLK_MP) ++h->mp_values_version;
+  if (blk == NSK_BLK_F) h->asmd.mf_valid = false;
   ++A.values_version;
   A.refresh_blocked(h->s());
   return 0;
@@ -1782,8 +1857,11 @@ int nsk_time_assemble(nsk_handle h, double nu, double inv_dt, int reps, double *
   auto once = [&]() {
     asm_cell_state(s, M, A.sol_u, A.sol_p, A.have_old ? A.old_u : nullptr, A.cq.p);
     asm_d0(s, M, A.cq.p, nu, inv_dt, 0, h->ctx.slot(sl));
+    vec_copy(s, 1, h->ctx.slot(sl), A.d0.p);
     asm_F_rows(s, M, A.cq.p, nu, inv_dt, 0, h->ctx.slot(sl), F.rowptr.p, F.val.p);
     ++F.values_version;
+    A.mf_valid = true;
+    A.mf_nu = nu; A.mf_inv_dt = inv_dt; A.mf_stokes = 0;
     F.refresh_blocked(s);
     asm_rhs_u(s, M, A.cq.p, nu, A.have_old ? inv_dt : 0.0, 1.0, 0, h->ctx.slot(sl), nullptr, h->rhs_b, h->x_b);
     asm_rhs_p(s, M, A.cq.p, 0, h->rhs_b + h->n_u());
@@ -2274,7 +2352,7 @@ int nsk_inner_value_bytes(nsk_handle h, int b, int32_t *bytes) {
   NSK_TRY(h)
   if (b != NSK_BLK_F && b != NSK_BLK_S && b != NSK_BLK_MP) throw Error(-62, "nsk_inner_value_bytes: F, S or M_p");
   if (h->prec_type < 0) throw Error(-46, "call nsk_setup_preconditioner first");
-  *bytes = h->inner_solve_on(b) ? h->inner_width(h->blk[b]) : 0;
+  *bytes = !h->inner_solve_on(b) || (b == NSK_BLK_F && h->matfree_in_effect()) ? 0 : h->inner_width(h->blk[b]);
   return 0;
   NSK_CATCH(h)
 }
@@ -2304,6 +2382,28 @@ int nsk_inner_spmv(nsk_handle h, int b, const double *x, double *y) {
   pool.put(yv);
   return 0;
   NSK_CATCH_ABORT(h)
+}
+
+int nsk_inner_matrix_free(nsk_handle h, int32_t *on) {
+  NSK_TRY(h)
+  *on = h->matfree_in_effect() ? 1 : 0;
+  return 0;
+  NSK_CATCH(h)
+}
+
+int nsk_matfree_f(nsk_handle h, const double *x, double *y) {
+  NSK_TRY(h)
+  (void)hipSetDevice(h->ctx.device);
+  h->matfree_check("nsk_matfree_f");
+  double *xv = h->pool_u.get(true), *yv = h->pool_u.get(true);
+  NSK_HIP(hipMemcpyAsync(xv, x, sizeof(double) * (size_t)h->pool_u.n, hipMemcpyHostToDevice, h->s()));
+  h->matfree_apply(h->pool_u.view(xv), yv);
+  NSK_HIP(hipMemcpyAsync(y, yv, sizeof(double) * (size_t)h->pool_u.n, hipMemcpyDeviceToHost, h->s()));
+  h->ctx.sync();
+  h->pool_u.put(xv);
+  h->pool_u.put(yv);
+  return 0;
+  NSK_CATCH(h)
 }
 
 int nsk_tri_get_perm(nsk_handle h, int which, int32_t *perm) {
@@ -2458,7 +2558,8 @@ int nsk_profile_read(nsk_handle h, int op, double *avg_ms, int *n_samples, doubl
   }
   if (bytes_format) {   // what the storage format in use really holds (<= the CSR figure for the node-block copies)
     // (F, S, M_p with fp32 copies for the inner solves: the fp32 format — see nsk.h, NSK_OPT_INNER_MATRIX_PRECISION)
-    if (op >= 0 && op <= NSK_BLK_S) *bytes_format = h->blk[op].format_bytes(h->use_stream && h->use_bsr, h->inner_width(h->blk[op]), h->spmv_on_index16(h->blk[op]));
+    if (op == NSK_BLK_F && h->matfree_in_effect()) *bytes_format = h->matfree_bytes();
+    else if (op >= 0 && op <= NSK_BLK_S) *bytes_format = h->blk[op].format_bytes(h->use_stream && h->use_bsr, h->inner_width(h->blk[op]), h->spmv_on_index16(h->blk[op]));
     else if (op == 20) *bytes_format = h->tF.format_bytes();
     else if (op == 21 && h->tP) *bytes_format = h->tP->format_bytes();
     else *bytes_format = 0.0;
@@ -2513,9 +2614,19 @@ int nsk_time_op(nsk_handle h, int op, int reps, double *avg_ms, double *bytes) {
     double *xs = pc.get(true);
     vec_set(h->s(), pc.n, xs, 1.0);
     const DVec xv = pc.view(xs);
-    by = A.format_bytes(h->use_stream && h->use_bsr, h->inner_width(A), h->spmv_on_index16(A));
+    by = b == NSK_BLK_F && h->matfree_in_effect() ? h->matfree_bytes()
+                                                  : A.format_bytes(h->use_stream && h->use_bsr, h->inner_width(A), h->spmv_on_index16(A));
     f = [=, &A]() { h->spmv_halo(A, cs, xv, yb); };
     pc.put(xs);   // stays valid until the pool hands it out again (not during this call)
+  } else if (op == 56) {
+    // the matrix-free product with F on the state of the last assembly, whatever the option says (nsk_matfree_f)
+    h->matfree_check("nsk_time_op");
+    double *xs = h->pool_u.get(true);
+    vec_set(h->s(), h->pool_u.n, xs, 1.0);
+    const DVec xv = h->pool_u.view(xs);
+    by = h->matfree_bytes();
+    f = [=]() { h->matfree_apply(xv, yb); };
+    h->pool_u.put(xs);   // stays valid until the pool hands it out again (not during this call)
   } else if (op == 10) {
     Csr &F = h->blk[NSK_BLK_F], &Bt = h->blk[NSK_BLK_BT], &B = h->blk[NSK_BLK_B];
     by = (double)F.spmv_bytes() + (double)Bt.spmv_bytes() + (double)B.spmv_bytes();

@@ -24,7 +24,8 @@ def report_factor_precision(ls):
     """After a handle's first preconditioner set-up: one line when a triangular factor holds fp32 values
     (NSK_FACTOR_PRECISION=32), one when the inner solve on F multiplies by fp32 values (NSK_INNER_MATRIX_PRECISION=32),
     one when its Krylov basis is stored in fp32 (NSK_INNER_BASIS_PRECISION=32); all three are read by the library and
-    are labelled deviations from the reference (include/nsk.h)."""
+    are labelled deviations from the reference (include/nsk.h).  One more when that inner solve multiplies by the
+    matrix-free F (NSK_INNER_MATRIX_FREE_F=1: the same operator in double, no deviation in storage)."""
     if getattr(ls, "_precision_reported", False):
         return
     ls._precision_reported = True
@@ -34,6 +35,8 @@ def report_factor_precision(ls):
         print("[nsk] NSK_INNER_MATRIX_PRECISION=32: inner-solve matrices stored in fp32 (deviation from the reference)")
     if ls.rank == 0 and ls.inner_basis_bytes() == 4:
         print("[nsk] NSK_INNER_BASIS_PRECISION=32: inner FGMRES basis on F stored in fp32 (deviation from the reference)")
+    if ls.rank == 0 and ls.inner_matrix_free() == 1:
+        print("[nsk] NSK_INNER_MATRIX_FREE_F=1: inner FGMRES multiplies by the matrix-free F of the last assembly")
 
 
 class InletVelocity:

@@ -1,0 +1,98 @@
+"""NSK_OPT_INNER_MATRIX_FREE_F in the public header, the Python wrapper, the library's source, the drivers and the documents
+(no GPU)."""
+import os
+import re
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LINE = "[nsk] NSK_INNER_MATRIX_FREE_F=1: inner FGMRES multiplies by the matrix-free F of the last assembly"
+
+
+def _read(*parts):
+    with open(os.path.join(ROOT, *parts)) as f:
+        return f.read()
+
+
+def test_option_value_matches_the_header_and_is_documented():
+    from navier_stokes_solver_amd import solver as S
+    h = _read("include", "nsk.h")
+    m = re.search(r"NSK_OPT_INNER_MATRIX_FREE_F\s*=\s*(\d+)\s*,?\s*/\*(.*?)\*/", h, re.S)
+    assert m, "NSK_OPT_INNER_MATRIX_FREE_F is not declared with a comment in include/nsk.h"
+    assert S.OPT_INNER_MATRIX_FREE_F == int(m.group(1)) == 19
+    doc = " ".join(m.group(2).split())
+    for what in ("0 (default)", "the same bits", "matrix-free", "inner FGMRES on F", "nsk_setup_preconditioner", "-61",
+                 "NSK_INNER_MATRIX_FREE_F=0 / 1", "nsk_inner_matrix_free", "nsk_update_values", "nsk_scale_values",
+                 "nsk_set_block_csr", "nsk_assembly_set_cells", "nsk_assembly_set_dirichlet", "nsk_assembly_set_simplex",
+                 "nranks > 1", "NSK_OPT_SUBDOMAINS > 1", "[nsk] warning:", "NSK_OPT_INNER_MATRIX_PRECISION = 32"):
+        assert what.lower() in doc.lower(), what
+    ids = re.findall(r"^\s*NSK_OPT_\w+\s*=\s*(\d+)", h, re.M)
+    assert len(ids) == len(set(ids)) and "19" in ids
+    # nsk_inner_value_bytes: 0 while matrix-free is in effect; nsk_time_op: op 56
+    assert re.search(r"F while its inner products are matrix-free.*?int nsk_inner_value_bytes", h, re.S)
+    assert re.search(r"56 = the matrix-free product with F", h)
+
+
+def test_the_entry_points_are_declared_listed_and_wrapped():
+    from navier_stokes_solver_amd import solver as S
+    h = _read("include", "nsk.h")
+    assert re.search(r"int\s+nsk_inner_matrix_free\s*\(\s*nsk_handle\s+h\s*,\s*int32_t\s*\*\s*on\s*\)", h)
+    assert re.search(r"int\s+nsk_matfree_f\s*\(\s*nsk_handle\s+h\s*,\s*const\s+double\s*\*\s*x_owned\s*,\s*double\s*\*\s*y\s*\)", h)
+    for name in ("nsk_inner_matrix_free", "nsk_matfree_f"):
+        assert name in S.EXPORTS, name
+    assert callable(getattr(S.LinearSolver, "inner_matrix_free")) and callable(getattr(S.LinearSolver, "matfree_f"))
+    assert S.TIMEOP_MATFREE_F == 56
+
+
+def test_the_environment_override_is_read_once_and_takes_0_or_1_only():
+    """A function-local static (read once per process), as the three precision switches are read; exactly "0" or "1",
+    anything else counts as unset."""
+    src = _read("navier_stokes_solver_amd", "csrc", "nsk_capi.cpp")
+    m = re.search(r"static const int (\w+) = \[\] \{\s*const char \*e = std::getenv\(\"NSK_INNER_MATRIX_FREE_F\"\);"
+                  r"\s*if \(e && e\[0\] == '0' && !e\[1\]\) return 0;\s*if \(e && e\[0\] == '1' && !e\[1\]\) return 1;"
+                  r"\s*return -1;\s*\}\(\);", src)
+    assert m, "NSK_INNER_MATRIX_FREE_F is not parsed by a function-local static that takes 0 or 1 only"
+    name = m.group(1)
+    assert re.search(rf"matfree_wanted = \({name} >= 0 \? {name} : matrix_free_f\) == 1;", src)
+    assert src.count('getenv("NSK_INNER_MATRIX_FREE_F")') == 1
+    assert re.search(r"case NSK_OPT_INNER_MATRIX_FREE_F:\s*if \(v != 0\.0 && v != 1\.0\) throw Error\(-61,", src)
+    # the fallback announces itself, once per handle
+    assert src.count("[nsk] warning: NSK_OPT_INNER_MATRIX_FREE_F = 1") == 1 and "matfree_warned = true;" in src
+
+
+def test_every_writer_of_f_or_the_cell_data_clears_the_flag():
+    src = _read("navier_stokes_solver_amd", "csrc", "nsk_capi.cpp")
+
+    def body(name):
+        m = re.search(rf"^int {name}\(.*?^}}", src, re.M | re.S)
+        assert m, name
+        return m.group(0)
+
+    for name in ("nsk_set_block_csr", "nsk_update_values", "nsk_scale_values", "nsk_assembly_set_cells",
+                 "nsk_assembly_set_dirichlet", "nsk_assembly_set_simplex"):
+        assert "mf_valid = false" in body(name), name
+    for name in ("nsk_assemble", "nsk_time_assemble"):
+        assert "mf_valid = true" in body(name), name
+    kern = _read("navier_stokes_solver_amd", "csrc", "nsk_assembly_kernels.hip")
+    assert "mf_cell_flux_kernel" in kern and "mf_rows_kernel" in kern and "atomic" not in kern.lower().split("mf_cell_flux_kernel", 1)[1].split("asm_cell_state(")[0].replace("no atomics", "")
+
+
+def test_both_drivers_print_the_line():
+    assert LINE in _read("navier_stokes_solver_amd", "csrc", "cli_main.cpp")
+    assert LINE in _read("navier_stokes_solver_amd", "newton.py")
+
+
+def test_the_documents_name_the_option_the_switch_the_getter_and_the_resource_file():
+    readme, design = _read("README.md"), _read("DESIGN.md")
+    assert "NSK_INNER_MATRIX_FREE_F=0|1" in readme and "NSK_OPT_INNER_MATRIX_FREE_F" in readme
+    heads = re.findall(r"^## (\w+)\.", design, re.M)
+    assert heads.index("5m") == heads.index("5l") + 1 and heads[heads.index("5m") + 1] == "5a"
+    m = re.search(r"^## 5m\. .*$", design, re.M)
+    assert "NSK_OPT_INNER_MATRIX_FREE_F" in m.group(0)
+    sec = design[m.start():]
+    sec = sec[:re.search(r"^## (?!5m)", sec[4:], re.M).start() + 4]
+    for what in ("nsk_inner_matrix_free", "nsk_matfree_f", "NSK_INNER_MATRIX_FREE_F", "stays assembled", "mf_cell_flux_kernel",
+                 "mf_rows_kernel", "profiles/matrix_free_f_kernel_resource_usage.txt", "scripts/time_matrix_free_f.py"):
+        assert what in sec, what
+    res = _read("profiles", "matrix_free_f_kernel_resource_usage.txt")
+    assert "mf_cell_flux_kernel" in res and "mf_rows_kernel" in res
+    assert re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", res) == ["0", "0"]
+    assert "matrix_free_f_" in _read("profiles", "README.md") and "time_matrix_free_f.py" in _read("scripts", "README.md")
