@@ -319,6 +319,10 @@ int nsk_precond_vmult(nsk_handle h, const double *src_u, const double *src_p, do
 /* size and content of a block held by the library (used for NSK_BLK_S) */
 int64_t nsk_block_nnz(nsk_handle h, int blk);
 int nsk_get_block(nsk_handle h, int blk, int32_t *rowptr, int32_t *col, double *val);
+/* Which SpMV kernel a block with these flags runs under these options: the library's one rule on bare values (no handle,
+ * no device; described with the other test hooks in csrc/nsk_internal.h).  0 CSR-vector, 1 stream, 2 stream on fp32
+ * values, 3 blocked, 4 blocked on fp32 values */
+int nsk_debug_spmv_form(int blk_ok, int stream_ok, int inner32, int use_stream, int use_bsr, int mode, int inner);
 
 /* ---------------------------------------------------------------------------------------------------
  * Device assembly of the Newton system and the Newton-loop state.

@@ -395,9 +395,7 @@ void Amg::setup(Ctx *c, Csr &F, const std::vector<int> &shard_off) {
 }
 
 void Amg::mv(Csr &A, const double *x, double *y, int mode, const double *z) {
-  hipStream_t s = ctx->stream;
-  if (A.stream_ok) nsk::spmv_stream(s, A.view(), A.rowblk.p, A.nblk, A.even_rows, x, nullptr, y, mode, z);
-  else nsk::spmv(s, A.view(), A.lpr, x, nullptr, y, mode, z);
+  A.spmv_launch(ctx->stream, A.spmv_form(true, false, mode), x, nullptr, y, mode, z);   // (no ghost tail, no 16-bit offsets)
   ++ctx->st.spmv_calls;
   ctx->st.spmv_bytes += (double)A.spmv_bytes() + (mode ? 8.0 * A.n_rows : 0.0);
 }

@@ -85,6 +85,27 @@ struct EventSampler {
   }
 };
 
+// One sampled operation: e0 when the scope opens, e1 (and the sample counted) when it closes; nothing while `op` is not
+// being sampled or its samples are used up
+struct Sampled {
+  EventSampler::Slot *smp;
+  hipStream_t s;
+  Sampled(EventSampler &es, int op, hipStream_t st) : smp(es.want(op)), s(st) {
+    if (smp) (void)hipEventRecord(smp->e0[smp->used], s);
+  }
+  Sampled(const Sampled &) = delete;
+  ~Sampled() {
+    if (smp) (void)hipEventRecord(smp->e1[smp->used++], s);
+  }
+};
+struct Event {   // a timing event of one scope
+  hipEvent_t e = nullptr;
+  Event() { NSK_HIP(hipEventCreate(&e)); }
+  Event(const Event &) = delete;
+  ~Event() { (void)hipEventDestroy(e); }
+  operator hipEvent_t() const { return e; }
+};
+
 // Row runs of the fused velocity block row y_u = F x_u + Bt x_p: the cap bounds both matrices' entries together
 // (jacobian_vmult; the test hook nsk_debug_spmv builds its two-matrix plans with the same calls)
 static bool fused_blk_plan(const Csr &F, const Csr &Bt, std::vector<int> &rb) {
@@ -262,11 +283,11 @@ struct nsk_handle_s {
   }
   double matfree_bytes() const { return asm_matfree_F_bytes(asm_view(), asmd.mf_stokes); }
   void matfree_apply(const DVec &x, double *y) {
-    EventSampler::Slot *smp = sampler.want(NSK_BLK_F);
-    if (smp) (void)hipEventRecord(smp->e0[smp->used], s());
-    asm_matfree_F(s(), asm_view(), asmd.cq.p, asmd.mf_nu, asmd.mf_inv_dt, asmd.mf_stokes, asmd.d0.p, x.own, x.ghost,
-                  asmd.mf_wk.p, y);
-    if (smp) (void)hipEventRecord(smp->e1[smp->used++], s());
+    {
+      Sampled smp(sampler, NSK_BLK_F, s());
+      asm_matfree_F(s(), asm_view(), asmd.cq.p, asmd.mf_nu, asmd.mf_inv_dt, asmd.mf_stokes, asmd.d0.p, x.own, x.ghost,
+                    asmd.mf_wk.p, y);
+    }
     ++ctx.st.spmv_calls;
     ctx.st.spmv_bytes += matfree_bytes();
   }
@@ -303,30 +324,17 @@ struct nsk_handle_s {
     if (b == NSK_BLK_S) return prec_type == 2 && variant == 0;
     return false;
   }
-  // Bytes per value the inner solves' SpMV of A reads: 4 when A holds an fp32 copy for the path the current options
-  // select (F: the 2x2 stream kernel; S, M_p: the scalar stream kernel), else 8 (CSR-vector kernels, no copy).
-  int inner_width(const Csr &A) const {
-    if (A.inner32 == 1) return use_stream && use_bsr && A.blk_ok ? 4 : 8;
-    if (A.inner32 == 2) return use_stream && A.stream_ok && !(A.blk_ok && use_bsr) ? 4 : 8;
-    return 8;
-  }
-  // inner: the SpMV of an inner solve (spmv_halo), which reads the fp32 copy where inner_width says so (y = A x only)
+  // The kernel form of a product with A under the handle's options (the rule: nsk::spmv_form); inner: that of
+  // the inner solves (spmv_halo), which read the fp32 copy where A holds one for that form (y = A x only)
+  SpmvForm form_of(const Csr &A, int mode = 0, bool inner = false) const { return A.spmv_form(use_stream != 0, use_bsr != 0, mode, inner); }
+  // Bytes per value the inner solves' SpMV of A reads: 4 on an fp32 copy, else 8
+  int inner_width(const Csr &A) const { return is_f32(form_of(A, 0, true)) ? 4 : 8; }
+  // (the 8 n_rows of z are counted for mode 1 only, Ctx::spmv counts them for mode 2 as well: see there)
   void spmv_nohalo(Csr &A, const DVec &x, double *y, int mode = 0, const double *z = nullptr, bool inner = false) {
-    const int op = (int)(&A - blk);
-    EventSampler::Slot *smp = sampler.want(op);
-    if (smp) (void)hipEventRecord(smp->e0[smp->used], s());
-    const bool f32 = inner && mode == 0 && inner_width(A) == 4;
-    if (f32 && A.inner32 == 1)
-      nsk::spmv_blk_stream(s(), A.blk_view32(), A.blk_rowblk.p, A.blk_nblk, x.own, x.ghost, y);
-    else if (f32)
-      nsk::spmv_stream(s(), A.view32(), A.rowblk.p, A.nblk, A.even_rows, x.own, x.ghost, y, A.off16.p, A.colbase.p);
-    else if (A.blk_ok && use_stream && use_bsr && mode == 0)
-      nsk::spmv_blk_stream(s(), A.blk_view(), A.blk_R, A.blk_C, A.blk_rowblk.p, A.blk_nblk, x.own, x.ghost, y);
-    else if (A.stream_ok && use_stream)
-      nsk::spmv_stream(s(), A.view(), A.rowblk.p, A.nblk, A.even_rows, x.own, x.ghost, y, mode, z, A.off16.p, A.colbase.p);
-    else
-      nsk::spmv(s(), A.view(), A.lpr, x.own, x.ghost, y, mode, z);
-    if (smp) (void)hipEventRecord(smp->e1[smp->used++], s());
+    {
+      Sampled smp(sampler, (int)(&A - blk), s());
+      A.spmv_launch(s(), form_of(A, mode, inner), x.own, x.ghost, y, mode, z);
+    }
     ++ctx.st.spmv_calls;
     ctx.st.spmv_bytes += (double)A.spmv_bytes() + (mode == 1 ? 8.0 * A.n_rows : 0.0);
   }
@@ -339,8 +347,6 @@ struct nsk_handle_s {
   // NSK_IOPT_INDEX16: 16-bit column offsets in the scalar stream kernels of S and M_p (SpMV and the split ILU / SGS halves)
   // wherever every run qualifies; 0: int32 columns everywhere
   bool index16 = true;
-  // does the SpMV of A go through the scalar stream kernel on 16-bit offsets with the current options?
-  bool spmv_on_index16(const Csr &A) const { return A.off16.p && A.stream_ok && use_stream && !(A.blk_ok && use_bsr); }
   void index16_for(Csr &A, const char *name) {
     A.build_index16(s(), index16);
     if (verbose() && index16 && A.stream_ok && !A.off16.p)
@@ -363,15 +369,14 @@ struct nsk_handle_s {
         fprintf(stderr, "[nsk] warning: NSK_OPT_INNER_MATRIX_FREE_F = 1, but %s: the inner FGMRES multiplies by the assembled F\n", why);
       }
     }
-    const bool blocked = A.blk_ok && use_stream && use_bsr;
-    const bool streamed = !blocked && A.stream_ok && use_stream;
-    const bool f32 = inner_width(A) == 4;
-    if (f32 && A.val32_version != A.values_version) A.refresh_f32(s(), false);   // (stream-ordered: no host sync)
+    const SpmvForm form = form_of(A, 0, true);
+    if (is_f32(form) && A.val32_version != A.values_version) A.refresh_f32(s(), false);   // (stream-ordered: no host sync)
+    const bool blocked = is_blk(form);
     const int b0 = blocked ? A.blk_int_b0 : A.int_b0, b1 = blocked ? A.blk_int_b1 : A.int_b1;
     const int nb = blocked ? A.blk_nblk : A.nblk;
     EventSampler::Slot *smp = sampler.find((int)(&A - blk));
     const bool sampling = smp && smp->used < smp->cap;   // (a launch that is being timed stays one launch)
-    if (!overlap_halo || ctx.comm.nranks <= 1 || !(blocked || streamed) || b1 <= b0 || sampling) {
+    if (!overlap_halo || ctx.comm.nranks <= 1 || form == SpmvForm::csr_vector || b1 <= b0 || sampling) {
       halo(space, x);
       spmv_nohalo(A, x, y, 0, nullptr, true);
       return;
@@ -379,13 +384,7 @@ struct nsk_handle_s {
     if (smp) ++smp->seen;
     ++overlapped_spmvs;
     ctx.ensure_stream2();
-    auto part = [&](hipStream_t st, int c0, int c1) {
-      if (c1 <= c0) return;
-      if (blocked && f32) nsk::spmv_blk_stream(st, A.blk_view32(), A.blk_rowblk.p + c0, c1 - c0, x.own, x.ghost, y);
-      else if (blocked) nsk::spmv_blk_stream(st, A.blk_view(), A.blk_R, A.blk_C, A.blk_rowblk.p + c0, c1 - c0, x.own, x.ghost, y);
-      else if (f32) nsk::spmv_stream(st, A.view32(), A.rowblk.p + c0, c1 - c0, A.even_rows, x.own, x.ghost, y, A.off16.p, A.off16.p ? A.colbase.p + c0 : nullptr);
-      else nsk::spmv_stream(st, A.view(), A.rowblk.p + c0, c1 - c0, A.even_rows, x.own, x.ghost, y, 0, nullptr, A.off16.p, A.off16.p ? A.colbase.p + c0 : nullptr);
-    };
+    auto part = [&](hipStream_t st, int c0, int c1) { A.spmv_launch(st, form, x.own, x.ghost, y, 0, nullptr, c0, c1); };
     NSK_HIP(hipEventRecord(ctx.ev_fork, s()));                 // x is complete here
     NSK_HIP(hipStreamWaitEvent(ctx.stream2, ctx.ev_fork, 0));
     part(ctx.stream2, b0, b1);                                 // interior rows: owned entries of x only
@@ -439,10 +438,8 @@ struct nsk_handle_s {
     spmv_nohalo(B, xu, yb + n_u(), 0);
   }
   void tri_apply_sampled(TriSolve &T, int op, const double *b, double *x) {
-    EventSampler::Slot *smp = sampler.want(op);
-    if (smp) (void)hipEventRecord(smp->e0[smp->used], s());
+    Sampled smp(sampler, op, s());
     T.apply(b, x);
-    if (smp) (void)hipEventRecord(smp->e1[smp->used++], s());
   }
   std::vector<int> sub_offsets(int space) const {
     std::vector<int> off;
@@ -472,15 +469,23 @@ struct nsk_handle_s {
         e |= ei;
       }
     if (ctx.comm.active() && sync_free_mode > 0) {
-      const int sl = ctx.alloc_slots(1);
+      const SlotLease sl(ctx, 1);
       vec_set(s(), 1, ctx.slot(sl), e ? 1.0 : 0.0);
       ctx.comm.allreduce_sum(ctx.slot(sl), 1, s());
       e = ctx.read_slots(sl, 1)[0] > 0.0;
-      ctx.slot_top = sl;
     }
     if (e)
       throw Error(-70, "sync-free triangular solve: a producer/consumer wait ran out of spins (results invalid); "
                        "set NSK_OPT_TRI_SYNC_FREE to 0");
+  }
+  // what the triangular factors take of the handle's options (every nsk_set_option, every set-up)
+  void push_tri_options() {
+    tMp.sync_free = tS.sync_free = sync_free_mode >= 1;
+    tF.sync_free = sync_free_mode == 2;
+    tMp.sf_fault = tS.sf_fault = (fault_inject & 1) != 0;
+    tF.sf_fault = (fault_inject & 2) != 0;
+    tMp.want_index16 = tS.want_index16 = index16;
+    tF.use_stream = tMp.use_stream = tS.use_stream = use_stream != 0;
   }
   void schur_symbolic();
   void setup(int type, int variant_, double alpha_);
@@ -586,11 +591,7 @@ void H::setup(int type, int variant_, double alpha_) {
   ensure_pools();
   drop_pending();   // a fresh preconditioner object: the application the last solve left over fed the old one's state
   ctx.ws.pairs = blas1_pairs < 0 ? (variant_ == 0) : blas1_pairs;   // NSK_OPT_BLAS1_PAIRS
-  tMp.sync_free = tS.sync_free = sync_free_mode >= 1;
-  tMp.want_index16 = tS.want_index16 = index16;
-  tF.sync_free = sync_free_mode == 2;
-  tMp.sf_fault = tS.sf_fault = (fault_inject & 1) != 0;
-  tF.sf_fault = (fault_inject & 2) != 0;
+  push_tri_options();
   // storage precision of the factors' off-diagonal values; NSK_FACTOR_PRECISION=32 / 64 overrides the option (A/B
   // measurements with unchanged callers), any other value is ignored.  numeric() reallocates the halves when it changes.
   static const int env_precision = [] {
@@ -731,14 +732,12 @@ void H::setup(int type, int variant_, double alpha_) {
   matfree_wanted = (env_matfree >= 0 ? env_matfree : matrix_free_f) == 1;
   for (int b : {(int)NSK_BLK_F, (int)NSK_BLK_MP, (int)NSK_BLK_S}) {
     Csr &A = blk[b];
-    int mode = 0;
     // (F while its products are matrix-free: no stored value is read, so no copy is made)
-    if (inner32 && A.present && use_stream && inner_solve_on(b) && !(b == NSK_BLK_F && matfree_in_effect())) {
-      if (b == NSK_BLK_F) mode = use_bsr && A.blk_ok && A.blk_R == 2 && A.blk_C == 2 ? 1 : 0;
-      else mode = A.stream_ok && !A.blk_ok ? 2 : 0;
-    }
-    if (!mode) { A.release_f32(); continue; }
-    A.inner32 = mode;
+    const bool wanted = inner32 && A.present && inner_solve_on(b) && !(b == NSK_BLK_F && matfree_in_effect());
+    // the copy this block would hold: F's 2 x 2 blocks (the only shape build_blocked gives F, and the only one of the
+    // blocked fp32 kernel), else the scalar values — kept where the rule gives the inner product an _f32 form for it
+    A.inner32 = !wanted ? 0 : b == NSK_BLK_F ? 1 : 2;
+    if (!is_f32(form_of(A, 0, true))) { A.release_f32(); continue; }   // (release_f32 puts inner32 back to 0)
     A.refresh_f32(s(), true);
   }
   ctx.sync();
@@ -772,7 +771,7 @@ void H::prec_vmult(DVec &dst, const DVec &src) {
     // the application the last solve did not need: this one starts from the state it leaves (counted as work done)
     const SolverFGMRES::Pending p = pending;
     pending = SolverFGMRES::Pending{};
-    struct Put { VecPool &pool; double *v, *z; ~Put() { pool.put(v); pool.put(z); } } put{pool_b, p.v, p.z};
+    const Lease z = Lease::adopt(pool_b, p.z), v = Lease::adopt(pool_b, p.v);
     DVec pz = bb(p.z);
     prec_vmult(pz, bb(p.v));
   }
@@ -787,8 +786,7 @@ void H::prec_vmult(DVec &dst, const DVec &src) {
     else tri_apply_sampled(tF, 20, r.own, d.own);
   };
   PrecVmult P_P = [&](DVec &d, const DVec &r) { tri_apply_sampled(*tP, 21, r.own, d.own); };
-  const int sl = ctx.alloc_slots(4);
-  struct Rel { Ctx &c; int sl; ~Rel() { c.slot_top = sl; } } rel{ctx, sl};
+  const SlotLease sl(ctx, 4);
   auto norm_of = [&](const double *v, int n) { ctx.norm2(n, v, sl); return ctx.read_slots(sl + 1, 1)[0]; };
 
   if (prec_type == 0 || prec_type == 1) {
@@ -944,8 +942,7 @@ int H::solve_resident(int solver, double tol, int max_iter, int *iters, double *
   } catch (const Error &e) {
     if (e.code != -70 || !guarded) throw;
     const long undo = outer_iters;
-    sync_free_mode = 0;
-    tMp.sync_free = tS.sync_free = tF.sync_free = false;
+    sync_free_mode = 0;   // (setup() below pushes it into the factors)
     ++sync_free_fallbacks;
     ctx.warn("single-launch triangular solve: a producer/consumer wait ran out of spins (workgroups not resident in "
              "dispatch order: another process on the GPU?); the solve is redone from the caller's initial guess with one "
@@ -1279,17 +1276,14 @@ int nsk_set_option(nsk_handle h, int opt, double v) {
     case NSK_OPT_TRI_ORDERING: h->tri_ordering = v != 0.0 ? ORDER_MULTICOLOR : ORDER_NATURAL; break;
     case NSK_OPT_SUBDOMAINS: h->subdomains = std::max(1, (int)v); break;
     case NSK_OPT_FUSE_BLOCK_ROW: h->fuse_block_row = v != 0.0; break;
+    // (the next line keeps its own push of use_stream beside push_tri_options below: tests read the NSK_OPT case lines)
     case NSK_OPT_STREAM_KERNELS: h->use_stream = v != 0.0; h->tF.use_stream = h->tMp.use_stream = h->tS.use_stream = h->use_stream; break;
     case NSK_OPT_TRI_SYNC_FREE:
       if (v != 0.0 && v != 1.0 && v != 2.0) throw Error(-61, "NSK_OPT_TRI_SYNC_FREE: 0, 1 or 2");
       h->sync_free_mode = (int)v;
-      h->tMp.sync_free = h->tS.sync_free = v >= 1.0;
-      h->tF.sync_free = v == 2.0;
       break;
     case NSK_IOPT_FAULT_INJECT:
       h->fault_inject = (int)v;
-      h->tMp.sf_fault = h->tS.sf_fault = (h->fault_inject & 1) != 0;
-      h->tF.sf_fault = (h->fault_inject & 2) != 0;
       h->ctx.mgs_fault = (h->fault_inject & 4) != 0;
       break;
     case NSK_OPT_TRI_LINE_GROUPS:
@@ -1321,7 +1315,6 @@ int nsk_set_option(nsk_handle h, int opt, double v) {
     case NSK_IOPT_TIMEOP_BETWEEN: h->timeop_between = (int)v; break;
     case NSK_IOPT_INDEX16:
       h->index16 = v != 0.0;
-      h->tS.want_index16 = h->tMp.want_index16 = h->index16;
       (void)hipSetDevice(h->ctx.device);
       for (int b : {NSK_BLK_MP, NSK_BLK_S})
         if (h->blk[b].present && h->blk[b].stream_ok) h->index16_for(h->blk[b], b == NSK_BLK_S ? "S" : "M_p");
@@ -1369,6 +1362,7 @@ int nsk_set_option(nsk_handle h, int opt, double v) {
     case NSK_OPT_CG_SINGLE_REDUCTION: h->cg_fused = v != 0.0; break;
     default: throw Error(-61, "nsk_set_option: unknown option");
   }
+  h->push_tri_options();
   return 0;
   NSK_CATCH(h)
 }
@@ -1431,15 +1425,13 @@ int nsk_spmv(nsk_handle h, int b, const double *x, double *y, int add) {
   const int rs = (b == NSK_BLK_F || b == NSK_BLK_BT) ? 0 : 1, cs = (b == NSK_BLK_F || b == NSK_BLK_B) ? 0 : 1;
   if (b == NSK_BLK_BT_GHOST) throw Error(-63, "nsk_spmv: ghost rows are not an operator");
   VecPool &pc = cs == 0 ? h->pool_u : h->pool_p, &pr = rs == 0 ? h->pool_u : h->pool_p;
-  double *xv = pc.get(true), *yv = pr.get(true);
+  const Lease xv(pc, true), yv(pr, true);
   NSK_HIP(hipMemcpyAsync(xv, x, sizeof(double) * (size_t)pc.n, hipMemcpyHostToDevice, h->s()));
   if (add) NSK_HIP(hipMemcpyAsync(yv, y, sizeof(double) * (size_t)pr.n, hipMemcpyHostToDevice, h->s()));
   h->halo(cs, pc.view(xv));
   h->spmv_nohalo(A, pc.view(xv), yv, add ? 1 : 0);
   NSK_HIP(hipMemcpyAsync(y, yv, sizeof(double) * (size_t)pr.n, hipMemcpyDeviceToHost, h->s()));
   h->ctx.sync();
-  pc.put(xv);
-  pr.put(yv);
   return 0;
   NSK_CATCH(h)
 }
@@ -1448,15 +1440,13 @@ int nsk_jacobian_vmult(nsk_handle h, const double *xu, const double *xp, double 
   NSK_TRY(h)
   (void)hipSetDevice(h->ctx.device);
   h->ensure_pools();
-  double *xb = h->pool_b.get(true), *yb = h->pool_b.get(true);
+  const Lease xb(h->pool_b, true), yb(h->pool_b, true);
   NSK_HIP(hipMemcpyAsync(xb, xu, sizeof(double) * (size_t)h->n_u(), hipMemcpyHostToDevice, h->s()));
   NSK_HIP(hipMemcpyAsync(xb + h->n_u(), xp, sizeof(double) * (size_t)h->n_p(), hipMemcpyHostToDevice, h->s()));
   h->jacobian_vmult(h->bb(xb), yb);
   NSK_HIP(hipMemcpyAsync(yu, yb, sizeof(double) * (size_t)h->n_u(), hipMemcpyDeviceToHost, h->s()));
   NSK_HIP(hipMemcpyAsync(yp, yb + h->n_u(), sizeof(double) * (size_t)h->n_p(), hipMemcpyDeviceToHost, h->s()));
   h->ctx.sync();
-  h->pool_b.put(xb);
-  h->pool_b.put(yb);
   return 0;
   NSK_CATCH(h)
 }
@@ -1467,13 +1457,12 @@ int nsk_dot(nsk_handle h, int n, const double *x, const double *y, double *dot_o
   DBuf<double> dx, dy;
   dx.upload(x, (size_t)n, h->s());
   dy.upload(y, (size_t)n, h->s());
-  const int sl = h->ctx.alloc_slots(4);
+  const SlotLease sl(h->ctx, 4);
   h->ctx.dot(n, dx.p, dy.p, sl);
   h->ctx.norm2(n, dx.p, sl + 1);
   const double *r = h->ctx.read_slots(sl, 3);
   if (dot_out) *dot_out = r[0];
   if (norm_out) *norm_out = r[2];
-  h->ctx.slot_top = sl;
   return 0;
   NSK_CATCH(h)
 }
@@ -1492,8 +1481,7 @@ int nsk_vec_op(nsk_handle h, int op, int n, double a, double c, const double *x,
   dy.upload(y, (size_t)n, s);
   dz.upload(z, (size_t)n, s);
   dd.upload(d, (size_t)n, s);
-  const int sl = h->ctx.alloc_slots(2);
-  struct Rel { Ctx &c; int sl; ~Rel() { c.slot_top = sl; } } rel{h->ctx, sl};
+  const SlotLease sl(h->ctx, 2);
   double sc = 0.0;
   switch (op) {
     case 0: vec_copy(s, n, dx.p, dy.p); break;
@@ -1776,8 +1764,7 @@ int nsk_assemble(nsk_handle h, int stokes, double nu, double inv_dt, double p_ou
   Csr &F = h->blk[NSK_BLK_F];
   hipStream_t s = h->s();
   const double t0 = wall_ms();
-  const int sl = h->ctx.alloc_slots(3);
-  struct Rel { Ctx &c; int sl; ~Rel() { c.slot_top = sl; } } rel{h->ctx, sl};
+  const SlotLease sl(h->ctx, 3);
   if (A.simplex) {   // P2/P1 triangles: general cells (nsk_assembly_kernels.hip, second half)
     const SimplexMesh SM{A.n_cells, A.sx_blocks, h->n_u() / 2, h->n_p(), A.sx_pos00, A.cell_u.p, A.cell_p.p, A.sx_grad.p,
                          A.sx_area.p, A.sx_blk_ptr.p, A.sx_blk_ent.p, A.sx_pos0.p, A.sx_pos1.p, A.sx_node_ptr.p,
@@ -1850,10 +1837,8 @@ int nsk_time_assemble(nsk_handle h, double nu, double inv_dt, int reps, double *
   Csr &F = h->blk[NSK_BLK_F];
   hipStream_t s = h->s();
   const AsmMesh M = h->asm_view();
-  const int sl = h->ctx.alloc_slots(1);
-  hipEvent_t e0, e1;
-  NSK_HIP(hipEventCreate(&e0));
-  NSK_HIP(hipEventCreate(&e1));
+  const SlotLease sl(h->ctx, 1);
+  const Event e0, e1;
   auto once = [&]() {
     asm_cell_state(s, M, A.sol_u, A.sol_p, A.have_old ? A.old_u : nullptr, A.cq.p);
     asm_d0(s, M, A.cq.p, nu, inv_dt, 0, h->ctx.slot(sl));
@@ -1873,9 +1858,6 @@ int nsk_time_assemble(nsk_handle h, double nu, double inv_dt, int reps, double *
   NSK_HIP(hipEventSynchronize(e1));
   float ms = 0;
   NSK_HIP(hipEventElapsedTime(&ms, e0, e1));
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  h->ctx.slot_top = sl;
   if (avg_ms) *avg_ms = ms / reps;
   return 0;
   NSK_CATCH(h)
@@ -1887,14 +1869,12 @@ int nsk_tri_apply(nsk_handle h, int which, const double *b, double *x) {
   if (h->prec_type < 0) throw Error(-46, "call nsk_setup_preconditioner first");
   TriSolve *T = which == NSK_TRI_VELOCITY ? &h->tF : h->tP;
   VecPool &p = which == NSK_TRI_VELOCITY ? h->pool_u : h->pool_p;
-  double *bv = p.get(true), *xv = p.get(true);
+  const Lease bv(p, true), xv(p, true);
   NSK_HIP(hipMemcpyAsync(bv, b, sizeof(double) * (size_t)p.n, hipMemcpyHostToDevice, h->s()));
   if (which == NSK_TRI_VELOCITY && h->amg_active) { h->amg_ready(); h->amgF.apply(bv, xv); }  // the velocity preconditioner is the AMG
   else T->apply(bv, xv);
   NSK_HIP(hipMemcpyAsync(x, xv, sizeof(double) * (size_t)p.n, hipMemcpyDeviceToHost, h->s()));
   h->ctx.sync();
-  p.put(bv);
-  p.put(xv);
   h->check_sync_free();
   return 0;
   NSK_CATCH(h)
@@ -1909,7 +1889,7 @@ int nsk_debug_tri_trace(nsk_handle h, int which, int64_t *out16, int max_runs, i
   if (!(T->stream_ready && T->sync_free)) return 0;   // only the scalar single-launch kernels carry the stamps
   const int n_wg = T->n_Lsf + T->n_Usf;
   VecPool &p = which == NSK_TRI_VELOCITY ? h->pool_u : h->pool_p;
-  double *bv = p.get(true), *xv = p.get(true);
+  const Lease bv(p, true), xv(p, true);
   vec_set(h->s(), p.n, bv, 1.0);
   T->apply(bv, xv);   // warm
   DBuf<long long> dbg;
@@ -1921,8 +1901,6 @@ int nsk_debug_tri_trace(nsk_handle h, int which, int64_t *out16, int max_runs, i
   const int n = std::min(max_runs, n_wg);
   NSK_HIP(hipMemcpyAsync(out16, dbg.p, sizeof(long long) * (size_t)n * 16, hipMemcpyDeviceToHost, h->s()));
   h->ctx.sync();
-  p.put(bv);
-  p.put(xv);
   if (grid) *grid = -T->n_Lsf;
   h->check_sync_free();
   return n_wg;
@@ -1979,12 +1957,7 @@ int nsk_debug_krylov(nsk_handle h, int op, int n, int m, int offset, const doubl
     d[k] = buf[k].p + offset;
     NSK_HIP(hipMemcpyAsync(d[k], vec[k], sizeof(double) * (size_t)len[k], hipMemcpyHostToDevice, st));
   }
-  struct Restore {
-    Ctx &c;
-    int top;
-    ~Restore() { c.slot_top = top; }
-  } restore{c, c.slot_top};
-  const int so = c.alloc_slots(64);
+  const SlotLease so(c, 64);
   NSK_HIP(hipMemsetAsync(c.slot(so), 0xFF, sizeof(double) * 64, st));
   auto set_slots = [&](int count) {
     NSK_HIP(hipMemcpyAsync(c.slot(so), par, sizeof(double) * (size_t)count, hipMemcpyHostToDevice, st));
@@ -2266,29 +2239,22 @@ int nsk_debug_spmv(nsk_handle h, int form, int lpr, int mode, int misalign, int 
       if (lpr != 2 && lpr != 4 && lpr != 8 && lpr != 16 && lpr != 32 && lpr != 64) throw Error(-61, "nsk_debug_spmv: lpr");
       info[2] = nsk::spmv(st, A.view(), lpr, xa.p, xag.p, yv.p, mode, zv.p);
       break;
-    case NSK_DBG_SPMV_STREAM:
-      info[1] = nsk::spmv_stream(st, A.view(), d_rb + c0, n_run, A.even_rows, xa.p, xag.p, yv.p, mode, zv.p);
+    // the single-matrix run forms through the handle's launcher (16-bit offsets: built above for the I16 forms only)
+    case NSK_DBG_SPMV_STREAM: case NSK_DBG_SPMV_STREAM_I16:
+      info[1] = A.spmv_launch(st, SpmvForm::stream, xa.p, xag.p, yv.p, mode, zv.p, c0, c1);
       break;
-    case NSK_DBG_SPMV_STREAM_I16:
-      info[1] = nsk::spmv_stream(st, A.view(), d_rb + c0, n_run, A.even_rows, xa.p, xag.p, yv.p, mode, zv.p, A.off16.p, A.colbase.p + c0);
-      break;
-    case NSK_DBG_SPMV_STREAM_I16_F32:
+    case NSK_DBG_SPMV_STREAM_F32: case NSK_DBG_SPMV_STREAM_I16_F32:
       A.inner32 = 2;
       A.refresh_f32(st, false);
-      info[1] = nsk::spmv_stream(st, A.view32(), d_rb + c0, n_run, A.even_rows, xa.p, xag.p, yv.p, A.off16.p, A.colbase.p + c0);
-      break;
-    case NSK_DBG_SPMV_STREAM_F32:
-      A.inner32 = 2;
-      A.refresh_f32(st, false);
-      info[1] = nsk::spmv_stream(st, A.view32(), d_rb + c0, n_run, A.even_rows, xa.p, xag.p, yv.p);
+      info[1] = A.spmv_launch(st, SpmvForm::stream_f32, xa.p, xag.p, yv.p, 0, nullptr, c0, c1);
       break;
     case NSK_DBG_SPMV_BLK22: case NSK_DBG_SPMV_BLK21: case NSK_DBG_SPMV_BLK12: case NSK_DBG_SPMV_BLK11:
-      nsk::spmv_blk_stream(st, A.blk_view(), R, C, d_rb + c0, n_run, xa.p, xag.p, yv.p);
+      A.spmv_launch(st, SpmvForm::blk, xa.p, xag.p, yv.p, 0, nullptr, c0, c1);
       break;
     case NSK_DBG_SPMV_BLK22_F32:
       A.inner32 = 1;
       A.refresh_f32(st, false);
-      nsk::spmv_blk_stream(st, A.blk_view32(), d_rb + c0, n_run, xa.p, xag.p, yv.p);
+      A.spmv_launch(st, SpmvForm::blk_f32, xa.p, xag.p, yv.p, 0, nullptr, c0, c1);
       break;
     case NSK_DBG_SPMV_BLK21_EPI:
       nsk::spmv_blk_stream(st, A.blk_view(), 2, 1, d_rb + c0, n_run, xa.p, xag.p, yv.p, dv.p, div.p);
@@ -2339,13 +2305,25 @@ int nsk_debug_index_width(nsk_handle h, int b, int32_t *out3) {
   if (h->prec_type < 0) throw Error(-46, "call nsk_setup_preconditioner first");
   const Csr &A = h->blk[b];
   const TriSolve &T = b == NSK_BLK_S ? h->tS : h->tMp;
-  const bool spmv_streams = A.present && A.stream_ok && h->use_stream && !(A.blk_ok && h->use_bsr);
-  out3[0] = !spmv_streams ? 0 : h->spmv_on_index16(A) ? 16 : 32;
+  out3[0] = !A.present || h->form_of(A) != SpmvForm::stream ? 0 : A.off16.p ? 16 : 32;
   const bool halves = T.stream_ready && T.halves_in_use();
   out3[1] = !halves ? 0 : T.Loff16.p ? 16 : 32;
   out3[2] = !halves ? 0 : T.Uoff16.p ? 16 : 32;
   return 0;
   NSK_CATCH(h)
+}
+
+int nsk_debug_spmv_form(int blk_ok, int stream_ok, int inner32, int use_stream, int use_bsr, int mode, int inner) {   // nsk_internal.h
+  return (int)spmv_form(blk_ok != 0, stream_ok != 0, inner32, use_stream != 0, use_bsr != 0, mode, inner != 0);
+}
+
+int nsk_debug_pool_counts(nsk_handle h, int32_t *out6) {   // nsk_internal.h
+  int k = 0;
+  for (const VecPool *p : {&h->pool_u, &h->pool_p, &h->pool_b}) {
+    out6[k++] = (int32_t)p->all.size();
+    out6[k++] = (int32_t)p->free_list.size();
+  }
+  return 0;
 }
 
 int nsk_inner_value_bytes(nsk_handle h, int b, int32_t *bytes) {
@@ -2373,13 +2351,11 @@ int nsk_inner_spmv(nsk_handle h, int b, const double *x, double *y) {
   if (!h->blk[b].present) throw Error(-62, "nsk_inner_spmv: block not set");
   const int space = b == NSK_BLK_F ? 0 : 1;
   VecPool &pool = space == 0 ? h->pool_u : h->pool_p;
-  double *xv = pool.get(true), *yv = pool.get(true);
+  const Lease xv(pool, true), yv(pool, true);
   NSK_HIP(hipMemcpyAsync(xv, x, sizeof(double) * (size_t)pool.n, hipMemcpyHostToDevice, h->s()));
   h->spmv_halo(h->blk[b], space, pool.view(xv), yv);
   NSK_HIP(hipMemcpyAsync(y, yv, sizeof(double) * (size_t)pool.n, hipMemcpyDeviceToHost, h->s()));
   h->ctx.sync();
-  pool.put(xv);
-  pool.put(yv);
   return 0;
   NSK_CATCH_ABORT(h)
 }
@@ -2395,13 +2371,11 @@ int nsk_matfree_f(nsk_handle h, const double *x, double *y) {
   NSK_TRY(h)
   (void)hipSetDevice(h->ctx.device);
   h->matfree_check("nsk_matfree_f");
-  double *xv = h->pool_u.get(true), *yv = h->pool_u.get(true);
+  const Lease xv(h->pool_u, true), yv(h->pool_u, true);
   NSK_HIP(hipMemcpyAsync(xv, x, sizeof(double) * (size_t)h->pool_u.n, hipMemcpyHostToDevice, h->s()));
   h->matfree_apply(h->pool_u.view(xv), yv);
   NSK_HIP(hipMemcpyAsync(y, yv, sizeof(double) * (size_t)h->pool_u.n, hipMemcpyDeviceToHost, h->s()));
   h->ctx.sync();
-  h->pool_u.put(xv);
-  h->pool_u.put(yv);
   return 0;
   NSK_CATCH(h)
 }
@@ -2423,7 +2397,7 @@ int nsk_precond_vmult(nsk_handle h, const double *su, const double *sp_, double 
   NSK_TRY(h)
   (void)hipSetDevice(h->ctx.device);
   if (h->prec_type < 0) throw Error(-46, "call nsk_setup_preconditioner first");
-  double *sb = h->pool_b.get(true), *db = h->pool_b.get(true);
+  const Lease sb(h->pool_b, true), db(h->pool_b, true);
   const size_t bu = sizeof(double) * (size_t)h->n_u(), bp = sizeof(double) * (size_t)h->n_p();
   NSK_HIP(hipMemcpyAsync(sb, su, bu, hipMemcpyHostToDevice, h->s()));
   NSK_HIP(hipMemcpyAsync(sb + h->n_u(), sp_, bp, hipMemcpyHostToDevice, h->s()));
@@ -2440,8 +2414,6 @@ int nsk_precond_vmult(nsk_handle h, const double *su, const double *sp_, double 
   NSK_HIP(hipMemcpyAsync(du, db, bu, hipMemcpyDeviceToHost, h->s()));
   NSK_HIP(hipMemcpyAsync(dp, db + h->n_u(), bp, hipMemcpyDeviceToHost, h->s()));
   h->ctx.sync();
-  h->pool_b.put(sb);
-  h->pool_b.put(db);
   h->check_sync_free();
   return rc;
   NSK_CATCH_ABORT(h)
@@ -2559,7 +2531,7 @@ int nsk_profile_read(nsk_handle h, int op, double *avg_ms, int *n_samples, doubl
   if (bytes_format) {   // what the storage format in use really holds (<= the CSR figure for the node-block copies)
     // (F, S, M_p with fp32 copies for the inner solves: the fp32 format — see nsk.h, NSK_OPT_INNER_MATRIX_PRECISION)
     if (op == NSK_BLK_F && h->matfree_in_effect()) *bytes_format = h->matfree_bytes();
-    else if (op >= 0 && op <= NSK_BLK_S) *bytes_format = h->blk[op].format_bytes(h->use_stream && h->use_bsr, h->inner_width(h->blk[op]), h->spmv_on_index16(h->blk[op]));
+    else if (op >= 0 && op <= NSK_BLK_S) *bytes_format = h->blk[op].format_bytes(h->form_of(h->blk[op], 0, true));
     else if (op == 20) *bytes_format = h->tF.format_bytes();
     else if (op == 21 && h->tP) *bytes_format = h->tP->format_bytes();
     else *bytes_format = 0.0;
@@ -2582,13 +2554,18 @@ int nsk_time_op(nsk_handle h, int op, int reps, double *avg_ms, double *bytes) {
   (void)hipSetDevice(h->ctx.device);
   h->ensure_pools();
   if (reps < 1) reps = 1;
-  hipEvent_t e0, e1;
-  NSK_HIP(hipEventCreate(&e0));
-  NSK_HIP(hipEventCreate(&e1));
-  double *xb = h->pool_b.get(true), *yb = h->pool_b.get(true), *zb = h->pool_b.get(true);
+  // everything this call borrows goes back on every way out: events, vectors (`held`: the operands an op takes on top
+  // of the three block vectors), reduction slots.  The operands stay borrowed while the op is timed, so the operation
+  // of NSK_IOPT_TIMEOP_BETWEEN gets vectors of its own (it used to be handed the timed op's x back): one or two more
+  // pool vectors in that mode
+  const Event e0, e1;
+  const Lease xl(h->pool_b, true), yl(h->pool_b, true), zl(h->pool_b, true);
+  double *const xb = xl, *const yb = yl, *const zb = zl;   // (the operations below capture plain pointers)
+  std::vector<Lease> held;
   vec_set(h->s(), h->N(), xb, 1.0);
   vec_set(h->s(), h->N(), zb, 0.5);
-  const int sl = h->ctx.alloc_slots(4);
+  const SlotLease slots(h->ctx, 4);
+  const int sl = slots;
   double by = 0.0;
   std::function<void()> f;
   if (op >= 0 && op <= NSK_BLK_S && op != NSK_BLK_BT_GHOST) {
@@ -2597,12 +2574,11 @@ int nsk_time_op(nsk_handle h, int op, int reps, double *avg_ms, double *bytes) {
     const int cs = (op == NSK_BLK_F || op == NSK_BLK_B) ? 0 : 1;
     // operand from the pool of its own space, as the inner solvers hand it over (owned | ghost contiguous, aligned)
     VecPool &pc = cs == 0 ? h->pool_u : h->pool_p;
-    double *xs = pc.get(true);
+    double *xs = held.emplace_back(pc, true);
     vec_set(h->s(), pc.n, xs, 1.0);
     const DVec xv = pc.view(xs);
     by = (double)A.spmv_bytes();
     f = [=, &A]() { h->halo(cs, xv); h->spmv_nohalo(A, xv, yb, 0); };
-    pc.put(xs);   // stays valid until the pool hands it out again (not during this call)
   } else if (op == 50 + NSK_BLK_F || op == 50 + NSK_BLK_MP || op == 50 + NSK_BLK_S) {
     // the inner solves' SpMV of that block, with the values and kernel they read (fp32 copy or double)
     const int b = op - 50;
@@ -2611,22 +2587,19 @@ int nsk_time_op(nsk_handle h, int op, int reps, double *avg_ms, double *bytes) {
     Csr &A = h->blk[b];
     const int cs = b == NSK_BLK_F ? 0 : 1;
     VecPool &pc = cs == 0 ? h->pool_u : h->pool_p;
-    double *xs = pc.get(true);
+    double *xs = held.emplace_back(pc, true);
     vec_set(h->s(), pc.n, xs, 1.0);
     const DVec xv = pc.view(xs);
-    by = b == NSK_BLK_F && h->matfree_in_effect() ? h->matfree_bytes()
-                                                  : A.format_bytes(h->use_stream && h->use_bsr, h->inner_width(A), h->spmv_on_index16(A));
+    by = b == NSK_BLK_F && h->matfree_in_effect() ? h->matfree_bytes() : A.format_bytes(h->form_of(A, 0, true));
     f = [=, &A]() { h->spmv_halo(A, cs, xv, yb); };
-    pc.put(xs);   // stays valid until the pool hands it out again (not during this call)
   } else if (op == 56) {
     // the matrix-free product with F on the state of the last assembly, whatever the option says (nsk_matfree_f)
     h->matfree_check("nsk_time_op");
-    double *xs = h->pool_u.get(true);
+    double *xs = held.emplace_back(h->pool_u, true);
     vec_set(h->s(), h->pool_u.n, xs, 1.0);
     const DVec xv = h->pool_u.view(xs);
     by = h->matfree_bytes();
     f = [=]() { h->matfree_apply(xv, yb); };
-    h->pool_u.put(xs);   // stays valid until the pool hands it out again (not during this call)
   } else if (op == 10) {
     Csr &F = h->blk[NSK_BLK_F], &Bt = h->blk[NSK_BLK_BT], &B = h->blk[NSK_BLK_B];
     by = (double)F.spmv_bytes() + (double)Bt.spmv_bytes() + (double)B.spmv_bytes();
@@ -2656,7 +2629,7 @@ int nsk_time_op(nsk_handle h, int op, int reps, double *avg_ms, double *bytes) {
     const int n = h->n_u();
     auto vs = std::make_shared<std::vector<double *>>();
     for (int k = 0; k < 9; ++k) {
-      vs->push_back(h->pool_u.get(true));
+      vs->push_back(held.emplace_back(h->pool_u, true));
       vec_set(h->s(), n, vs->back(), 1.0 / (k + 1));
     }
     const int cs = h->ctx.alloc_slots(10);
@@ -2665,14 +2638,13 @@ int nsk_time_op(nsk_handle h, int op, int reps, double *avg_ms, double *bytes) {
       if (op == 33) h->ctx.multi_dot(n, (*vs)[8], vs->data(), 8, cs, true);
       else h->ctx.multi_axpy(n, (*vs)[8], vs->data(), 8, cs, -1);
     };
-    for (double *p : *vs) h->pool_u.put(p);   // (stay valid until the pool hands them out again: not during this call)
   } else if (op >= 35 && op <= 37) {
     // the same sweeps over a whole basis of 30 (Ctx::multi_dot_all / multi_axpy_all with the norm) and the cycle-end update
     // of 29 terms (Ctx::multi_add), as NSK_IOPT_GS_ONE_LAUNCH launches them; bytes: what the chosen form moves
     const int n = h->n_u(), m = op == 37 ? 29 : 30;
     auto vs = std::make_shared<std::vector<double *>>();
     for (int k = 0; k <= m; ++k) {
-      vs->push_back(h->pool_u.get(true));
+      vs->push_back(held.emplace_back(h->pool_u, true));
       vec_set(h->s(), n, vs->back(), 1.0 / (k + 1));
     }
     const int cs = h->ctx.alloc_slots(m + 2);
@@ -2686,7 +2658,6 @@ int nsk_time_op(nsk_handle h, int op, int reps, double *avg_ms, double *bytes) {
     const double b0 = h->ctx.st.blas1_bytes;
     f();
     by = h->ctx.st.blas1_bytes - b0;
-    for (double *p : *vs) h->pool_u.put(p);   // (stay valid until the pool hands them out again: not during this call)
   } else if (op == 40 || op == 41) {
     // host round trip of one device scalar (what every Krylov iteration pays for its SolverControl check): wall time
     const double t0 = wall_ms();
@@ -2696,12 +2667,6 @@ int nsk_time_op(nsk_handle h, int op, int reps, double *avg_ms, double *bytes) {
     }
     if (avg_ms) *avg_ms = (wall_ms() - t0) / reps;
     if (bytes) *bytes = op == 41 ? 16.0 * h->N() : 0.0;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    h->ctx.slot_top = sl;
-    h->pool_b.put(xb);
-    h->pool_b.put(yb);
-    h->pool_b.put(zb);
     return 0;
   } else {
     throw Error(-65, "nsk_time_op: unknown op");
@@ -2714,7 +2679,7 @@ int nsk_time_op(nsk_handle h, int op, int reps, double *avg_ms, double *bytes) {
     Csr &A = h->blk[bw];
     VecPool &pc = (bw == NSK_BLK_F || bw == NSK_BLK_B) ? h->pool_u : h->pool_p;
     VecPool &pr = (bw == NSK_BLK_F || bw == NSK_BLK_BT) ? h->pool_u : h->pool_p;
-    double *xs = pc.get(true), *ys = pr.get(true);
+    const Lease xs(pc, true), ys(pr, true);
     vec_set(h->s(), pc.n, xs, 1.0);
     const DVec xv = pc.view(xs);
     for (int r = 0; r < reps; ++r) {
@@ -2727,8 +2692,6 @@ int nsk_time_op(nsk_handle h, int op, int reps, double *avg_ms, double *bytes) {
       NSK_HIP(hipEventElapsedTime(&one, e0, e1));
       ms += one;
     }
-    pc.put(xs);
-    pr.put(ys);
   } else {
     NSK_HIP(hipEventRecord(e0, h->s()));
     for (int r = 0; r < reps; ++r) f();
@@ -2738,13 +2701,7 @@ int nsk_time_op(nsk_handle h, int op, int reps, double *avg_ms, double *bytes) {
   }
   if (avg_ms) *avg_ms = (double)ms / reps;
   if (bytes) *bytes = by;
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
   h->check_sync_free();
-  h->ctx.slot_top = sl;
-  h->pool_b.put(xb);
-  h->pool_b.put(yb);
-  h->pool_b.put(zb);
   return 0;
   NSK_CATCH(h)
 }

@@ -120,6 +120,22 @@ struct DVec {
   int n = 0;
 };
 
+// Which kernel multiplies by a block.  The `_f32` forms read the fp32 copy of the values, the two `stream`
+// forms 16-bit column offsets exactly when Csr::off16 is set.
+enum class SpmvForm { csr_vector, stream, stream_f32, blk, blk_f32 };
+inline bool is_f32(SpmvForm f) { return f == SpmvForm::stream_f32 || f == SpmvForm::blk_f32; }
+inline bool is_blk(SpmvForm f) { return f == SpmvForm::blk || f == SpmvForm::blk_f32; }
+// THE rule, on a block's flags and the options.  mode: 0 y = A x, 1 y += A x, 2 y = z - A x; inner: the product of a
+// preconditioner's inner solve, the only reader of the fp32 copies.  inner32 == 1 is set on F alone, whose blocks are
+// 2 x 2 (build_blocked(2, 2)): the blocked fp32 kernel exists in that shape only.
+constexpr SpmvForm spmv_form(bool blk_ok, bool stream_ok, int inner32, bool use_stream, bool use_bsr, int mode, bool inner) {
+  if (inner && mode == 0 && inner32 == 1 && use_stream && use_bsr && blk_ok) return SpmvForm::blk_f32;
+  if (inner && mode == 0 && inner32 == 2 && use_stream && stream_ok && !(blk_ok && use_bsr)) return SpmvForm::stream_f32;
+  if (blk_ok && use_stream && use_bsr && mode == 0) return SpmvForm::blk;
+  if (stream_ok && use_stream) return SpmvForm::stream;
+  return SpmvForm::csr_vector;
+}
+
 struct Csr {  // device CSR block with host copy of the pattern
   int n_rows = 0, n_cols = 0, n_own_cols = 0;
   int64_t nnz = 0;
@@ -168,13 +184,22 @@ struct Csr {  // device CSR block with host copy of the pattern
   void refresh_f32(hipStream_t s, bool count_overflow);   // (re)convert the copy inner32 names from val, stream-ordered
   BlkView32 blk_view32() const { return BlkView32{blk_rows, n_own_cols / blk_C, blk_rowptr.p, blk_col.p, blk_val32.p}; }
   CsrView32 view32() const { return CsrView32{n_rows, n_own_cols, rowptr.p, col.p, val32.p}; }
-  // bytes the storage format the SpMV kernels actually stream holds (values, indices, descriptors) + y + x once;
-  // value_bytes 4: the fp32 copies; index16: see below
-  double format_bytes(bool blocked, int value_bytes = 8, bool index16 = false) const {
-    if (blocked && blk_ok)
-      return (double)blk_count * (4.0 + (double)value_bytes * blk_R * blk_C) + 4.0 * (blk_rows + 1.0) + 8.0 * n_rows + 8.0 * n_cols;
-    // (index16: the caller's SpMV runs the stream kernel on 16-bit offsets — 2 bytes per entry instead of 4, one base per run)
-    return (double)spmv_bytes() - (8.0 - value_bytes) * (double)nnz - (index16 ? 2.0 * (double)nnz - 4.0 * nblk : 0.0);
+  static constexpr int kToPlanEnd = -1;
+  SpmvForm spmv_form(bool use_stream, bool use_bsr, int mode = 0, bool inner = false) const {
+    return nsk::spmv_form(blk_ok, stream_ok, inner32, use_stream, use_bsr, mode, inner);
+  }
+  // The one launch of form f: runs [c0, c1) of that form's plan (c1 = kToPlanEnd: up to its last run; nothing for an
+  // empty range).  Returns
+  // what the nsk:: launcher returned (the stream kernels' VEC, the CSR-vector kernel's lanes per row; 0 for the blocked forms)
+  int spmv_launch(hipStream_t s, SpmvForm f, const double *x_own, const double *x_ghost, double *y, int mode = 0,
+                  const double *z = nullptr, int c0 = 0, int c1 = kToPlanEnd) const;
+  // bytes the storage format form f streams holds (values, indices, descriptors) + y + x once
+  double format_bytes(SpmvForm f) const {
+    const double vb = is_f32(f) ? 4.0 : 8.0;
+    if (is_blk(f)) return (double)blk_count * (4.0 + vb * blk_R * blk_C) + 4.0 * (blk_rows + 1.0) + 8.0 * n_rows + 8.0 * n_cols;
+    // (the stream forms on 16-bit offsets: 2 bytes per entry instead of 4, one base per run)
+    const bool index16 = off16.p && f != SpmvForm::csr_vector;
+    return (double)spmv_bytes() - (8.0 - vb) * (double)nnz - (index16 ? 2.0 * (double)nnz - 4.0 * nblk : 0.0);
   }
   size_t spmv_bytes() const {  // 12 nnz + 4 (rows+1) + 8 rows + 8 cols
     return (size_t)12 * nnz + 4 * ((size_t)n_rows + 1) + 8 * (size_t)n_rows + 8 * (size_t)n_cols;
@@ -342,6 +367,40 @@ struct VecPool {
   void put(double *p) { free_list.push_back(p); }
   void destroy();
   DVec view(double *p) const { return DVec{p, p + n, n}; }
+};
+
+// A vector borrowed from a pool for one scope: it goes back when the lease ends, on a throw as well.  Move-only.
+struct Lease {
+  VecPool *pool = nullptr;
+  double *p = nullptr;
+  Lease() = default;
+  Lease(VecPool &pl, bool zero) : pool(&pl), p(pl.get(zero)) {}
+  static Lease adopt(VecPool &pl, double *v) { Lease l; l.pool = &pl; l.p = v; return l; }   // v came from pl.get
+  Lease(Lease &&o) noexcept : pool(o.pool), p(o.p) { o.p = nullptr; }
+  Lease &operator=(Lease &&o) noexcept {
+    if (this != &o) { release(); pool = o.pool; p = o.p; o.p = nullptr; }
+    return *this;
+  }
+  Lease(const Lease &) = delete;
+  Lease &operator=(const Lease &) = delete;
+  ~Lease() { release(); }
+  void release() {
+    if (p) pool->put(p);
+    p = nullptr;
+  }
+  operator double *() const { return p; }
+};
+
+// Reduction slots for one scope: `k` slots from the top, and the top back where it was when the scope ends (slots taken
+// after these go with them)
+struct SlotLease {
+  Ctx &ctx;
+  const int first;
+  SlotLease(Ctx &c, int k) : ctx(c), first(c.alloc_slots(k)) {}
+  SlotLease(const SlotLease &) = delete;
+  SlotLease &operator=(const SlotLease &) = delete;
+  ~SlotLease() { ctx.slot_top = first; }
+  operator int() const { return first; }
 };
 
 // fp32 basis vectors of the inner FGMRES on F (NSK_OPT_INNER_BASIS_PRECISION = 32): n owned entries each — the

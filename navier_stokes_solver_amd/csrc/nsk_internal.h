@@ -170,6 +170,12 @@ int nsk_debug_spmv(struct nsk_handle_s *h, int form, int lpr, int mode, int misa
  * block's SpMV, the lower half of its triangular factor, the upper half}; 16: 16-bit offsets, 32: int32 column ids, 0: that
  * operation does not go through the scalar stream kernels on this handle. */
 int nsk_debug_index_width(struct nsk_handle_s *h, int b, int32_t *out3);
+/* The rule that chooses a block's SpMV kernel (nsk::spmv_form) on bare flags: no handle, no device.  Returns
+ * 0 CSR-vector, 1 stream, 2 stream on the fp32 values, 3 blocked, 4 blocked on the fp32 values.  (Declared in
+ * include/nsk.h as well: solver.EXPORTS lists it, and that list is the public header's.) */
+int nsk_debug_spmv_form(int blk_ok, int stream_ok, int inner32, int use_stream, int use_bsr, int mode, int inner);
+/* Work vectors of the handle's three pools: out6 = {allocated, free} of the velocity, the pressure and the block pool. */
+int nsk_debug_pool_counts(struct nsk_handle_s *h, int32_t *out6);
 #ifdef __cplusplus
 }
 #endif

@@ -56,6 +56,7 @@ EXPORTS = [
     "nsk_tri_apply", "nsk_amg_info", "nsk_tri_get_perm", "nsk_tri_get_value_bytes", "nsk_inner_value_bytes", "nsk_inner_basis_bytes", "nsk_inner_matrix_free", "nsk_matfree_f", "nsk_inner_spmv", "nsk_precond_vmult", "nsk_block_nnz", "nsk_get_block", "nsk_get_stats",
     "nsk_reset_stats", "nsk_get_history", "nsk_cancel", "nsk_abort_group", "nsk_assembly_set_cells", "nsk_assembly_set_simplex", "nsk_assembly_set_dirichlet", "nsk_state_set", "nsk_state_get",
     "nsk_state_save", "nsk_state_save_old", "nsk_state_update", "nsk_assemble", "nsk_scale_values", "nsk_download_rhs", "nsk_time_assemble", "nsk_time_op", "nsk_profile_begin", "nsk_profile_read", "nsk_profile_end",
+    "nsk_debug_spmv_form",
 ]
 
 
@@ -196,6 +197,17 @@ def tri_ordering_host(csr, xy=None, group=1, want_block2=False, sub_off=None):
     if rc != 0:
         raise RuntimeError("nsk_debug_tri_ordering failed")
     return perm, int(info[0]), int(info[1]), bool(info[2]), chain[:int(info[3])]
+
+
+SPMV_FORMS = ("csr_vector", "stream", "stream_f32", "blk", "blk_f32")
+
+
+def spmv_form(blk_ok, stream_ok, inner32, use_stream, use_bsr, mode, inner) -> str:
+    """Host-only: the kernel form the library's one rule picks for a block with these flags and options."""
+    L = lib()
+    L.nsk_debug_spmv_form.argtypes = [C.c_int] * 7
+    return SPMV_FORMS[L.nsk_debug_spmv_form(int(blk_ok), int(stream_ok), int(inner32), int(use_stream), int(use_bsr), int(mode),
+                                            int(inner))]
 
 
 def local_group_id(nranks: int, on_stream: bool = False) -> bytes:
@@ -434,6 +446,13 @@ class LinearSolver:
         self.L.nsk_debug_index_width.argtypes = [C.c_void_p, C.c_int, C.c_void_p]   # (nsk_internal.h: not in EXPORTS)
         self._ck(self.L.nsk_debug_index_width(self.h, blk, w.ctypes.data))
         return tuple(int(v) for v in w)
+
+    def pool_counts(self):
+        """((allocated, free) of the velocity pool, of the pressure pool, of the block pool): nsk_debug_pool_counts."""
+        w = np.zeros(6, np.int32)
+        self.L.nsk_debug_pool_counts.argtypes = [C.c_void_p, C.c_void_p]   # (nsk_internal.h: not in EXPORTS)
+        self._ck(self.L.nsk_debug_pool_counts(self.h, w.ctypes.data))
+        return tuple((int(w[2 * k]), int(w[2 * k + 1])) for k in range(3))
 
     def inner_spmv(self, blk, x):
         """y = A x with the values, kernel and row runs the inner solves use (BLK_F, BLK_S or BLK_MP); collective."""
