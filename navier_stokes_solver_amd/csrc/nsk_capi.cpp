@@ -2276,6 +2276,163 @@ int nsk_debug_spmv(nsk_handle h, int form, int lpr, int mode, int misalign, int 
   NSK_CATCH(h)
 }
 
+// test hook (nsk_internal.h): one TriSolve on the caller's CSR — analyze, numeric, n_apply applies — and what it chose
+int nsk_debug_tri(nsk_handle h, const nsk_dbg_tri_args *a, int32_t *info) {
+  NSK_TRY(h)
+  (void)hipSetDevice(h->ctx.device);
+  Ctx &c = h->ctx;
+  hipStream_t st = h->s();
+  for (int k = 0; k < 40; ++k) info[k] = 0;
+  if (!a || a->n < 1 || !a->rowptr || !a->col || !a->val || a->rowptr[0] != 0 || a->n_apply < 1 || !a->b || !a->x ||
+      !a->perm_out || !a->factor_out)
+    throw Error(-61, "nsk_debug_tri: arguments");
+  if (a->kind < 0 || a->kind > 1 || a->ordering < ORDER_NATURAL || a->ordering > ORDER_MULTICOLOR || a->group < 1)
+    throw Error(-61, "nsk_debug_tri: kind, ordering or group");
+  const int n = a->n;
+  for (int i = 0; i < n; ++i)
+    if (a->rowptr[i + 1] < a->rowptr[i]) throw Error(-58, "nsk_debug_tri: rowptr not monotone");
+  const int64_t nnz = a->rowptr[n];
+  for (int i = 0; i < n; ++i)
+    for (int k = a->rowptr[i]; k < a->rowptr[i + 1]; ++k)
+      if (a->col[k] < 0 || a->col[k] >= n || (k > a->rowptr[i] && a->col[k - 1] >= a->col[k]))
+        throw Error(-59, "nsk_debug_tri: column ids out of range or not sorted");
+  std::vector<int> sub;
+  if (a->n_sub > 1) {
+    if (!a->sub_off || a->sub_off[0] != 0 || a->sub_off[a->n_sub] != n) throw Error(-61, "nsk_debug_tri: sub-domain offsets");
+    for (int k = 0; k < a->n_sub; ++k)
+      if (a->sub_off[k + 1] < a->sub_off[k]) throw Error(-61, "nsk_debug_tri: sub-domain offsets");
+    sub.assign(a->sub_off, a->sub_off + a->n_sub + 1);
+  }
+  // the colour-ordered working vector belongs to the blocked single-launch solve (H::setup): anything else is not forced
+  if (a->x_layout != 0 && !(a->want_block2 && a->sync_free)) {
+    info[16] = 1;
+    return 1;
+  }
+
+  Csr A;   // what nsk_set_block_csr leaves of a block, as far as the analysis and numeric() read it
+  A.n_rows = A.n_cols = A.n_own_cols = n;
+  A.nnz = nnz;
+  A.h_rowptr.assign(a->rowptr, a->rowptr + n + 1);
+  A.h_col.assign(a->col, a->col + nnz);
+  A.rowptr.upload(a->rowptr, (size_t)n + 1, st);
+  A.col.upload(a->col, (size_t)nnz, st);
+  A.val.upload(a->val, (size_t)nnz, st);
+  A.present = true;
+
+  TriSolve T;
+  T.use_stream = a->use_stream != 0;
+  T.sync_free = a->sync_free != 0;
+  T.tiny_bytes = a->tiny_bytes;
+  T.host_analysis = a->host_analysis != 0;
+  T.want_index16 = a->want_index16 != 0;
+  T.want_f32 = a->want_f32 != 0;
+  T.x_layout = a->x_layout != 0 ? 1 : 0;
+  T.analyze(&c, A, a->kind, a->ordering, sub, a->want_block2 != 0, a->xy, a->group);
+  // guard words behind the intermediate vector (analyze() sized it n + 1; nothing reads its size afterwards)
+  T.y.alloc((size_t)n + 1 + kDbgBack);
+  NSK_HIP(hipMemsetAsync(T.y.p, 0xFF, sizeof(double) * T.y.n, st));
+  if (T.x_layout) {   // the colour-ordered working vector too (apply() keeps a vector that is long enough)
+    T.xc.alloc((size_t)n + 1 + kDbgBack);
+    NSK_HIP(hipMemsetAsync(T.xc.p, 0xFF, sizeof(double) * T.xc.n, st));
+  }
+  T.numeric(A.val.p);
+  NSK_HIP(hipGetLastError());
+
+  std::vector<DbgVec> bv((size_t)a->n_apply), xv((size_t)a->n_apply);
+  for (int k = 0; k < a->n_apply; ++k) {
+    bv[k].put(a->b + (size_t)k * n, (size_t)n, 0, st);
+    xv[k].put(a->x + (size_t)k * n, (size_t)n, 0, st);
+  }
+  for (int k = 0; k < a->n_apply; ++k) T.apply(bv[k].p, xv[k].p);
+  NSK_HIP(hipGetLastError());
+  int bad = 0;
+  for (int k = 0; k < a->n_apply; ++k) {
+    bad += xv[k].fetch(a->x + (size_t)k * n, c);
+    bad += bv[k].fetch(nullptr, c);
+  }
+  for (const DBuf<double> *iv : {&T.y, &T.xc}) {
+    if (iv->n != (size_t)n + 1 + kDbgBack) continue;   // (xc: only where the hook allocated it)
+    std::vector<double> tail(kDbgBack);
+    NSK_HIP(hipMemcpyAsync(tail.data(), iv->p + n + 1, sizeof(double) * kDbgBack, hipMemcpyDeviceToHost, st));
+    c.sync();
+    for (double v : tail) {
+      uint64_t bits;
+      memcpy(&bits, &v, 8);
+      bad += bits != ~0ull;
+    }
+  }
+
+  // the permutation, and the factor at the caller's positions
+  for (int i = 0; i < n; ++i) a->perm_out[i] = T.perm.empty() ? i : T.perm[i];
+  {
+    std::vector<double> fv((size_t)T.nnz);
+    std::vector<int> sp((size_t)T.nnz);
+    if (T.nnz) {
+      NSK_HIP(hipMemcpyAsync(fv.data(), T.val.p, sizeof(double) * fv.size(), hipMemcpyDeviceToHost, st));
+      NSK_HIP(hipMemcpyAsync(sp.data(), T.srcpos.p, sizeof(int) * sp.size(), hipMemcpyDeviceToHost, st));
+    }
+    c.sync();
+    uint64_t nan_bits = 0x7FF8000000000000ull;
+    double nanv;
+    memcpy(&nanv, &nan_bits, 8);
+    for (int64_t k = 0; k < nnz; ++k) a->factor_out[k] = nanv;
+    for (size_t k = 0; k < fv.size(); ++k) {
+      if (sp[k] < 0 || sp[k] >= nnz) throw Error(-62, "nsk_debug_tri: a source position outside the matrix");
+      a->factor_out[sp[k]] = fv[k];
+    }
+  }
+
+  const int path = T.last_path;
+  const bool scalar_halves = path == TRI_PATH_SF_SCALAR || path == TRI_PATH_COLOUR_SCALAR;
+  const bool halves = scalar_halves || path == TRI_PATH_SF_BLOCKED || path == TRI_PATH_COLOUR_BLOCKED;
+  info[0] = path;
+  info[1] = halves && T.f32 ? 32 : 64;
+  info[2] = !scalar_halves ? 0 : T.Loff16.p ? 16 : 32;
+  info[3] = !scalar_halves ? 0 : T.Uoff16.p ? 16 : 32;
+  info[4] = T.gmax;
+  info[5] = T.n_colors;
+  info[6] = T.n_levels_L;
+  info[7] = T.n_levels_U;
+  if (T.stream_ready || T.block2_ready) {
+    for (int half = 0; half < 2; ++half) {
+      const DBuf<int4> &D = half ? T.Udesc : T.Ldesc;
+      std::vector<int4> d(D.n);
+      if (D.n) NSK_HIP(hipMemcpyAsync(d.data(), D.p, sizeof(int4) * D.n, hipMemcpyDeviceToHost, st));
+      c.sync();
+      info[8 + 2 * half] = (int)D.n;
+      info[9 + 2 * half] = (half ? T.n_Usf : T.n_Lsf) - (int)D.n;
+      for (const int4 &r : d) {
+        info[12] = std::max(info[12], r.y - r.x);
+        info[13] = std::max(info[13], r.w - r.z);
+      }
+    }
+  }
+  if (T.sf_err.p) {
+    int e = 0;
+    NSK_HIP(hipMemcpy(&e, T.sf_err.p, sizeof(int), hipMemcpyDeviceToHost));
+    info[14] = e != 0;
+  }
+  info[15] = bad;
+  info[17] = (a->want_block2 && !T.block2_ready ? 1 : 0) | (a->want_index16 && !(scalar_halves && T.Loff16.p) ? 2 : 0) |
+             (a->want_f32 && info[1] != 32 ? 4 : 0) |
+             (a->ordering == ORDER_NATURAL && n >= 4096 && !T.ring_ready ? 8 : 0);
+  info[18] = T.lpr;
+  for (const TriSolve::Step &s : T.schedL) ++info[s.serial ? 20 : 19];
+  for (const TriSolve::Step &s : T.schedU) ++info[s.serial ? 29 : 28];
+  info[21] = T.last_tiny;
+  info[22] = T.ring_ready ? T.ringL.n_pass : 0;
+  if (a->kind == 0)
+    for (const TriSolve::Step &s : T.schedN) ++info[s.serial ? 24 : 23];
+  info[25] = T.stream_ready;
+  info[26] = T.block2_ready;
+  info[27] = T.dev_analysis;
+  info[30] = T.max_row_nnz;
+  info[31] = (int32_t)T.nnz;
+  info[32] = path == TRI_PATH_SF_BLOCKED && T.x_layout != 0;
+  return 0;
+  NSK_CATCH(h)
+}
+
 int nsk_amg_info(nsk_handle h, int shard, int level, int64_t *rows, int64_t *nnz, double *lambda_max) {
   NSK_TRY(h)
   if (h->amg_active) h->amg_ready();

@@ -166,6 +166,54 @@ struct nsk_dbg_spmv_mat {
 int nsk_debug_spmv(struct nsk_handle_s *h, int form, int lpr, int mode, int misalign, int c0, int c1,
                    const struct nsk_dbg_spmv_mat *A, const struct nsk_dbg_spmv_mat *B, double *y, const double *z,
                    const double *d, const double *dinv, int32_t *rowblk_out, int rowblk_cap, int32_t *info16);
+/* Test hook for the triangular-solve kernels (tests/test_gpu_tri_kernels.py): ONE TriSolve on the caller's square CSR,
+ * built the way the handle builds its factors — analyze, numeric, apply — so that the plan builders and the kernels are
+ * tested together; n_apply applies in a row on the one factor (the sentinel the single-launch kernels leave behind for the
+ * next apply is state).  Device and stream of the handle.
+ * In: the matrix (sorted rows, every column < n, a diagonal entry in every row), kind 0 ILU(0) / 1 SGS, ordering 0 the
+ * caller's / 1 multicolour, sub_off (n_sub + 1 offsets of emulated sub-domains, or null), xy (2 doubles per row, or null)
+ * and group (members per line group), and what the handle sets on a factor from its options: want_block2, use_stream,
+ * sync_free, tiny_bytes, host_analysis, want_index16, want_f32, x_layout (NSK_IOPT_TRI_X_LAYOUT: 0 or 2; the colour-ordered
+ * vector exists for the blocked single-launch solve alone — asked for without want_block2 and sync_free the hook returns 1,
+ * info[16] = 1, and launches nothing).  b: n_apply right-hand sides of n doubles; x: as many vectors, in (what the
+ * kernels find there) and out.
+ * Out: x per apply; perm_out[new] = old (the identity in the caller's order); factor_out: the combined factor `val` at the
+ * positions of the CALLER's entries (through srcpos) — ILU(0): L below the diagonal (unit diagonal not stored), U on and
+ * above it; SGS: the matrix' own values — with NaN at the entries the analysis dropped (cross-shard columns).
+ * b, x (one allocation per apply each) sit between guard words, all bits set; the factor's intermediate vector y and
+ * the colour-ordered working vector xc, which the kernels address from the start of their allocations, have guard words
+ * BEHIND them only (a write in front of either is not seen).
+ * info40: [0] the branch apply() took (TRI_PATH_* of nsk_tri.hpp: 1 scalar single-launch, 2 scalar per-colour, 3 blocked
+ * single-launch, 4 blocked per-colour, 5 ring, 6 level walker), [1] bits of the off-diagonal values that branch reads
+ * (64 / 32), [2] [3] index width of the lower / upper half (16 / 32; 0: the branch reads no scalar halves), [4] gmax,
+ * [5] colours, [6] [7] levels of L / U, [8] runs and [9] padding runs of the lower half's single-launch grid, [10] [11] of
+ * the upper half's, [12] rows and [13] entries (blocks for the blocked factor) of the longest run of either half,
+ * [14] sf_err was raised, [15] guard words that changed, [16] why the hook refused (0: it did not), [17] what was asked
+ * for and not granted: bit 0 want_block2 (no node structure, odd n, the caller's order), bit 1 want_index16 (a run spans
+ * 65 536 columns or more, or no scalar halves), bit 2 want_f32 (the branch reads the double factor), bit 3 the ring (the
+ * caller's order and 4096 rows or more — the hook's reading of when analyze() tries — and ring_ready false), [18] lanes per row of the walker's level steps, [19] level steps and
+ * [20] serial steps of the walker's schedule of the lower half, [28] [29] of the upper half (what the walker launches when
+ * it is the branch taken), [21] the factor is below tiny_bytes (TriSolve::last_tiny, recorded by apply()), [22] passes of the lower ring (0: no ring was built),
+ * [23] level and [24] serial launches of the ILU(0) factorisation (0 for SGS), [25] stream_ready, [26] block2_ready,
+ * [27] the symbolic set-up ran on the device (TriSolve::dev_analysis, recorded by analyze()), [30] longest row of the restricted pattern, [31] entries kept, [32] the
+ * blocked single-launch solve ran on the colour-ordered working vector (PERMX of tri_blk_sf_kernel); the rest 0.
+ * 0, 1 (refused) or a negative error code (-31 no diagonal, -32 a row above 448 entries, ...). */
+struct nsk_dbg_tri_args {
+  int32_t n, kind, ordering, n_sub;
+  const int32_t *rowptr, *col;
+  const double *val;
+  const int32_t *sub_off;
+  const double *xy;
+  int32_t group, want_block2, use_stream, sync_free;
+  double tiny_bytes;
+  int32_t host_analysis, want_index16, want_f32, x_layout;
+  int32_t n_apply, pad_;
+  const double *b;
+  double *x;
+  int32_t *perm_out;
+  double *factor_out;
+};
+int nsk_debug_tri(struct nsk_handle_s *h, const struct nsk_dbg_tri_args *a, int32_t *info40);
 /* Which index width the scalar stream kernels of block b (NSK_BLK_S or NSK_BLK_MP) run on after the set-up: out3 = {the
  * block's SpMV, the lower half of its triangular factor, the upper half}; 16: 16-bit offsets, 32: int32 column ids, 0: that
  * operation does not go through the scalar stream kernels on this handle. */

@@ -422,6 +422,7 @@ void TriSolve::analyze(Ctx *c, const Csr &A, int kind_, int ordering_, const std
   // builds no array of the factor's size.  host_analysis (NSK_IOPT_HOST_ANALYSIS): the host path below (what the tests compare with)
   const bool dev = !host_analysis && !perm.empty() && gmax == 1 && O.identity && A.rowptr.p && A.col.p && (int64_t)A.nnz == (int64_t)nnz &&
                    maxw <= 448 && n > 0;
+  dev_analysis = dev;
   hipStream_t s = ctx->stream;
   bool missing_diag = false;
   if (dev) {
@@ -1089,6 +1090,7 @@ void TriSolve::apply(const double *b, double *x) {
   // Tiny factors (a few MB: they sit in one XCD's L2) are latency-bound on the ~5 us per level launch:
   // one 1024-thread workgroup walking all levels with __syncthreads in between is faster there.
   const bool tiny = (double)nnz * 12.0 < tiny_bytes && !schedL.empty();
+  last_tiny = tiny;
   // y stays armed with the sentinel only while consecutive applies go through the single-launch CSR kernels
   if (!(sync_free && use_stream && !tiny && (stream_ready || block2_ready))) sf_armed = false;
   if (sync_free && use_stream && !tiny && stream_ready) {
@@ -1099,6 +1101,7 @@ void TriSolve::apply(const double *b, double *x) {
     }
     // the lower half arms x for the upper half, the upper half re-arms y for the next call: no fill launches
     if (!sf_armed) { vec_fill_sentinel(s, n, y.p); sf_armed = true; }
+    last_path = TRI_PATH_SF_SCALAR;
     auto run = [&](const auto &L, const auto &U, const auto &cl, const auto &cu) {
       tri_stream_syncfree(s, L, n_Lsf, 1, kind, kStreamNnz, 0, dinv.p, d_perm.p, b, nullptr, y.p, x, sf_err.p, sf_dbg, cl);
       tri_stream_syncfree(s, U, n_Usf, 0, kind, kStreamNnz, sf_fault ? 1 : 0, dinv.p, d_perm.p, nullptr, y.p, x, y.p, sf_err.p,
@@ -1114,6 +1117,7 @@ void TriSolve::apply(const double *b, double *x) {
   }
   if (stream_ready && use_stream && !tiny && !grouped) {   // (line groups: the per-colour kernels do not know them)
     // x doubles as the intermediate vector: rows not yet solved hold L^-1 b, solved rows hold the result
+    last_path = TRI_PATH_COLOUR_SCALAR;
     auto run = [&](const auto &L, const auto &U) {
       for (int c = 0; c < n_colors; ++c) tri_stream_level(s, L, LB[c], LB[c + 1], 1, kind, kStreamNnz, dinv.p, d_perm.p, b, x);
       for (int c = n_colors - 1; c >= 0; --c) tri_stream_level(s, U, UB[c], UB[c + 1], 0, kind, kStreamNnz, dinv.p, d_perm.p, nullptr, x);
@@ -1132,7 +1136,8 @@ void TriSolve::apply(const double *b, double *x) {
     // lower half into y, upper half into x (xc); each half is ONE launch.  The lower half arms the upper half's
     // vector with the sentinel, the upper half re-arms y for the next call: no fill launches
     if (!sf_armed) { vec_fill_sentinel(s, n, y.p); sf_armed = true; }
-    if (x_layout && xc.n != (size_t)n + 1) xc.alloc((size_t)n + 1);
+    if (x_layout && xc.n < (size_t)n + 1) xc.alloc((size_t)n + 1);
+    last_path = TRI_PATH_SF_BLOCKED;
     auto run = [&](const auto &L, const auto &U, const auto &cl, const auto &cu) {
       if (x_layout) {  // colour-ordered working vectors y, xc; the upper half also writes the caller-order result
         tri_blk_syncfree(s, L, n_Lsf, 1, kind, 1, 0, intra.p, permn.p, b, nullptr, y.p, nullptr, xc.p, sf_err.p, cl);
@@ -1153,6 +1158,7 @@ void TriSolve::apply(const double *b, double *x) {
   if (block2_ready && x_layout && use_stream && !tiny && !grouped)
     throw Error(-33, "the colour-ordered layout of the blocked factor needs the single-launch solves");
   if (block2_ready && use_stream && !tiny && !grouped) {
+    last_path = TRI_PATH_COLOUR_BLOCKED;
     auto run = [&](const auto &L, const auto &U) {
       for (int c = 0; c < n_colors; ++c) tri_blk_level(s, L, LB[c], LB[c + 1], 1, kind, intra.p, permn.p, b, x);
       for (int c = n_colors - 1; c >= 0; --c) tri_blk_level(s, U, UB[c], UB[c + 1], 0, kind, intra.p, permn.p, nullptr, x);
@@ -1174,6 +1180,7 @@ void TriSolve::apply(const double *b, double *x) {
                           {(size_t)Rg.n_ent * 12, (size_t)n * 16, (size_t)Rg.n_pass * kRingWaves * 16, 0, 0, 0}};
       mem_touch(s, R, touch_sink.p);
     };
+    last_path = TRI_PATH_RING;
     vec_gather(s, n, ringL.rowid.p, b, ringL.own.p);              // the right-hand side in the lower half's position order
     touch(ringL);
     tri_ring(s, ringL.view(), 1, kind, ringL.own.p, ringU.own.p);   // (its result lands in the upper half's order)
@@ -1184,6 +1191,7 @@ void TriSolve::apply(const double *b, double *x) {
     ctx->st.tri_bytes += (double)apply_bytes();
     return;
   }
+  last_path = TRI_PATH_WALKER;
   const TriView T = view();
   for (const Step &st : schedL) {
     if (st.serial) tri_lower_serial(s, T, kind, lvlL_ptr.p, lvlL_rows.p, st.l0, st.l1, b, y.p);

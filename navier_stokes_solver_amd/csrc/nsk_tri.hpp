@@ -18,6 +18,9 @@
 namespace nsk {
 
 enum { ORDER_NATURAL = 0, ORDER_MULTICOLOR = 1 };
+// the branch TriSolve::apply took (TriSolve::last_path; what the test hook nsk_debug_tri reports)
+enum { TRI_PATH_NONE = 0, TRI_PATH_SF_SCALAR = 1, TRI_PATH_COLOUR_SCALAR = 2, TRI_PATH_SF_BLOCKED = 3, TRI_PATH_COLOUR_BLOCKED = 4,
+       TRI_PATH_RING = 5, TRI_PATH_WALKER = 6 };
 
 // greedy distance-1 colouring of the graph of G + G^T (CSR grp/gcol, nv vertices, visited in natural order);
 // returns the number of colours
@@ -140,6 +143,9 @@ struct TriSolve {
   // bytes per stored off-diagonal value of what apply() streams: 4 for single-precision halves in use, else 8
   int value_bytes() const { return f32 && halves_in_use() ? 4 : 8; }
   void apply(const double *b, double *x);          // x = M^{-1} b, caller's ordering
+  int last_path = TRI_PATH_NONE;                   // TRI_PATH_*: the branch the last apply() took (host bookkeeping only)
+  bool last_tiny = false;                          // the last apply() found the factor below tiny_bytes
+  bool dev_analysis = false;                       // analyze() built the permuted pattern and the halves on the device
   TriView view() const { return TriView{n, rowptr.p, diag.p, col.p, val.p, perm.empty() ? nullptr : d_perm.p}; }
   // 12 nnz_factor + 4 (rows + 1) * 2 + 16 rows
   size_t apply_bytes() const { return (size_t)12 * nnz + 8 * ((size_t)n + 1) + 16 * (size_t)n; }

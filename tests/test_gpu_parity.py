@@ -3,7 +3,8 @@ CPU oracle on the same inputs.  Tolerances (f64 everywhere, SURVEY 8c tier 2):
   SpMV / axpy-like ops  : max |a - b| <= 1e-13 max |b| over the vector (same products, different summation tree;
                           row by row against exact sums: test_gpu_spmv_kernels.py)
   dots / norms           : <= 1e-12 relative (reduction order differs)
-  ILU(0)/SGS applies     : <= 1e-11 relative (factorisation + two solves, FMA contraction on the GPU)
+  ILU(0)/SGS applies     : <= 1e-11 relative (factorisation + two solves, FMA contraction on the GPU;
+                          per position of the factor and row by row against exact substitution: test_gpu_tri_kernels.py)
   full solves            : true residual <= tol, and ||x_gpu - x_oracle||_inf / ||x_oracle||_inf <= 1e-7
                            at tol = 1e-12 (both are iterates of a Krylov method stopped on the residual)
 """
