@@ -9,7 +9,10 @@
 #include <chrono>
 #include <cmath>
 
+#include <cstring>
+
 #include "nsk_amg_kernels.h"
+#include "nsk_internal.h"
 
 namespace nsk {
 namespace {
@@ -57,6 +60,43 @@ double now_ms() {
 
 amgk::Mat mat(const Csr &A) { return amgk::Mat{A.n_rows, A.n_cols, A.rowptr.p, A.col.p, A.val.p}; }
 
+// Device arrays of the test hook (debug_amg): each an allocation of its own at its exact size, kGuard bytes with all bits
+// set in front of it and behind it.
+struct Guarded {
+  static constexpr size_t kGuard = 256;   // (the array keeps the alignment hipMalloc gives)
+  struct Item {
+    DBuf<char> buf;
+    size_t bytes;
+  };
+  hipStream_t s;
+  std::vector<Item> items;
+  explicit Guarded(hipStream_t st) : s(st) {}
+  // count elements, from h (null: all bits set)
+  template <class T>
+  T *put(const T *h, size_t count) {
+    items.emplace_back();
+    Item &it = items.back();
+    it.bytes = count * sizeof(T);
+    it.buf.alloc(it.bytes + 2 * kGuard);
+    NSK_HIP(hipMemsetAsync(it.buf.p, 0xFF, it.buf.n, s));
+    T *p = reinterpret_cast<T *>(it.buf.p + kGuard);
+    if (h && it.bytes) NSK_HIP(hipMemcpyAsync(p, h, it.bytes, hipMemcpyHostToDevice, s));
+    return p;
+  }
+  // 32-bit guard words that no longer hold all bits (a word is counted once however many of its bytes changed)
+  int changed() {
+    int bad = 0;
+    std::vector<unsigned char> g(2 * kGuard);
+    for (Item &it : items) {
+      NSK_HIP(hipMemcpyAsync(g.data(), it.buf.p, kGuard, hipMemcpyDeviceToHost, s));
+      NSK_HIP(hipMemcpyAsync(g.data() + kGuard, it.buf.p + kGuard + it.bytes, kGuard, hipMemcpyDeviceToHost, s));
+      NSK_HIP(hipStreamSynchronize(s));
+      for (size_t w = 0; w < 2 * kGuard; w += 4) bad += !(g[w] == 0xFF && g[w + 1] == 0xFF && g[w + 2] == 0xFF && g[w + 3] == 0xFF);
+    }
+    return bad;
+  }
+};
+
 // Scratch of the set-up.  Work arrays of a level come from an arena that lives across set-ups (a Newton run rebuilds
 // the hierarchy before every solve, NSSolverStationary.cpp:621-626, always with the same sizes): the first set-up
 // allocates what it needs piece by piece and records the largest level's total, the following ones take slices.
@@ -69,12 +109,14 @@ struct Scratch {
   DBuf<long long> total;
   DBuf<int> counters;   // [0] undecided rows, [1] error word of the row products
   int rounds = 0;       // independent-set rounds so far (NSK_AMG_TIMING)
+  Guarded *exact = nullptr;   // test hook: every take() is an allocation of its own at its exact size between guard words
   Scratch(Ctx *c, DBuf<char> &arena_, size_t &want_) : ctx(c), arena(arena_), want(want_) {
     total.alloc(1);
     counters.alloc(2);
   }
   template <class T>
   T *take(size_t count) {
+    if (exact) return exact->put<T>(nullptr, count);
     const size_t bytes = (std::max<size_t>(count, 1) * sizeof(T) + 255) & ~(size_t)255;
     level_total += bytes;
     if (top + bytes <= arena.n) {
@@ -267,6 +309,329 @@ int64_t device_product_pattern(Ctx *ctx, const Csr &A, const Csr &B, DBuf<int> &
   if (S.read_counter(1) != 0) throw Error(-84, "device_product_pattern: the fill found a row its count had not");
   ctx->sync();
   return pl.nnz;
+}
+
+// ---------------------------------------------------------------- test hook (nsk_internal.h: nsk_debug_amg)
+namespace {
+void dbg_check_mat(const nsk_dbg_amg_mat &M, bool need_val) {
+  if (M.n_rows < 1 || M.n_cols < 1 || !M.rowptr || (need_val && !M.val)) throw Error(-61, "nsk_debug_amg: matrix shape");
+  if (M.rowptr[0] != 0) throw Error(-58, "nsk_debug_amg: rowptr does not start at 0");
+  for (int i = 0; i < M.n_rows; ++i)
+    if (M.rowptr[i + 1] < M.rowptr[i]) throw Error(-58, "nsk_debug_amg: rowptr not monotone");
+  const int64_t nnz = M.rowptr[M.n_rows];
+  if (nnz > 0 && !M.col) throw Error(-61, "nsk_debug_amg: matrix shape");
+  for (int64_t k = 0; k < nnz; ++k)
+    if (M.col[k] < 0 || M.col[k] >= M.n_cols) throw Error(-59, "nsk_debug_amg: column id out of range");
+}
+amgk::Mat dbg_put_mat(Guarded &G, const nsk_dbg_amg_mat &M) {
+  const size_t nnz = (size_t)M.rowptr[M.n_rows];
+  return amgk::Mat{M.n_rows, M.n_cols, G.put(M.rowptr, (size_t)M.n_rows + 1), G.put(M.col, nnz), G.put(M.val, nnz)};
+}
+// a Csr over arrays it does not own (aggregate() and transpose() take a Csr)
+struct BorrowedCsr {
+  Csr A;
+  BorrowedCsr(const amgk::Mat &M, int64_t nnz) {
+    A.n_rows = M.n_rows;
+    A.n_cols = A.n_own_cols = M.n_cols;
+    A.nnz = nnz;
+    A.rowptr.p = const_cast<int *>(M.rp);
+    A.col.p = const_cast<int *>(M.col);
+    A.val.p = const_cast<double *>(M.val);
+    A.present = true;
+  }
+  ~BorrowedCsr() { A.rowptr.p = nullptr; A.col.p = nullptr; A.val.p = nullptr; }
+};
+}  // namespace
+
+int debug_amg(Ctx *ctx, const nsk_dbg_amg_args *a, int32_t *info) {
+  hipStream_t s = ctx->stream;
+  for (int k = 0; k < 16; ++k) info[k] = 0;
+  if (!a || !a->out64) throw Error(-61, "nsk_debug_amg: arguments");
+  for (int k = 0; k < 8; ++k) a->out64[k] = k >= 4 && k < 7 ? -1 : 0;
+  const int op = a->op;
+  if (op < NSK_DBG_AMG_SCAN || op > NSK_DBG_AMG_START_VECTOR) throw Error(-65, "nsk_debug_amg: unknown op");
+  const bool uses_A = op != NSK_DBG_AMG_SCAN && op != NSK_DBG_AMG_MIS_DECIDE && op != NSK_DBG_AMG_ROOTS &&
+                      op != NSK_DBG_AMG_AGG_WEIGHTS && op != NSK_DBG_AMG_START_VECTOR;
+  const bool graph = op == NSK_DBG_AMG_MIS_PULL || op == NSK_DBG_AMG_MIS_MARK || op == NSK_DBG_AMG_JOIN;
+  if (uses_A) dbg_check_mat(a->A, true);
+  const int n = uses_A ? a->A.n_rows : a->n;
+  if (n < 0) throw Error(-61, "nsk_debug_amg: n");
+  const int64_t nnz = uses_A ? a->A.rowptr[n] : 0;
+  const size_t fwords = uses_A ? amgk::flag_words((long)nnz, n) : 0;
+  const bool square = op == NSK_DBG_AMG_BLOCK || op == NSK_DBG_AMG_DIAG || op == NSK_DBG_AMG_STRENGTH || graph ||
+                      op == NSK_DBG_AMG_AGGREGATE;
+  if (square && a->A.n_cols != n) throw Error(-61, "nsk_debug_amg: a square matrix");
+  if ((op == NSK_DBG_AMG_STRENGTH || graph) && (a->flag_words != (int64_t)fwords || !(op == NSK_DBG_AMG_STRENGTH ? (const void *)a->flag_out : (const void *)a->flag)))
+    throw Error(-61, "nsk_debug_amg: flag words");
+  if (graph && !a->key) throw Error(-61, "nsk_debug_amg: key");
+
+  Guarded G(s);
+  DBuf<char> no_arena;
+  size_t want = 0;
+  Scratch S(ctx, no_arena, want);
+  S.exact = &G;
+  const amgk::Tally t0 = amgk::tally();
+  struct Out {
+    void *host;
+    const void *dev;
+    size_t bytes;
+  };
+  std::vector<Out> outs;
+  auto out = [&](auto *host, const auto *dev, size_t count) {
+    if (host && count) outs.push_back(Out{(void *)host, (const void *)dev, count * sizeof(*host)});
+  };
+  auto finish = [&]() {
+    for (const Out &o : outs) NSK_HIP(hipMemcpyAsync(o.host, o.dev, o.bytes, hipMemcpyDeviceToHost, s));
+    ctx->sync();
+    NSK_HIP(hipGetLastError());
+    info[0] = G.changed();
+    const amgk::Tally &t1 = amgk::tally();
+    info[5] = (int32_t)(t1.pull1_stamped - t0.pull1_stamped);
+    info[6] = (int32_t)(t1.pull1_all - t0.pull1_all);
+    info[7] = (int32_t)(t1.pull2 - t0.pull2);
+    info[8] = (int32_t)(t1.join[1] - t0.join[1]);
+    info[9] = (int32_t)(t1.join[0] - t0.join[0]);
+    for (int p = 0; p < 2; ++p)
+      for (int t = 0; t < 3; ++t) {
+        info[10 + t] += (int32_t)(t1.product[p][t][0] - t0.product[p][t][0]);
+        info[13 + t] += (int32_t)(t1.product[p][t][1] - t0.product[p][t][1]);
+      }
+    info[4] = (info[10] + info[11] + info[12] ? 1 : 0) | (info[13] + info[14] + info[15] ? 2 : 0);
+  };
+
+  try {
+    switch (op) {
+      case NSK_DBG_AMG_SCAN: {
+        if (!a->i_in && n > 0) throw Error(-61, "nsk_debug_amg: SCAN input");
+        const int *in = G.put(a->i_in, (size_t)n);
+        int *o = G.put<int>(nullptr, (size_t)n + 1);
+        out(a->i_out, o, (size_t)n + 1);
+        out(a->out64, S.total.p, 1);
+        (void)S.scan(n, in, o);
+        break;
+      }
+      case NSK_DBG_AMG_BLOCK: {
+        const int r0 = a->r0, r1 = a->r1;
+        if (r0 < 0 || r1 < r0 || r1 > n) throw Error(-61, "nsk_debug_amg: BLOCK range");
+        const amgk::Mat M = dbg_put_mat(G, a->A);
+        int *len = S.take<int>((size_t)(r1 - r0) + 1);
+        amgk::block_count(s, M, r0, r1, len);
+        int *rp = G.put<int>(nullptr, (size_t)(r1 - r0) + 1);
+        const int64_t bn = S.scan(r1 - r0, len, rp);
+        if (bn > a->out_cap) throw Error(-61, "nsk_debug_amg: out_cap");
+        int *col = G.put<int>(nullptr, (size_t)bn);
+        double *val = G.put<double>(nullptr, (size_t)bn);
+        amgk::block_fill(s, M, r0, r1, rp, col, val);
+        a->out64[0] = bn;
+        out(a->out_rp, rp, (size_t)(r1 - r0) + 1);
+        out(a->out_col, col, (size_t)bn);
+        out(a->out_val, val, (size_t)bn);
+        break;
+      }
+      case NSK_DBG_AMG_DIAG: {
+        const amgk::Mat M = dbg_put_mat(G, a->A);
+        double *ad = G.put<double>(nullptr, (size_t)n), *dinv = G.put<double>(nullptr, (size_t)n);
+        amgk::diag(s, M, ad, dinv);
+        out(a->d_out, ad, (size_t)n);
+        out(a->d_out2, dinv, (size_t)n);
+        break;
+      }
+      case NSK_DBG_AMG_STRENGTH: {
+        if (!a->ad) throw Error(-61, "nsk_debug_amg: ad");
+        const amgk::Mat M = dbg_put_mat(G, a->A);
+        const double *ad = G.put(a->ad, (size_t)n);
+        uint16_t *flag = G.put<uint16_t>(nullptr, fwords);
+        uint64_t *key = G.put<uint64_t>(nullptr, (size_t)n);
+        int *agg = G.put<int>(nullptr, (size_t)n);
+        S.zero_counter(0);
+        amgk::strength(s, M, ad, a->threshold, flag, key, agg, S.counters.p);
+        a->out64[0] = S.read_counter(0);
+        out(a->flag_out, flag, fwords);
+        out(a->k_out, key, (size_t)n);
+        out(a->i_out, agg, (size_t)n);
+        break;
+      }
+      case NSK_DBG_AMG_MIS_PULL: {
+        if ((a->pass != 1 && a->pass != 2) || !a->i_in || !a->k_out || (a->pass == 2 && !a->key2))
+          throw Error(-61, "nsk_debug_amg: MIS_PULL arguments");
+        const amgk::Mat M = dbg_put_mat(G, a->A);
+        const uint16_t *flag = G.put(a->flag, fwords);
+        const uint64_t *key = G.put(a->key, (size_t)n);
+        const int *need = G.put(a->i_in, (size_t)n);
+        const uint64_t *in = a->pass == 1 ? key : G.put(a->key2, (size_t)n);   // (pass 1 reads the keys, as the set-up's does)
+        uint64_t *o = G.put((const uint64_t *)a->k_out, (size_t)n);
+        amgk::mis_pull(s, M, flag, a->pass, key, need, a->stamp, in, o);
+        out(a->k_out, o, (size_t)n);
+        break;
+      }
+      case NSK_DBG_AMG_MIS_DECIDE: {
+        if (!a->key || !a->key2 || n < 1) throw Error(-61, "nsk_debug_amg: MIS_DECIDE arguments");
+        for (int i = 0; i < n; ++i)   // (the row a found key names is read)
+          if ((a->key[i] >> 62) == 1 && (int64_t)(a->key2[i] & 0x7fffffffu) >= n) throw Error(-59, "nsk_debug_amg: a key names no row");
+        const uint64_t *key = G.put(a->key, (size_t)n), *key2 = G.put(a->key2, (size_t)n);
+        uint64_t *o = G.put<uint64_t>(nullptr, (size_t)n);
+        S.zero_counter(0);
+        amgk::mis_decide(s, n, key, key2, o, S.counters.p);
+        a->out64[0] = S.read_counter(0);
+        out(a->k_out, o, (size_t)n);
+        break;
+      }
+      case NSK_DBG_AMG_MIS_MARK: {
+        if (!a->i_in) throw Error(-61, "nsk_debug_amg: need");
+        const amgk::Mat M = dbg_put_mat(G, a->A);
+        const uint16_t *flag = G.put(a->flag, fwords);
+        const uint64_t *key = G.put(a->key, (size_t)n);
+        int *need = G.put(a->i_in, (size_t)n);
+        amgk::mis_mark(s, M, flag, key, a->stamp, need);
+        out(a->i_out, need, (size_t)n);
+        break;
+      }
+      case NSK_DBG_AMG_ROOTS: {
+        if (!a->key || !a->i_in || n < 1) throw Error(-61, "nsk_debug_amg: ROOTS arguments");
+        const uint64_t *key = G.put(a->key, (size_t)n);
+        int *agg = G.put(a->i_in, (size_t)n);
+        int *is_root = S.take<int>((size_t)n), *scan = S.take<int>((size_t)n + 1);
+        amgk::root_flags(s, n, key, is_root);
+        a->out64[0] = S.scan(n, is_root, scan);
+        amgk::root_ids(s, n, key, scan, a->first, agg);
+        out(a->i_out, agg, (size_t)n);
+        break;
+      }
+      case NSK_DBG_AMG_JOIN: {
+        if (!a->i_in || !a->i_out) throw Error(-61, "nsk_debug_amg: JOIN arguments");
+        const amgk::Mat M = dbg_put_mat(G, a->A);
+        const uint16_t *flag = G.put(a->flag, fwords);
+        const uint64_t *key = G.put(a->key, (size_t)n);
+        const int *agg_in = G.put(a->i_in, (size_t)n);
+        int *agg_out = G.put((const int *)a->i_out, (size_t)n);
+        amgk::join(s, M, flag, key, a->roots_only != 0, agg_in, agg_out);
+        out(a->i_out, agg_out, (size_t)n);
+        break;
+      }
+      case NSK_DBG_AMG_AGG_WEIGHTS: {
+        const int nc = a->nc;
+        if (!a->i_in || n < 1 || nc < 1) throw Error(-61, "nsk_debug_amg: AGG_WEIGHTS arguments");
+        for (int i = 0; i < n; ++i)
+          if (a->i_in[i] >= nc) throw Error(-59, "nsk_debug_amg: aggregate id out of range");
+        const int *agg = G.put(a->i_in, (size_t)n);
+        int *count = G.put<int>(nullptr, (size_t)nc);
+        NSK_HIP(hipMemsetAsync(count, 0, sizeof(int) * (size_t)nc, s));
+        amgk::agg_sizes(s, n, agg, count);
+        double *pw = G.put<double>(nullptr, (size_t)nc);
+        amgk::agg_weights(s, nc, count, pw);
+        out(a->i_out, count, (size_t)nc);
+        out(a->d_out, pw, (size_t)nc);
+        break;
+      }
+      case NSK_DBG_AMG_AGGREGATE: {
+        if (!a->ad) throw Error(-61, "nsk_debug_amg: ad");
+        const amgk::Mat M = dbg_put_mat(G, a->A);
+        BorrowedCsr A(M, nnz);
+        const double *ad = G.put(a->ad, (size_t)n);
+        int *agg = nullptr;
+        double *pw = nullptr;
+        const int nc = aggregate(S, A.A, ad, agg, pw);
+        a->out64[0] = nc;
+        a->out64[1] = S.rounds;
+        a->out64[2] = amgk::tally().pull1_stamped - t0.pull1_stamped;
+        out(a->i_out, agg, (size_t)n);
+        if (nc > 0) out(a->d_out, pw, (size_t)nc);
+        break;
+      }
+      case NSK_DBG_AMG_PRODUCT:
+      case NSK_DBG_AMG_PRODUCT_COUNT: {
+        const int product = a->product, ft = a->first_tier;
+        if (product < 0 || product > 1 || ft < 0 || ft > 2) throw Error(-61, "nsk_debug_amg: product or tier");
+        amgk::RowProduct P{};
+        if (product == 0) {
+          dbg_check_mat(a->B, true);
+          if (a->B.n_rows != a->A.n_cols) throw Error(-61, "nsk_debug_amg: shapes of A and B");
+          P.A = dbg_put_mat(G, a->A);
+          P.B = dbg_put_mat(G, a->B);
+        } else {
+          const int nc = a->nc;
+          if (a->A.n_cols != n || nc < 1 || !a->i_in || !a->pw || !a->dinv) throw Error(-61, "nsk_debug_amg: prolongator arguments");
+          for (int i = 0; i < n; ++i)
+            if (a->i_in[i] >= nc) throw Error(-59, "nsk_debug_amg: aggregate id out of range");
+          P.A = dbg_put_mat(G, a->A);
+          P.agg = G.put(a->i_in, (size_t)n);
+          P.pw = G.put(a->pw, (size_t)nc);
+          P.dinv = G.put(a->dinv, (size_t)n);
+          P.c = a->c;
+        }
+        info[1] = product;
+        if (op == NSK_DBG_AMG_PRODUCT_COUNT) {
+          int *len = G.put<int>(nullptr, (size_t)n + 1);
+          S.zero_counter(1);
+          amgk::product_count(s, P, product, ft, len, S.counters.p + 1);
+          a->out64[0] = S.read_counter(1);
+          out(a->i_out, len, (size_t)n);
+          info[2] = ft == 0 ? 8 : ft == 1 ? 16 : 64;
+          info[3] = ft == 0 ? 64 : ft == 1 ? 128 : 512;
+          break;
+        }
+        for (int t = ft; t <= 2; ++t) {   // the error word of every tier, each from a count of its own
+          int *len = G.put<int>(nullptr, (size_t)n + 1);
+          S.zero_counter(1);
+          amgk::product_count(s, P, product, t, len, S.counters.p + 1);
+          a->out64[4 + t] = S.read_counter(1);
+        }
+        int *rp = G.put<int>(nullptr, (size_t)n + 1);
+        const ProductPlan pl = product_rows(S, P, product, ft, rp);
+        a->out64[0] = pl.nnz;
+        a->out64[1] = pl.tier;
+        if (pl.nnz > a->out_cap) throw Error(-61, "nsk_debug_amg: out_cap");
+        int *col = G.put<int>(nullptr, (size_t)pl.nnz);
+        double *val = G.put<double>(nullptr, (size_t)pl.nnz);
+        S.zero_counter(1);
+        amgk::product_fill(s, P, product, pl.tier, rp, col, val, S.counters.p + 1);
+        a->out64[2] = S.read_counter(1);
+        info[2] = pl.tier == 0 ? 8 : pl.tier == 1 ? 16 : 64;
+        info[3] = pl.tier == 0 ? 64 : pl.tier == 1 ? 128 : 512;
+        out(a->out_rp, rp, (size_t)n + 1);
+        out(a->out_col, col, (size_t)pl.nnz);
+        out(a->out_val, val, (size_t)pl.nnz);
+        if (a->out64[2] != 0) throw Error(-84, "AMG set-up: the fill of a row product found a row its count had not");
+        break;
+      }
+      case NSK_DBG_AMG_TRANSPOSE: {
+        const amgk::Mat M = dbg_put_mat(G, a->A);
+        BorrowedCsr A(M, nnz);
+        if (nnz > a->out_cap) throw Error(-61, "nsk_debug_amg: out_cap");
+        Csr T;
+        transpose(S, A.A, T);
+        a->out64[0] = T.nnz;
+        // (the result leaves the device here: T is gone when finish() runs)
+        if (a->out_rp) NSK_HIP(hipMemcpyAsync(a->out_rp, T.rowptr.p, sizeof(int) * ((size_t)T.n_rows + 1), hipMemcpyDeviceToHost, s));
+        if (a->out_col && T.nnz) NSK_HIP(hipMemcpyAsync(a->out_col, T.col.p, sizeof(int) * (size_t)T.nnz, hipMemcpyDeviceToHost, s));
+        if (a->out_val && T.nnz) NSK_HIP(hipMemcpyAsync(a->out_val, T.val.p, sizeof(double) * (size_t)T.nnz, hipMemcpyDeviceToHost, s));
+        ctx->sync();
+        break;
+      }
+      case NSK_DBG_AMG_ROWS_SORT: {
+        if (nnz > a->out_cap) throw Error(-61, "nsk_debug_amg: out_cap");
+        const amgk::Mat M = dbg_put_mat(G, a->A);
+        int *col = G.put<int>(nullptr, (size_t)nnz);
+        double *val = G.put<double>(nullptr, (size_t)nnz);
+        amgk::rows_sort(s, n, M.rp, M.col, M.val, col, val);
+        out(a->out_col, col, (size_t)nnz);
+        out(a->out_val, val, (size_t)nnz);
+        break;
+      }
+      case NSK_DBG_AMG_START_VECTOR: {
+        double *x = G.put<double>(nullptr, (size_t)n);
+        amgk::start_vector(s, n, x);
+        out(a->d_out, x, (size_t)n);
+        break;
+      }
+    }
+  } catch (const Error &e) {
+    if (e.code == -61 || e.code == -58 || e.code == -59) throw;   // (refused on the host: nothing ran)
+    finish();   // what the operation left behind still comes back: the 64-bit total of a scan, the guard words
+    throw;
+  }
+  finish();
+  return 0;
 }
 
 // lambda = kEigBoost x ||(D^-1 A)^k x0|| / ||(D^-1 A)^(k-1) x0|| after kEigIts steps, x0(i) = start_entry(i), on the device

@@ -22,6 +22,8 @@
 
 #include "nsk_core.hpp"
 
+struct nsk_dbg_amg_args;
+
 namespace nsk {
 
 struct AmgLevel {
@@ -71,5 +73,10 @@ struct Amg {
 // in LDS, at most 512 distinct columns per row, Error -81 beyond).  A and B without ghost columns.  rp: n_rows + 1 row
 // pointers, col: the columns; returns the number of entries.  Used for aSIMPLE's Schur pattern B~ [D^-1] B~^T (round 4).
 int64_t device_product_pattern(Ctx *ctx, const Csr &A, const Csr &B, DBuf<int> &rp, DBuf<int> &col);
+
+
+// Test hook behind nsk_debug_amg (nsk_internal.h): one operation of the set-up on the caller's arrays, on ctx's device and
+// stream.  Lives in nsk_amg.cpp so that it calls Scratch::scan, product_rows, transpose() and aggregate() as the set-up does.
+int debug_amg(Ctx *ctx, const nsk_dbg_amg_args *a, int32_t *info16);
 
 }  // namespace nsk

@@ -68,5 +68,13 @@ void transpose_scatter(hipStream_t s, const Mat &A, int *cursor /* copy of the t
 void rows_sort(hipStream_t s, int n_rows, const int *rp, const int *col_in, const double *val_in, int *col_out,
                double *val_out);
 
+// ---- which kernels the launchers above started, per host thread (what the test hook nsk_debug_amg reports) ----
+struct Tally {
+  long product[2][3][2];   // [product][tier][count 0 / fill 1]
+  long pull1_stamped, pull1_all, pull2;   // mis_pull<1> with stamp >= 0 / stamp < 0, mis_pull<2>
+  long join[2];            // [roots_only]
+};
+Tally &tally();
+
 }  // namespace amgk
 }  // namespace nsk

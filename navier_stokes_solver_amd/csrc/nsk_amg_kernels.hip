@@ -13,9 +13,19 @@
 
 #include "nsk_amg_kernels.h"
 
+// No fused multiply-adds in this file: the set-up is specified operation by operation.  The __dmul_rn /
+// __dadd_rn of the HIP headers are plain `*` and `+` that carry the headers' permission to contract, and the compiler
+// did fuse them into v_fma_f64 in the row products; mul_rn / add_rn / sub_rn below are defined under this pragma and
+// stay single operations.
+#pragma clang fp contract(off)
+
 namespace nsk {
 namespace amgk {
 namespace {
+
+__device__ inline double mul_rn(double a, double b) { return a * b; }
+__device__ inline double add_rn(double a, double b) { return a + b; }
+__device__ inline double sub_rn(double a, double b) { return a - b; }
 
 constexpr int WG = 256;
 constexpr int LPR = 16;          // lanes per row of the graph kernels
@@ -175,7 +185,7 @@ __global__ __launch_bounds__(WG) void strength_kernel(Mat A, const double *__res
     if (i >= A.n_rows) break;
     const int a0 = A.rp[i], a1 = A.rp[i + 1];
     const long wb = flag_base(A.rp, i);
-    const double ti = __dmul_rn(t2, ad[i]);
+    const double ti = mul_rn(t2, ad[i]);
     int any = 0;
     for (int c0 = 0; a0 + LPR * c0 < a1; c0 += U) {
       int j[U];
@@ -191,7 +201,7 @@ __global__ __launch_bounds__(WG) void strength_kernel(Mat A, const double *__res
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         if (a0 + LPR * (c0 + u) >= a1) break;   // (the same for all lanes of the group)
-        const int f = j[u] >= 0 && j[u] != i && __dmul_rn(v[u], v[u]) > __dmul_rn(ti, aj[u]);
+        const int f = j[u] >= 0 && j[u] != i && mul_rn(v[u], v[u]) > mul_rn(ti, aj[u]);
         const unsigned long long mask = __ballot(f);
         if (l == 0) fw[wb + c0 + u] = (uint16_t)(mask >> (LPR * gw));
         any |= f;
@@ -494,11 +504,11 @@ __global__ __launch_bounds__(WG) void product_ab_kernel(Mat A, Mat B, const int 
 #pragma unroll
       for (int p = 0; p < PF; ++p) {
         if (t0 + p >= steps) break;
-        if (bc[p] >= 0) acc[g][hs[p]] = __dadd_rn(acc[g][hs[p]], __dmul_rn(as[p], bv[p]));
+        if (bc[p] >= 0) acc[g][hs[p]] = add_rn(acc[g][hs[p]], mul_rn(as[p], bv[p]));
         const int src = (t0 + p) & (L - 1);
         for (int q = __shfl(q0l, src, L) + l + L; q < q1s[p]; q += L) {   // B rows of more than L entries
           const int h = set_find<H>(tab[g], B.col[q]);
-          acc[g][h] = __dadd_rn(acc[g][h], __dmul_rn(as[p], B.val[q]));
+          acc[g][h] = add_rn(acc[g][h], mul_rn(as[p], B.val[q]));
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // the next entry's lanes may meet these accumulators
       }
@@ -563,16 +573,16 @@ __global__ __launch_bounds__(WG) void prolong_kernel(RowProduct P, const int *__
   }
   if (!act) return;
   const int w0 = c_rp[i];
-  const double si = __dmul_rn(P.c, P.dinv[i]);
+  const double si = mul_rn(P.c, P.dinv[i]);
   for (int e = l; e < d; e += L) {
     const int mine = lst[g][e];
     const double w = P.pw[mine];
     double acc = mine == own ? w : 0.0;
     const int staged = a1 - a0 < H ? a1 - a0 : H;
     for (int x = 0; x < staged; ++x)
-      if (pc[g][x] == mine) acc = __dsub_rn(acc, __dmul_rn(__dmul_rn(si, pv[g][x]), w));
+      if (pc[g][x] == mine) acc = sub_rn(acc, mul_rn(mul_rn(si, pv[g][x]), w));
     for (int k = a0 + H; k < a1; ++k)   // rows of more than H entries
-      if (P.agg[A.col[k]] == mine) acc = __dsub_rn(acc, __dmul_rn(__dmul_rn(si, A.val[k]), w));
+      if (P.agg[A.col[k]] == mine) acc = sub_rn(acc, mul_rn(mul_rn(si, A.val[k]), w));
     const int r = rank_of(lst[g], d, mine);
     len_or_col[w0 + r] = mine;
     c_val[w0 + r] = acc;
@@ -622,6 +632,11 @@ __global__ __launch_bounds__(WG) void rows_sort_kernel(int n_rows, const int *__
 
 }  // namespace
 
+Tally &tally() {
+  static thread_local Tally t{};
+  return t;
+}
+
 size_t scan_tmp_words(int n) { return (size_t)(n + kScanChunk - 1) / kScanChunk + 2; }
 
 void scan_exclusive(hipStream_t s, int n, const int *in, int *out, long long *tmp, long long *total64) {
@@ -652,6 +667,7 @@ void mis_pull(hipStream_t s, const Mat &A, const uint16_t *flag, int pass, const
               const uint64_t *in, uint64_t *out) {
   if (A.n_rows <= 0) return;
   const dim3 grid(row_grid(A.n_rows, SLAB));
+  ++(pass == 1 ? (stamp >= 0 ? tally().pull1_stamped : tally().pull1_all) : tally().pull2);
   if (pass == 1) hipLaunchKernelGGL(mis_pull_kernel<1>, grid, dim3(WG), 0, s, A, flag, key, need, stamp, in, out);
   else hipLaunchKernelGGL(mis_pull_kernel<2>, grid, dim3(WG), 0, s, A, flag, key, need, stamp, in, out);
 }
@@ -669,8 +685,9 @@ void root_ids(hipStream_t s, int n, const uint64_t *key, const int *scan, int fi
 }
 void join(hipStream_t s, const Mat &A, const uint16_t *flag, const uint64_t *key, int roots_only, const int *agg_in,
           int *agg_out) {
-  if (A.n_rows > 0)
-    hipLaunchKernelGGL(join_kernel, dim3(row_grid(A.n_rows, SLAB)), dim3(WG), 0, s, A, flag, key, roots_only, agg_in, agg_out);
+  if (A.n_rows <= 0) return;
+  ++tally().join[roots_only != 0];
+  hipLaunchKernelGGL(join_kernel, dim3(row_grid(A.n_rows, SLAB)), dim3(WG), 0, s, A, flag, key, roots_only, agg_in, agg_out);
 }
 void agg_sizes(hipStream_t s, int n, const int *agg, int *count) {
   if (n > 0) hipLaunchKernelGGL(agg_sizes_kernel, dim3(ew_grid(n)), dim3(WG), 0, s, n, agg, count);
@@ -686,6 +703,7 @@ static void product_launch(hipStream_t s, const RowProduct &P, int product, int 
   const int n = P.A.n_rows;
   if (n <= 0) return;
   const int lanes = tier == 0 ? 8 : tier == 1 ? 16 : 64;
+  ++tally().product[product != 0][tier <= 0 ? 0 : tier == 1 ? 1 : 2][FILL];
   const dim3 grid(row_grid(n, WG / lanes)), block(WG);
   if (product) {
     if (tier == 0) hipLaunchKernelGGL((prolong_kernel<8, 64, FILL>), grid, block, 0, s, P, c_rp, out, c_val, err);

@@ -2433,6 +2433,14 @@ int nsk_debug_tri(nsk_handle h, const nsk_dbg_tri_args *a, int32_t *info) {
   NSK_CATCH(h)
 }
 
+// test hook (nsk_internal.h): one operation of the AMG set-up on the caller's arrays (nsk_amg.cpp: debug_amg)
+int nsk_debug_amg(nsk_handle h, const nsk_dbg_amg_args *a, int32_t *info) {
+  NSK_TRY(h)
+  (void)hipSetDevice(h->ctx.device);
+  return debug_amg(&h->ctx, a, info);
+  NSK_CATCH(h)
+}
+
 int nsk_amg_info(nsk_handle h, int shard, int level, int64_t *rows, int64_t *nnz, double *lambda_max) {
   NSK_TRY(h)
   if (h->amg_active) h->amg_ready();

@@ -214,6 +214,74 @@ struct nsk_dbg_tri_args {
   double *factor_out;
 };
 int nsk_debug_tri(struct nsk_handle_s *h, const struct nsk_dbg_tri_args *a, int32_t *info40);
+/* Test hook for the kernels of the AMG set-up (tests/test_gpu_amg_kernels.py): ONE operation `op` on the caller's
+ * arrays, through the amgk:: launcher or the function of nsk_amg.cpp the set-up calls (Scratch::scan, product_rows and the
+ * fill as row_product runs it, transpose(), aggregate()).  Device and stream of the handle.
+ * Every device array the operation reads or writes is an allocation of its own at its exact size — the scratch the
+ * functions of nsk_amg.cpp take included: the hook's Scratch hands out exact allocations instead of 256-byte slices —
+ * between 64 guard words (32 bits each, all bits set) on either side; the level operators transpose() allocates for its
+ * result are the one exception (plain allocations of the library's own).  Arrays the operation does not write everywhere
+ * (`flag_out`, MIS_PULL's out) start as the caller's array, or with all bits set where the caller gives none.
+ * Inputs are checked on the host: a row pointer that does not start at 0 or decreases -58, a column, aggregate id or
+ * key index out of range -59, everything else -61; nothing out of range reaches a kernel.
+ *   SCAN          n, i_in                          Scratch::scan: i_out[0..n], out64[0] = the 64-bit total (also when the
+ *                                                  scan ends with -80)
+ *   BLOCK         A, r0, r1                        block_count, scan, block_fill: out_rp, out_col, out_val, out64[0] = nnz
+ *   DIAG          A                                d_out = ad, d_out2 = dinv
+ *   STRENGTH      A, ad, threshold, flag_words     flag_out (flag_words 16-bit words, must be amgk::flag_words), k_out = key,
+ *                                                  i_out = agg, out64[0] = undecided
+ *   MIS_PULL      A, flag, key, i_in = need, pass, stamp, key2 (pass 2: pass 1's result; pass 1 reads key, as the set-up
+ *                                                  does), k_out in/out
+ *   MIS_DECIDE    n, key, key2                     k_out, out64[0] = undecided
+ *   MIS_MARK      A, flag, key, stamp, i_in = need i_out = need
+ *   ROOTS         n, key, i_in = agg, first        root_flags, scan, root_ids: i_out = agg, out64[0] = roots
+ *   JOIN          A, flag, key, roots_only, i_in = agg_in, i_out = agg_out in/out
+ *   AGG_WEIGHTS   n, i_in = agg, nc                agg_sizes, agg_weights: i_out = count (nc), d_out = pw (nc)
+ *   AGGREGATE     A, ad                            aggregate(): i_out = agg, d_out = pw (the first out64[0] entries),
+ *                                                  out64[0] = nc, [1] = independent-set rounds, [2] = rounds whose pass 1 ran stamped
+ *   PRODUCT       A, product, first_tier; product 0: B; product 1: i_in = agg, pw, dinv, c, nc
+ *                                                  product_rows, then the fill of the tier it chose: out_rp, out_col, out_val,
+ *                                                  out64[0] = nnz, [1] = the tier used, [2] = error word after the fill,
+ *                                                  [4 + t] = error word of a count at tier t >= first_tier (-1: not run)
+ *   PRODUCT_COUNT the same inputs                  product_count at tier first_tier alone: i_out = len (n), out64[0] = error word
+ *   TRANSPOSE     A                                transpose(): out_rp, out_col, out_val (rows sorted), out64[0] = nnz
+ *   ROWS_SORT     A (rows in any order)            out_col, out_val
+ *   START_VECTOR  n                                d_out = x
+ * out_col / out_val hold out_cap entries (-61 when the result has more).  The fill of a row product is only ever launched
+ * on the row pointers of a count of the same tier whose error word was 0, as in the set-up: no call asks for another.
+ * info16: [0] guard words that changed, [1] product, [2] lanes per row and [3] hash slots of the last row-product launch,
+ * [4] bit 0 a count ran, bit 1 a fill ran, [5] launches of mis_pull<1> stamped, [6] of mis_pull<1> over all rows, [7] of
+ * mis_pull<2>, [8] of join with roots_only 1, [9] with roots_only 0, [10 + t] counts and [13 + t] fills launched at tier t.
+ * 0 or the library's negative error code (-80, -81, -84 as the set-up throws them). */
+enum {
+  NSK_DBG_AMG_SCAN = 0, NSK_DBG_AMG_BLOCK = 1, NSK_DBG_AMG_DIAG = 2, NSK_DBG_AMG_STRENGTH = 3, NSK_DBG_AMG_MIS_PULL = 4,
+  NSK_DBG_AMG_MIS_DECIDE = 5, NSK_DBG_AMG_MIS_MARK = 6, NSK_DBG_AMG_ROOTS = 7, NSK_DBG_AMG_JOIN = 8,
+  NSK_DBG_AMG_AGG_WEIGHTS = 9, NSK_DBG_AMG_AGGREGATE = 10, NSK_DBG_AMG_PRODUCT = 11, NSK_DBG_AMG_PRODUCT_COUNT = 12,
+  NSK_DBG_AMG_TRANSPOSE = 13, NSK_DBG_AMG_ROWS_SORT = 14, NSK_DBG_AMG_START_VECTOR = 15
+};
+struct nsk_dbg_amg_mat {
+  int32_t n_rows, n_cols;
+  const int32_t *rowptr, *col;
+  const double *val;
+};
+struct nsk_dbg_amg_args {
+  int32_t op, n, r0, r1, pass, stamp, roots_only, first, product, first_tier, nc, out_cap;
+  int64_t flag_words;
+  double threshold, c;
+  struct nsk_dbg_amg_mat A, B;
+  const int32_t *i_in;
+  const uint64_t *key, *key2;
+  const uint16_t *flag;
+  const double *ad, *dinv, *pw;
+  int32_t *i_out;
+  uint64_t *k_out;
+  uint16_t *flag_out;
+  double *d_out, *d_out2;
+  int32_t *out_rp, *out_col;
+  double *out_val;
+  int64_t *out64;   /* 8 */
+};
+int nsk_debug_amg(struct nsk_handle_s *h, const struct nsk_dbg_amg_args *a, int32_t *info16);
 /* Which index width the scalar stream kernels of block b (NSK_BLK_S or NSK_BLK_MP) run on after the set-up: out3 = {the
  * block's SpMV, the lower half of its triangular factor, the upper half}; 16: 16-bit offsets, 32: int32 column ids, 0: that
  * operation does not go through the scalar stream kernels on this handle. */
