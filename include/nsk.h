@@ -30,6 +30,8 @@
  *   -40..-47 missing blocks, bad preconditioner / solver type, call order
  *   -48 NSK_OPT_INNER_MATRIX_PRECISION = 32: a value of F, S or M_p is finite in fp64 but outside the range of fp32
  *   -50..-59 bad arguments of the hand-off calls           -60..-66 device assembly / Newton state
+ *   -69, -71..-73 forces / output patches from the resident state (-69: no cells, or no faces / edges handed over; -71:
+ *        faces on a P2/P1 handle, edges or patches on the other kind; -72: a cell index out of range; -73: no state)
  *   -70 single-launch triangular solve gave up waiting AND the per-colour retry failed too (see NSK_OPT_TRI_SYNC_FREE)
  *   -80..-84 AMG set-up (operator too large for 32-bit indices, rows too wide, rounds / estimates that do not end)
  *   -1 any other exception
@@ -374,6 +376,34 @@ int nsk_state_update(nsk_handle h, double alpha);
 int nsk_state_save_old(nsk_handle h);
 int nsk_assemble(nsk_handle h, int stokes, double nu, double inv_dt, double p_out, int inhomogeneous_bc,
                  double *residual_norm);
+/* ---------------------------------------------------------------------------------------------------
+ * Consumers of the resident `solution`: the forces on the obstacle and the output patches.
+ * Replaces the face loop of compute_lift_drag() (NSSolverStationary.cpp:836-897, NSSolver.cpp:876-935) and the reads
+ * DataOut::build_patches makes of the solution (:769-796); nothing on the linear-solve path changes.
+ *
+ * nsk_forces_set_faces: the faces with boundary id 10 of this rank's cells, after nsk_assembly_set_cells — per face the
+ *   local cell (index into that call's cell list) and the side (0: the neighbour at i-1 is missing, 1: i+1, 2: j-1,
+ *   3: j+1; the fluid cell's outward normal is (-1,0), (1,0), (0,-1), (0,1)) — and what FEFaceValues tabulates for the
+ *   congruent cell: 672 doubles, for side s and Gauss point q (4 per face) at (s * 4 + q) * 41 the physical
+ *   dphi/dx[16], dphi/dy[16] and psi[9], then JxW[4][4] at 656.  n_faces may be 0 (a rank whose cells do not touch the
+ *   obstacle).  nsk_forces_set_edges: the same for P2/P1 handles, after nsk_assembly_set_simplex — per id-10 edge its
+ *   cell, the cell's local edge (0: vertices 0-1, 1: 1-2, 2: 2-0) and (n_x, n_y, length) with the fluid cell's outward
+ *   normal; two Gauss points per edge.  Cell indices are checked on the host at hand-off (-72).
+ *   nsk_assembly_set_cells / nsk_assembly_set_simplex void the list.
+ * nsk_forces: drag_lift[0..1] = -sum over those faces of (nu (grad u + grad u^T) - p I) n JxW from the resident state
+ *   (owned entries and the ghost tail, as nsk_assemble reads them), summed over the ranks (Utilities::MPI::sum,
+ *   :895-896); local_drag_lift (or NULL): this rank's share.  Collective when nranks > 1.  One work item per (face,
+ *   Gauss point) writes its own slot, one workgroup adds the slots in a fixed order: two calls give the same bits.
+ * nsk_state_get_patches: for each listed local cell (u_x, u_y) [8 doubles] and p [4 doubles] at its vertices (0,0),
+ *   (1,0), (0,1), (1,1) — velocity nodes 0, 3, 12, 15 and pressure DoFs 0, 2, 6, 8 of the cell; the bits of the state,
+ *   owned or ghost.  Q3/Q2 handles. */
+int nsk_forces_set_faces(nsk_handle h, int64_t n_faces, const int32_t *face_cell, const uint8_t *face_side,
+                         const double *tables672);
+int nsk_forces_set_edges(nsk_handle h, int64_t n_edges, const int32_t *edge_cell, const uint8_t *edge_local,
+                         const double *edge_nl);
+int nsk_forces(nsk_handle h, double nu, double *drag_lift, double *local_drag_lift /* or NULL */);
+int nsk_state_get_patches(nsk_handle h, int64_t n, const int32_t *cells, double *vel /* 8 per cell */,
+                          double *prs /* 4 per cell */);
 /* values of a resident block times a factor: pressure_mass is assembled with 1/nu (:404, :450), block (1,0)
  * changes sign between the Stokes and the Newton phase (:397 against :444) */
 int nsk_scale_values(nsk_handle h, int blk, double factor);

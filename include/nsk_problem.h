@@ -110,6 +110,24 @@ const uint8_t *nsp_cell_flags(const nsp_mesh *m);
 int32_t nsp_cell_of_dof0(const nsp_mesh *m); /* local index of the cell holding global DoF 0 as its node 0, or -1 */
 void nsp_cell_tables(const nsp_mesh *m, double *out944);
 
+/* Consumers of the solution (lift / drag over boundary id 10, VTU patches; NSSolverStationary.cpp:765-897), valid after
+ * nsp_assemble like the cell lists above.
+ * nsp_cell_ij: lattice position (i, j) of every local cell, two int32 per cell.  nsp_cell_in_strip: 1 for the cells of
+ * this rank's strip of cell columns — the local cell list also holds the neighbour strips' cells that touch an owned DoF.
+ * Obstacle faces: one entry per face between a kept cell of THIS RANK'S STRIP and a removed cell, sorted by (i, j, side)
+ * of the fluid cell; face_cell: local cell index (into the nsp_cell_* arrays); face_side: 0 the neighbour at i-1, 1 at
+ * i+1, 2 at j-1, 3 at j+1 — the outward normal of the fluid cell is (-1,0), (1,0), (0,-1), (0,1).  A rank whose strip
+ * has no such face returns 0.
+ * nsp_face_tables fills 672 doubles, what FEFaceValues holds for the congruent cell (:844-853): for side s and Gauss
+ * point q (4 per face) at (s * 4 + q) * 41: physical dphi/dx[16], dphi/dy[16] (n = b*4 + a) and psi[9] (m = b*3 + a);
+ * then JxW[4][4] at 656 + s * 4 + q. */
+const int32_t *nsp_cell_ij(const nsp_mesh *m);
+const uint8_t *nsp_cell_in_strip(const nsp_mesh *m);
+int64_t nsp_n_obstacle_faces(const nsp_mesh *m);
+const int32_t *nsp_face_cell(const nsp_mesh *m);
+const uint8_t *nsp_face_side(const nsp_mesh *m);
+void nsp_face_tables(const nsp_mesh *m, double *out672);
+
 /* Support points of this rank's owned DoFs (what DoFTools::map_dofs_to_support_points gives the reference's caller):
  * out_xy[2 d], out_xy[2 d + 1] = (x, y) of owned DoF d of `space` (0: velocity, both components of a node share the
  * point; 1: pressure).  Valid after nsp_mesh_create; sizes 2 * (u_end - u_begin) and 2 * (p_end - p_begin). */

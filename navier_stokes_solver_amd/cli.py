@@ -99,19 +99,41 @@ def _levels(first, step, target):
     return out or [first]
 
 
-def _report(backend, nx, ny, nu, inlet_u, name, counter, n_digits):
-    """What the reference's main() / time loop does with the solution (testStationary.cpp:133-136,
-    NSSolver.cpp:830-833): VTU record, lift and drag forces over boundary id 10, their coefficients."""
-    import os
+def _host_postprocess() -> bool:
+    """NSK_HOST_POSTPROCESS=1: the report from downloaded global vectors (postprocess.lift_drag / write_vtu) — the
+    yardstick of the device path, kept for A/B."""
+    return os.environ.get("NSK_HOST_POSTPROCESS", "0") not in ("", "0")
+
+
+def _device_report(ls, pr, nu, name, counter, n_digits, rank=0, nranks=1):
+    """VTU piece of this rank's strip and the forces, both from the device-resident solution: the patches of
+    the strip's cells (`nsk_state_get_patches`) and `nsk_forces` over the strip's obstacle faces, summed over the ranks
+    inside the library.  Returns (drag_force, lift_force)."""
+    import numpy as np
 
     from . import postprocess as PP
-    u, p = backend.solution()
+    own = np.nonzero(pr.cell_in_strip)[0]
+    vel, prs = ls.state_patches(own)
+    PP.write_vtu_patches(os.environ.get("NSK_OUTPUT_DIR", "./"), name, counter, pr.cell_ij[own], PP.LX / pr.info["nx"],
+                         PP.LY / pr.info["ny"], vel, prs, n_digits=n_digits, rank=rank, nranks=nranks)
+    return ls.forces(nu)
+
+
+def _report(backend, nx, ny, nu, inlet_u, name, counter, n_digits, pr=None):
+    """What the reference's main() / time loop does with the solution (testStationary.cpp:133-136,
+    NSSolver.cpp:830-833): VTU record, lift and drag forces over boundary id 10, their coefficients.  `pr`: the
+    hand-off whose faces were given to the handle (`set_forces`) — then both come from the device-resident solution."""
+    from . import postprocess as PP
     print("===============================================")
-    PP.write_vtu(os.environ.get("NSK_OUTPUT_DIR", "./"), name, counter, nx, ny, u, p, n_digits=n_digits)
+    if pr is not None and not _host_postprocess():
+        drag, lift = _device_report(backend.ls, pr, nu, name, counter, n_digits)
+    else:
+        u, p = backend.solution()
+        PP.write_vtu(os.environ.get("NSK_OUTPUT_DIR", "./"), name, counter, nx, ny, u, p, n_digits=n_digits)
+        drag, lift = PP.lift_drag(nx, ny, u, p, nu)
     print("Output written to output-stokes")          # the reference prints this name in both drivers
     print("===============================================")
     print("===============================================\nComputing lift and drag forces")
-    drag, lift = PP.lift_drag(nx, ny, u, p, nu)
     cd, cl = PP.coefficients(drag, lift, inlet_u)
     print(f"===============================================\nLift coefficient: {cl:g}")
     print(f"===============================================\nDrag coefficient: {cd:g}")
@@ -150,6 +172,8 @@ def run_gmsh(cfg, unsteady: bool) -> int:
         ls.set_option(S.OPT_TRI_ORDERING, S.ORDER_MULTICOLOR)
         _env_options(ls, S)
 
+    device_forces = False
+
     def report(name, nu, inlet_u):
         u, p = backend.solution()
         out_dir = os.environ.get("NSK_OUTPUT_DIR", "./")
@@ -166,6 +190,8 @@ def run_gmsh(cfg, unsteady: bool) -> int:
         print("===============================================\n===============================================\nComputing lift and drag forces")
         if nranks > 1 and not unsteady:     # each rank its own share of the obstacle, summed (Utilities::MPI::sum, .cpp:895-896)
             drag, lift, _ = backend.lift_drag(nu)
+        elif device_forces:                 # one rank, device assembly: nsk_forces over the id-10 edges
+            drag, lift = ls.forces(nu)
         else:
             drag, lift = SX.lift_drag(space, u, p, nu)
         cd, cl = PP.coefficients(drag, lift, inlet_u)
@@ -176,6 +202,9 @@ def run_gmsh(cfg, unsteady: bool) -> int:
         first = SX.assemble(space, 1.0, mode=0, inlet_bc=1, U=0.3)
         first.simplex = SX.device_handoff(space, first)
         backend = N.DeviceBackend(ls, first, cfg["solver"], cfg["prec"], cfg["tol"], max_iter=100000, inv_dt=1.0 / cfg["dt"])
+        if not _host_postprocess():
+            ls.set_force_edges(space)
+            device_forces = True
         t0 = time.time()
         try:
             nu_last = 1.0 / max(_levels(1.0, 10.0, cfg["Re"]))
@@ -204,6 +233,9 @@ def run_gmsh(cfg, unsteady: bool) -> int:
         first = SX.assemble(space, 0.1, mode=0, inlet_bc=1, U=0.1)
         first.simplex = SX.device_handoff(space, first)
         backend = N.DeviceBackend(ls, first, cfg["solver"], cfg["prec"], cfg["tol"])
+        if not _host_postprocess():
+            ls.set_force_edges(space)
+            device_forces = True
     t0 = time.time()
     try:
         N.solve_newton(backend, cfg["Re"])
@@ -290,18 +322,26 @@ def _rank_main(cfg, unsteady, r, nranks, grp, make_handle, say):
                                   max_iter=100000 if unsteady else 20000, inv_dt=1.0 / cfg["dt"] if unsteady else 0.0,
                                   plan=plan)
 
+        host_report = _host_postprocess()
+        if not host_report:
+            ls.set_forces(first)
+
         def report(nu, inlet_u, name, counter, n_digits):
-            # the ranks' owned pieces side by side are the global vectors (x-strips own contiguous ranges)
-            pieces = grp.allgather(r, backend.solution())
-            u, p = np.concatenate([q[0] for q in pieces]), np.concatenate([q[1] for q in pieces])
             say("===============================================")
-            PP.write_vtu(os.environ.get("NSK_OUTPUT_DIR", "./"), name, counter, nx, ny, u, p, n_digits=n_digits, rank=r,
-                         nranks=nranks)
+            if host_report:
+                # the ranks' owned pieces side by side are the global vectors (x-strips own contiguous ranges)
+                pieces = grp.allgather(r, backend.solution())
+                u, p = np.concatenate([q[0] for q in pieces]), np.concatenate([q[1] for q in pieces])
+                PP.write_vtu(os.environ.get("NSK_OUTPUT_DIR", "./"), name, counter, nx, ny, u, p, n_digits=n_digits, rank=r,
+                             nranks=nranks)
+                forces = grp.allgather(r, PP.lift_drag(nx, ny, u, p, nu, rank=r, nranks=nranks))   # (Utilities::MPI::sum)
+                drag, lift = sum(f[0] for f in forces), sum(f[1] for f in forces)
+            else:
+                # rank-local: the strip's patches and faces from the resident state; nsk_forces sums over the ranks
+                drag, lift = _device_report(ls, first, nu, name, counter, n_digits, rank=r, nranks=nranks)
             say("Output written to output-stokes")
             say("===============================================")
             say("===============================================\nComputing lift and drag forces")
-            forces = grp.allgather(r, PP.lift_drag(nx, ny, u, p, nu, rank=r, nranks=nranks))   # (Utilities::MPI::sum)
-            drag, lift = sum(f[0] for f in forces), sum(f[1] for f in forces)
             cd, cl = PP.coefficients(drag, lift, inlet_u)
             say(f"===============================================\nLift coefficient: {cl:g}")
             say(f"===============================================\nDrag coefficient: {cd:g}")
@@ -431,10 +471,12 @@ def run(cfg, unsteady: bool) -> int:
         _env_options(ls, S)
         first_system = P.generate(nx, ny, nu=0.1, mode=0, state=0, inlet_bc=1, U=0.1)   # first level: nu = 1/10
         backend = N.DeviceBackend(ls, first_system, cfg["solver"], cfg["prec"], cfg["tol"])
+        ls.set_forces(first_system)
         t0 = time.time()
         try:
             N.solve_newton(backend, cfg["Re"])
-            _report(backend, nx, ny, 1.0 / max(l for l in _levels(10.0, 20.0, cfg["Re"])), 1.0, "output-stokes", 0, None)
+            _report(backend, nx, ny, 1.0 / max(l for l in _levels(10.0, 20.0, cfg["Re"])), 1.0, "output-stokes", 0, None,
+                    pr=first_system)
         finally:
             dt = time.time() - t0
             n = info["n_u_global"] + info["n_p_global"]
@@ -451,11 +493,12 @@ def run(cfg, unsteady: bool) -> int:
     first_system = P.generate(nx, ny, nu=1.0, mode=0, state=0, inlet_bc=1, U=0.3)        # first level: nu = 1/1
     backend = N.DeviceBackend(ls, first_system, cfg["solver"], cfg["prec"], cfg["tol"], max_iter=100000,
                               inv_dt=1.0 / cfg["dt"])
+    ls.set_forces(first_system)
     t0 = time.time()
     try:
         nu_last = 1.0 / max(_levels(1.0, 10.0, cfg["Re"]))
         N.time_loop(backend, cfg["T"], cfg["dt"], cfg["Re"],
-                    after_step=lambda step: _report(backend, nx, ny, nu_last, 0.3, "output", step, 3))
+                    after_step=lambda step: _report(backend, nx, ny, nu_last, 0.3, "output", step, 3, pr=first_system))
     finally:
         dt = time.time() - t0
         n = info["n_u_global"] + info["n_p_global"]

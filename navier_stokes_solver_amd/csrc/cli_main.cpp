@@ -10,7 +10,9 @@
 //   (nsk_solve_resident) and vector updates (nsk_state_*) resident on the GPU — SURVEY 8f rows 1 and 3.
 //   NSSolver runs the reference's time loop (NSSolver::solve(), NSSolver.cpp:799-837) with one solve_newton()
 //   (NSSolver.cpp:674-754) per step; the device assembly carries the mass term and the solution_old term.
-//   VTU output and lift/drag are consumers and not part of it.
+//   Both then do what the reference's main() / time loop does with the solution (testStationary.cpp:133-136,
+//   NSSolver.cpp:830-833): the VTU record (vtu_patches.hpp, from nsk_state_get_patches) and the lift / drag coefficients
+//   of the cylinder (nsk_forces) — once after solve_newton(), once per time step; SURVEY 8f row 4.
 //
 // Built twice from this file: -DNSK_UNSTEADY=0 -> StationaryNSSolver, -DNSK_UNSTEADY=1 -> NSSolver.
 #include <getopt.h>
@@ -26,6 +28,7 @@
 
 #include "../../include/nsk.h"
 #include "../../include/nsk_problem.h"
+#include "vtu_patches.hpp"
 
 #ifndef NSK_UNSTEADY
 #define NSK_UNSTEADY 0
@@ -48,6 +51,46 @@ static void check(nsk_handle h, int rc, const char *what) {
   if (rc < 0) throw std::runtime_error(std::string(what) + ": " + nsk_last_error(h));
 }
 
+
+// What both drivers do with a converged solution: NSSolverStationary::output() + compute_lift_drag() and the coefficient
+// lines of compute_lift_coeff() / compute_drag_coeff() (.cpp:765-919), from the device-resident solution.
+struct Report {
+  nsk_handle h;
+  double nu, inlet_u, hx, hy;
+  std::vector<int32_t> cells, ij;     // this rank's strip: local cell ids and their (i, j)
+  std::vector<double> vel, prs;
+  Report(nsk_handle h_, const nsp_mesh *mesh, const nsp_info &info, double nu_, double inlet_u_)
+      : h(h_), nu(nu_), inlet_u(inlet_u_), hx(2.2 / info.nx), hy(0.41 / info.ny) {
+    const int64_t nc = nsp_n_cells_local(mesh);
+    const int32_t *cij = nsp_cell_ij(mesh);
+    const uint8_t *own = nsp_cell_in_strip(mesh);
+    for (int64_t c = 0; c < nc; ++c)
+      if (own[c]) { cells.push_back((int32_t)c); ij.push_back(cij[2 * c]); ij.push_back(cij[2 * c + 1]); }
+    vel.resize(8 * cells.size());
+    prs.resize(4 * cells.size());
+    double tab[672];
+    nsp_face_tables(mesh, tab);
+    check(h, nsk_forces_set_faces(h, nsp_n_obstacle_faces(mesh), nsp_face_cell(mesh), nsp_face_side(mesh), tab),
+          "nsk_forces_set_faces");
+  }
+  void operator()(const char *name, unsigned counter, int n_digits) {
+    std::cout << "===============================================" << std::endl;
+    check(h, nsk_state_get_patches(h, (int64_t)cells.size(), cells.data(), vel.data(), prs.data()), "nsk_state_get_patches");
+    const char *dir = std::getenv("NSK_OUTPUT_DIR");
+    vtu::write_patches(dir ? dir : "./", name, vtu::counter_text(counter, n_digits), (int64_t)cells.size(), ij.data(), hx, hy,
+                       vel.data(), prs.data(), 0, 1);
+    std::cout << "Output written to output-stokes" << std::endl;   // the reference prints this name in both drivers
+    std::cout << "===============================================" << std::endl;
+    std::cout << "===============================================\nComputing lift and drag forces" << std::endl;
+    double f[2];
+    check(h, nsk_forces(h, nu, f, nullptr), "nsk_forces");
+    const double u_avg = 2.0 * inlet_u / 3.0;   // 2 F / (U_avg^2 D), D = 0.1 (.cpp:899-919)
+    std::cout << "===============================================\nLift coefficient: " << 2.0 * f[1] / (u_avg * u_avg * 0.1)
+              << std::endl;
+    std::cout << "===============================================\nDrag coefficient: " << 2.0 * f[0] / (u_avg * u_avg * 0.1)
+              << std::endl;
+  }
+};
 
 // solve_newton() of both reference drivers over device-resident state.
 struct InletVelocity {  // NSSolverStationary.hpp:59-111
@@ -212,8 +255,8 @@ struct NewtonDriver {
     std::cout << "===============================================" << std::endl;
   }
 
-  // NSSolver::solve() (NSSolver.cpp:799-837) without output / lift-drag
-  void time_loop(double T, double delta_t, double target_Re) {
+  // NSSolver::solve() (NSSolver.cpp:799-837)
+  void time_loop(double T, double delta_t, double target_Re, Report &report) {
     double time = 0.0;
     unsigned time_step = 0;
     bool apply_first = true;
@@ -224,6 +267,7 @@ struct NewtonDriver {
       std::printf("n = %3u, t = %5.6f\n", time_step, time);
       run_unsteady(target_Re, apply_first);
       apply_first = false;
+      report("output", time_step, 3);
       std::cout << std::endl;
     }
   }
@@ -355,9 +399,17 @@ int main(int argc, char *argv[]) {
       std::vector<double> zu((size_t)n_u, 0.0), zp((size_t)n_p, 0.0);
       check(h, nsk_state_set(h, zu.data(), zp.data()), "nsk_state_set");   // solution = 0
       NewtonDriver drv{h, solver_type, preconditioner, tolerance, 1.0, nu0, NSK_UNSTEADY ? 1.0 / time_step : 0.0};
+      // viscosity of the last continuation level (10, 30, ... / 1, 11, ... <= Re) and the inlet amplitude the Python
+      // drivers report with
+      double last_Re = NSK_UNSTEADY ? 1.0 : 10.0;
+      while (last_Re + (NSK_UNSTEADY ? 10.0 : 20.0) <= Re) last_Re += NSK_UNSTEADY ? 10.0 : 20.0;
+      Report report(h, mesh, info, 1.0 / last_Re, NSK_UNSTEADY ? 0.3 : 1.0);
       const auto t0 = std::chrono::steady_clock::now();
-      if (NSK_UNSTEADY) drv.time_loop(time_span, time_step, Re);
-      else drv.run(Re);
+      if (NSK_UNSTEADY) drv.time_loop(time_span, time_step, Re, report);
+      else {
+        drv.run(Re);
+        report("output-stokes", 0, 0);
+      }
       const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
       const double n = (double)(info.n_u_global + info.n_p_global);
       std::printf("[nsk] %d assemblies, %ld outer iterations of solve_system(), %.3f s in %s -> %.4g DoF*iters/s\n",

@@ -41,6 +41,16 @@ void asm_matfree_F(hipStream_t s, const AsmMesh &M, const double *cq, double nu,
                    const double *x_own, const double *x_ghost, double *wk, double *y);
 double asm_matfree_F_bytes(const AsmMesh &M, int stokes);   // bytes the two kernels move for one product
 
+// ---- consumers of the solution: forces over boundary id 10, output patches ----
+// su / sp: the resident `solution` [owned | ghost].  slots: 2 doubles per (face, Gauss point) — 4 points per Q3/Q2 face,
+// 2 per P2/P1 edge; out2: (drag, lift) of the handed-over faces, the slots added in a fixed order by one workgroup.
+// ftab: nsp_face_tables (672 doubles).  Two launches, no atomics.
+void forces_faces(hipStream_t s, const AsmMesh &M, long n_faces, const int *face_cell, const unsigned char *face_side,
+                  const double *ftab, const double *su, const double *sp, double nu, double *slots, double *out2);
+// (u_x, u_y) [8 per cell] and p [4 per cell] at the four vertices of the listed cells: the bits of the state
+void state_patches(hipStream_t s, const AsmMesh &M, long n, const int *cells, const double *su, const double *sp, double *vel,
+                   double *prs);
+
 // ---- P2/P1 on triangles (general cells; the reference's -M path) ----
 struct SimplexMesh {  // device pointers
   long n_cells, n_blocks;
@@ -61,5 +71,9 @@ struct SimplexMesh {  // device pointers
 void simplex_assemble(hipStream_t s, const SimplexMesh &M, const double *su, const double *sp, const double *so, double nu,
                       double inv_dt, double p_out, int stokes, const int *rowptr, const int *col, double *val, double *d0,
                       const double *bc, double *rhs_u, double *rhs_p, double *x0_u, double *x0_p);
+
+// forces over the id-10 edges: edge_cell, edge_local (the cell's local edge 0-2), edge_nl = (nx, ny, length) per edge
+void forces_edges(hipStream_t s, const SimplexMesh &M, long n_edges, const int *edge_cell, const unsigned char *edge_local,
+                  const double *edge_nl, const double *su, const double *sp, double nu, double *slots, double *out2);
 
 }  // namespace nsk

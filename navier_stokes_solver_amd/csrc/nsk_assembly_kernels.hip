@@ -297,7 +297,87 @@ __global__ __launch_bounds__(BLK) void mf_rows_kernel(AsmMesh M, const double *_
   *reinterpret_cast<double2 *>(y + 2 * (size_t)r) = o;
 }
 
+// ---- consumers of the solution: forces over boundary id 10 and output patches ----
+// compute_lift_drag (NSSolverStationary.cpp:836-897): -sum over the obstacle faces of (nu (grad u + grad u^T) - p I) n JxW
+// with the fluid cell's outward normal.  One thread per (face, Gauss point) writes its two components to its own slot;
+// forces_sum_kernel adds the slots in a fixed order.  No atomics: two calls give the same bits.
+// ftab: per (side, point) dphi/dx[16], dphi/dy[16], psi[9]; JxW[4][4] at 656 (nsp_face_tables)
+constexpr int FT_STRIDE = 41, FT_JXW = 656;
+__global__ __launch_bounds__(BLK) void forces_faces_kernel(long n_faces, const int *__restrict__ cell_u,
+                                                           const int *__restrict__ cell_p, const int *__restrict__ face_cell,
+                                                           const unsigned char *__restrict__ face_side,
+                                                           const double *__restrict__ ftab, const double *__restrict__ su,
+                                                           const double *__restrict__ sp, double nu, double *__restrict__ slots) {
+  const long t = (long)blockIdx.x * BLK + threadIdx.x;
+  if (t >= n_faces * 4) return;
+  const long f = t >> 2;
+  const int q = (int)(t & 3), side = face_side[f];
+  const long cell = face_cell[f];
+  const double *T = ftab + (side * 4 + q) * FT_STRIDE;
+  double g00 = 0, g01 = 0, g10 = 0, g11 = 0, p = 0;
+  for (int n = 0; n < 16; ++n) {
+    const int node = cell_u[cell * 16 + n];
+    const double2 uv = *reinterpret_cast<const double2 *>(su + 2 * (size_t)node);
+    const double dx = T[n], dy = T[16 + n];
+    g00 += uv.x * dx; g01 += uv.x * dy;
+    g10 += uv.y * dx; g11 += uv.y * dy;
+  }
+  for (int m = 0; m < 9; ++m) p += sp[cell_p[cell * 9 + m]] * T[32 + m];
+  const double nx = side == 0 ? -1.0 : side == 1 ? 1.0 : 0.0, ny = side == 2 ? -1.0 : side == 3 ? 1.0 : 0.0;
+  const double jxw = ftab[FT_JXW + side * 4 + q];
+  const double s00 = nu * (g00 + g00) - p, s01 = nu * (g01 + g10), s11 = nu * (g11 + g11) - p;
+  slots[2 * t] = -(s00 * nx + s01 * ny) * jxw;
+  slots[2 * t + 1] = -(s01 * nx + s11 * ny) * jxw;
+}
+
+// one workgroup: thread i adds slots i, i + BLK, ... in that order, then a binary tree over the BLK partial sums
+__global__ __launch_bounds__(BLK) void forces_sum_kernel(long n_slots, const double *__restrict__ slots, double *__restrict__ out) {
+  __shared__ double a0[BLK], a1[BLK];
+  double d = 0.0, l = 0.0;
+  for (long i = threadIdx.x; i < n_slots; i += BLK) { d += slots[2 * i]; l += slots[2 * i + 1]; }
+  a0[threadIdx.x] = d; a1[threadIdx.x] = l;
+  __syncthreads();
+  for (int w = BLK / 2; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) { a0[threadIdx.x] += a0[threadIdx.x + w]; a1[threadIdx.x] += a1[threadIdx.x + w]; }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) { out[0] = a0[0]; out[1] = a1[0]; }
+}
+
+// DataOut patches (NSSolverStationary.cpp:769-796): (u_x, u_y) and p at the four vertices (0,0), (1,0), (0,1), (1,1) of
+// the listed cells — velocity nodes 0, 3, 12, 15 and pressure DoFs 0, 2, 6, 8.  One thread per (cell, vertex).
+__global__ __launch_bounds__(BLK) void state_patches_kernel(long n, const int *__restrict__ cells, const int *__restrict__ cell_u,
+                                                            const int *__restrict__ cell_p, const double *__restrict__ su,
+                                                            const double *__restrict__ sp, double *__restrict__ vel,
+                                                            double *__restrict__ prs) {
+  const long t = (long)blockIdx.x * BLK + threadIdx.x;
+  if (t >= n * 4) return;
+  const long cell = cells[t >> 2];
+  const int v = (int)(t & 3);
+  const int un = v == 0 ? 0 : v == 1 ? 3 : v == 2 ? 12 : 15, pn = v == 0 ? 0 : v == 1 ? 2 : v == 2 ? 6 : 8;
+  const int node = cell_u[cell * 16 + un];
+  *reinterpret_cast<double2 *>(vel + 2 * t) = *reinterpret_cast<const double2 *>(su + 2 * (size_t)node);
+  prs[t] = sp[cell_p[cell * 9 + pn]];
+}
+
 }  // namespace
+
+static void forces_sum(hipStream_t s, long n_slots, const double *slots, double *out2) {
+  hipLaunchKernelGGL(forces_sum_kernel, dim3(1), dim3(BLK), 0, s, n_slots, slots, out2);
+}
+void forces_faces(hipStream_t s, const AsmMesh &M, long n_faces, const int *face_cell, const unsigned char *face_side,
+                  const double *ftab, const double *su, const double *sp, double nu, double *slots, double *out2) {
+  if (n_faces > 0)
+    hipLaunchKernelGGL(forces_faces_kernel, dim3((unsigned)((n_faces * 4 + BLK - 1) / BLK)), dim3(BLK), 0, s, n_faces, M.cell_u,
+                       M.cell_p, face_cell, face_side, ftab, su, sp, nu, slots);
+  forces_sum(s, n_faces * 4, slots, out2);
+}
+void state_patches(hipStream_t s, const AsmMesh &M, long n, const int *cells, const double *su, const double *sp, double *vel,
+                   double *prs) {
+  if (n > 0)
+    hipLaunchKernelGGL(state_patches_kernel, dim3((unsigned)((n * 4 + BLK - 1) / BLK)), dim3(BLK), 0, s, n, cells, M.cell_u,
+                       M.cell_p, su, sp, vel, prs);
+}
 
 void asm_matfree_F(hipStream_t s, const AsmMesh &M, const double *cq, double nu, double inv_dt, int stokes, const double *d0,
                    const double *x_own, const double *x_ghost, double *wk, double *y) {
@@ -525,7 +605,51 @@ __global__ __launch_bounds__(256) void simplex_rhs_p_kernel(SimplexMesh M, const
   x0[j] = 0.0;
 }
 
+// Forces on the id-10 edges of a P2/P1 mesh: one thread per (edge, Gauss point), the two points of simplex.lift_drag
+// (the integrand is at most quadratic along an edge).  The gradients of the six P2 functions come from the cell's
+// grad_lambda.  edge_nl: per edge the fluid cell's outward normal and the length.
+__global__ __launch_bounds__(256) void forces_edges_kernel(long n_edges, const int *__restrict__ cell_u,
+                                                           const int *__restrict__ cell_p, const double *__restrict__ grad_lam,
+                                                           const int *__restrict__ edge_cell,
+                                                           const unsigned char *__restrict__ edge_local,
+                                                           const double *__restrict__ edge_nl, const double *__restrict__ su,
+                                                           const double *__restrict__ spv, double nu, double *__restrict__ slots) {
+  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n_edges * 2) return;
+  const long e = t >> 1;
+  const long c = edge_cell[e];
+  const int k = edge_local[e], i = k, j = (k + 1) % 3;   // local edge k joins vertices k and (k + 1) % 3
+  const double gp = (t & 1) ? 0.78867513459481288 : 0.21132486540518712;   // 1/2 -+ 1/(2 sqrt 3)
+  double lam[3] = {0.0, 0.0, 0.0};
+  lam[i] = 1.0 - gp;
+  lam[j] = gp;
+  const int *cu = cell_u + 6 * (size_t)c;
+  const int *cp = cell_p + 3 * (size_t)c;
+  const double *gl = grad_lam + 6 * (size_t)c;
+  double g00 = 0, g01 = 0, g10 = 0, g11 = 0;
+  for (int n = 0; n < 6; ++n) {
+    double v, gx, gy;
+    p2_grad(n, lam, gl, v, gx, gy);
+    const double ux = su[2 * (size_t)cu[n]], uy = su[2 * (size_t)cu[n] + 1];
+    g00 += ux * gx; g01 += ux * gy;
+    g10 += uy * gx; g11 += uy * gy;
+  }
+  const double p = spv[cp[0]] * lam[0] + spv[cp[1]] * lam[1] + spv[cp[2]] * lam[2];
+  const double nx = edge_nl[3 * e], ny = edge_nl[3 * e + 1], w = 0.5 * edge_nl[3 * e + 2];
+  const double s00 = nu * (g00 + g00) - p, s01 = nu * (g01 + g10), s11 = nu * (g11 + g11) - p;
+  slots[2 * t] = -(s00 * nx + s01 * ny) * w;
+  slots[2 * t + 1] = -(s01 * nx + s11 * ny) * w;
+}
+
 }  // namespace
+
+void forces_edges(hipStream_t s, const SimplexMesh &M, long n_edges, const int *edge_cell, const unsigned char *edge_local,
+                  const double *edge_nl, const double *su, const double *sp, double nu, double *slots, double *out2) {
+  if (n_edges > 0)
+    hipLaunchKernelGGL(forces_edges_kernel, dim3((unsigned)((n_edges * 2 + 255) / 256)), dim3(256), 0, s, n_edges, M.cell_u,
+                       M.cell_p, M.grad_lam, edge_cell, edge_local, edge_nl, su, sp, nu, slots);
+  forces_sum(s, n_edges * 2, slots, out2);
+}
 
 void simplex_assemble(hipStream_t s, const SimplexMesh &M, const double *su, const double *sp, const double *so, double nu,
                       double inv_dt, double p_out, int stokes, const int *rowptr, const int *col, double *val, double *d0,

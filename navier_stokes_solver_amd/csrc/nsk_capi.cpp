@@ -261,6 +261,12 @@ struct nsk_handle_s {
     double mf_nu = 0, mf_inv_dt = 0;
     int mf_stokes = 0;
     DBuf<double> d0, mf_wk;   // the Dirichlet diagonal of that assembly; the cells' shares of their node rows
+    // forces over boundary id 10 (nsk_forces_set_faces / nsk_forces_set_edges): void with the cell data
+    bool forces_set = false;
+    long n_faces = 0;         // faces (Q3/Q2, 4 points each) or edges (P2/P1, 2 points each)
+    DBuf<int> face_cell;
+    DBuf<unsigned char> face_side;
+    DBuf<double> face_tab, force_slots, force_out;   // 672 doubles | (nx, ny, length) per edge; 2 per point; local + total
   } asmd;
   int matrix_free_f = 0;        // NSK_OPT_INNER_MATRIX_FREE_F
   bool matfree_wanted = false;  // what the last set-up took of it (the option or NSK_INNER_MATRIX_FREE_F)
@@ -1593,6 +1599,7 @@ int nsk_assembly_set_cells(nsk_handle h, int64_t n_cells, const int32_t *cell_u_
   A.mf_wk.alloc((size_t)n_cells * kMatfreeCellDoubles);
   A.d0.alloc(1);
   A.mf_valid = false;   // (cq of another mesh)
+  A.forces_set = false;   // (faces index the cells of another mesh)
   if (!A.sol_u) {
     A.sol_u = h->pool_u.get(true); A.eval_u = h->pool_u.get(true); A.old_u = h->pool_u.get(true);
     A.sol_p = h->pool_p.get(true); A.eval_p = h->pool_p.get(true);
@@ -1745,6 +1752,7 @@ int nsk_assembly_set_simplex(nsk_handle h, int64_t n_cells, const int32_t *cell_
   }
   h->ctx.sync();
   A.mf_valid = false;
+  A.forces_set = false;   // (edges index the cells of another mesh)
   A.simplex = true;
   A.ready = true;
   return 0;
@@ -1802,6 +1810,113 @@ int nsk_assemble(nsk_handle h, int stokes, double nu, double inv_dt, double p_ou
   A.assemble_ms = wall_ms() - t0;
   return 0;
   NSK_CATCH_ABORT(h)
+}
+
+// ------------------------------------------------------------------ consumers of the solution: forces, output patches
+int nsk_forces_set_faces(nsk_handle h, int64_t n_faces, const int32_t *face_cell, const uint8_t *face_side,
+                         const double *tables672) {
+  NSK_TRY(h)
+  (void)hipSetDevice(h->ctx.device);
+  auto &A = h->asmd;
+  if (!A.ready) throw Error(-69, "nsk_forces_set_faces: no cells on the handle (call nsk_assembly_set_cells first)");
+  if (A.simplex) throw Error(-71, "nsk_forces_set_faces: the handle holds P2/P1 triangles (nsk_forces_set_edges)");
+  if (n_faces < 0 || !tables672 || (n_faces > 0 && (!face_cell || !face_side))) throw Error(-60, "nsk_forces_set_faces: bad arguments");
+  // what the kernel indexes with: checked on the host before anything is launched
+  for (int64_t f = 0; f < n_faces; ++f) {
+    if (face_cell[f] < 0 || face_cell[f] >= A.n_cells) throw Error(-72, "nsk_forces_set_faces: cell index out of range");
+    if (face_side[f] > 3) throw Error(-72, "nsk_forces_set_faces: side out of range");
+  }
+  hipStream_t s = h->s();
+  A.face_cell.upload(face_cell, (size_t)n_faces, s);
+  A.face_side.upload(face_side, (size_t)n_faces, s);
+  A.face_tab.upload(tables672, 672, s);
+  A.force_slots.alloc((size_t)std::max<int64_t>(1, n_faces * 8));
+  A.force_out.alloc(4);
+  h->ctx.sync();
+  A.n_faces = (long)n_faces;
+  A.forces_set = true;
+  return 0;
+  NSK_CATCH(h)
+}
+
+int nsk_forces_set_edges(nsk_handle h, int64_t n_edges, const int32_t *edge_cell, const uint8_t *edge_local,
+                         const double *edge_nl) {
+  NSK_TRY(h)
+  (void)hipSetDevice(h->ctx.device);
+  auto &A = h->asmd;
+  if (!A.ready) throw Error(-69, "nsk_forces_set_edges: no cells on the handle (call nsk_assembly_set_simplex first)");
+  if (!A.simplex) throw Error(-71, "nsk_forces_set_edges: the handle holds Q3/Q2 cells (nsk_forces_set_faces)");
+  if (n_edges < 0 || (n_edges > 0 && (!edge_cell || !edge_local || !edge_nl))) throw Error(-60, "nsk_forces_set_edges: bad arguments");
+  for (int64_t e = 0; e < n_edges; ++e) {
+    if (edge_cell[e] < 0 || edge_cell[e] >= A.n_cells) throw Error(-72, "nsk_forces_set_edges: cell index out of range");
+    if (edge_local[e] > 2) throw Error(-72, "nsk_forces_set_edges: local edge out of range");
+  }
+  hipStream_t s = h->s();
+  A.face_cell.upload(edge_cell, (size_t)n_edges, s);
+  A.face_side.upload(edge_local, (size_t)n_edges, s);
+  A.face_tab.upload(edge_nl, (size_t)n_edges * 3, s);
+  A.force_slots.alloc((size_t)std::max<int64_t>(1, n_edges * 4));
+  A.force_out.alloc(4);
+  h->ctx.sync();
+  A.n_faces = (long)n_edges;
+  A.forces_set = true;
+  return 0;
+  NSK_CATCH(h)
+}
+
+int nsk_forces(nsk_handle h, double nu, double *drag_lift, double *local_drag_lift) {
+  NSK_TRY(h)
+  (void)hipSetDevice(h->ctx.device);
+  auto &A = h->asmd;
+  if (!A.ready) throw Error(-69, "nsk_forces: no cells on the handle");
+  if (!A.forces_set) throw Error(-69, A.simplex ? "nsk_forces: no edges handed over (nsk_forces_set_edges)"
+                                                : "nsk_forces: no faces handed over (nsk_forces_set_faces)");
+  if (!A.state_set) throw Error(-73, "nsk_forces: no state on the device");
+  if (!drag_lift) throw Error(-60, "nsk_forces: bad arguments");
+  hipStream_t s = h->s();
+  double *out = A.force_out.p;   // [0, 1] this rank's share, [2, 3] the sum over the ranks
+  if (A.simplex) {
+    const SimplexMesh SM{A.n_cells, A.sx_blocks, h->n_u() / 2, h->n_p(), A.sx_pos00, A.cell_u.p, A.cell_p.p, A.sx_grad.p,
+                         A.sx_area.p, A.sx_blk_ptr.p, A.sx_blk_ent.p, A.sx_pos0.p, A.sx_pos1.p, A.sx_node_ptr.p,
+                         A.sx_node_ent.p, A.sx_vert_ptr.p, A.sx_vert_ent.p, A.sx_outlet.p, A.dirichlet.p};
+    forces_edges(s, SM, A.n_faces, A.face_cell.p, A.face_side.p, A.face_tab.p, A.sol_u, A.sol_p, nu, A.force_slots.p, out);
+  } else {
+    forces_faces(s, h->asm_view(), A.n_faces, A.face_cell.p, A.face_side.p, A.face_tab.p, A.sol_u, A.sol_p, nu,
+                 A.force_slots.p, out);
+  }
+  vec_copy(s, 2, out, out + 2);
+  h->ctx.comm.allreduce_sum(out + 2, 2, s);   // Utilities::MPI::sum (NSSolverStationary.cpp:895-896)
+  double host[4];
+  NSK_HIP(hipMemcpyAsync(host, out, sizeof(host), hipMemcpyDeviceToHost, s));
+  h->ctx.sync();
+  drag_lift[0] = host[2]; drag_lift[1] = host[3];
+  if (local_drag_lift) { local_drag_lift[0] = host[0]; local_drag_lift[1] = host[1]; }
+  return 0;
+  NSK_CATCH_ABORT(h)
+}
+
+int nsk_state_get_patches(nsk_handle h, int64_t n, const int32_t *cells, double *vel, double *prs) {
+  NSK_TRY(h)
+  (void)hipSetDevice(h->ctx.device);
+  auto &A = h->asmd;
+  if (!A.ready) throw Error(-69, "nsk_state_get_patches: no cells on the handle (call nsk_assembly_set_cells first)");
+  if (A.simplex) throw Error(-71, "nsk_state_get_patches: the handle holds P2/P1 triangles");
+  if (!A.state_set) throw Error(-73, "nsk_state_get_patches: no state on the device");
+  if (n < 0 || (n > 0 && (!cells || !vel || !prs))) throw Error(-60, "nsk_state_get_patches: bad arguments");
+  for (int64_t c = 0; c < n; ++c)
+    if (cells[c] < 0 || cells[c] >= A.n_cells) throw Error(-72, "nsk_state_get_patches: cell index out of range");
+  if (n == 0) return 0;
+  hipStream_t s = h->s();
+  DBuf<int> dc;
+  DBuf<double> dv;
+  dc.upload(cells, (size_t)n, s);
+  dv.alloc((size_t)n * 12);
+  state_patches(s, h->asm_view(), (long)n, dc.p, A.sol_u, A.sol_p, dv.p, dv.p + (size_t)n * 8);
+  NSK_HIP(hipMemcpyAsync(vel, dv.p, sizeof(double) * (size_t)n * 8, hipMemcpyDeviceToHost, s));
+  NSK_HIP(hipMemcpyAsync(prs, dv.p + (size_t)n * 8, sizeof(double) * (size_t)n * 4, hipMemcpyDeviceToHost, s));
+  h->ctx.sync();
+  return 0;
+  NSK_CATCH(h)
 }
 
 int nsk_scale_values(nsk_handle h, int blk, double factor) {

@@ -67,6 +67,8 @@ struct Tables {
   double jxw[16];
   double K[16][16], M3[16][16], G[2][16][9], M2[9][9];
   double face_w3[4];  // integral of 1-D Q3 basis over [0,1]
+  // tabulated on the 4 Gauss points of each of the 4 faces (side s: neighbour at i-1, i+1, j-1, j+1), see nsp_face_tables
+  double face[672];
 };
 
 static void build_tables(Tables &T, double hx, double hy) {
@@ -100,6 +102,28 @@ static void build_tables(Tables &T, double hx, double hy) {
       for (int b = 0; b < 3; ++b)
         for (int a = 0; a < 3; ++a) T.psi[b * 3 + a][q] = L2[qx][a] * L2[qy][b];
     }
+  // FEFaceValues on the faces of the congruent cell (NSSolverStationary.cpp:844-853): side 0 / 1 at x = 0 / 1 of the
+  // reference cell with the Gauss points along y, side 2 / 3 at y = 0 / 1 with the points along x
+  for (int s = 0; s < 4; ++s) {
+    const double fixed = (s & 1) ? 1.0 : 0.0;
+    for (int q = 0; q < 4; ++q) {
+      const double xs = s < 2 ? fixed : gx[q], ys = s < 2 ? gx[q] : fixed;
+      double l3x[4], d3x[4], l3y[4], d3y[4], l2x[3], l2y[3], dd[3];
+      lagrange(T.gll, 4, xs, l3x, d3x);
+      lagrange(T.gll, 4, ys, l3y, d3y);
+      lagrange(T.q2, 3, xs, l2x, dd);
+      lagrange(T.q2, 3, ys, l2y, dd);
+      double *o = T.face + (s * 4 + q) * 41;
+      for (int b = 0; b < 4; ++b)
+        for (int a = 0; a < 4; ++a) {
+          o[b * 4 + a] = d3x[a] * l3y[b] / hx;
+          o[16 + b * 4 + a] = l3x[a] * d3y[b] / hy;
+        }
+      for (int b = 0; b < 3; ++b)
+        for (int a = 0; a < 3; ++a) o[32 + b * 3 + a] = l2x[a] * l2y[b];
+      T.face[656 + s * 4 + q] = gw[q] * (s < 2 ? hy : hx);
+    }
+  }
   for (int n = 0; n < 16; ++n)
     for (int m = 0; m < 16; ++m) {
       double k = 0, mm = 0;
@@ -156,6 +180,11 @@ struct nsp_mesh {
   // cell connectivity of the assembly hand-off (cells touching an owned DoF), local ids
   std::vector<int32_t> cell_u_nodes, cell_p_dofs;
   std::vector<uint8_t> cell_flags;
+  std::vector<int32_t> cell_ij;          // (i, j) of every local cell
+  std::vector<uint8_t> cell_in_strip;    // 1: a cell of this rank's strip of cell columns
+  // faces with boundary id 10 of the strip's cells: local cell, side (0: neighbour at i-1, 1: i+1, 2: j-1, 3: j+1)
+  std::vector<int32_t> face_cell;
+  std::vector<uint8_t> face_side;
   int32_t cell_of_dof0 = -1;
   std::vector<double> state_u, state_p;  // linearisation state in global DoF numbering (params.state == 2)
   std::vector<double> state_u_old;       // solution_old of the time loop (NSSolver.cpp:813), same numbering; empty = none
@@ -778,6 +807,7 @@ int nsp_assemble(nsp_mesh *mp, const nsp_params *p) {
   // cell -> local DoF lists (what cell->get_dof_indices gives the reference's assembly loop, .cpp:532)
   {
     M.cell_u_nodes.clear(); M.cell_p_dofs.clear(); M.cell_flags.clear();
+    M.cell_ij.clear(); M.cell_in_strip.clear(); M.face_cell.clear(); M.face_side.clear();
     M.cell_of_dof0 = -1;
     auto local_u = [&](int64_t g) -> int64_t {  // global u-DoF -> local id (owned first, ghosts appended), -1 if absent
       if (g >= u0 && g < u1) return g - u0;
@@ -817,7 +847,28 @@ int nsp_assemble(nsp_mesh *mp, const nsp_params *p) {
         M.cell_u_nodes.insert(M.cell_u_nodes.end(), un, un + 16);
         M.cell_p_dofs.insert(M.cell_p_dofs.end(), pn, pn + 9);
         M.cell_flags.push_back(ci == M.nx - 1 ? 1 : 0);
+        M.cell_ij.push_back(ci); M.cell_ij.push_back(cj);
+        M.cell_in_strip.push_back(ci >= M.ccol[M.rank] && ci < M.ccol[M.rank + 1] ? 1 : 0);
       }
+    // boundary id 10: a kept cell of the strip with a removed cell behind the face (the local cells are in (i, j) order)
+    const int di[4] = {-1, 1, 0, 0}, dj[4] = {0, 0, -1, 1};
+    for (size_t c = 0; c < M.cell_flags.size(); ++c) {
+      if (!M.cell_in_strip[c]) continue;
+      const int ci = M.cell_ij[2 * c], cj = M.cell_ij[2 * c + 1];
+      for (int s = 0; s < 4; ++s) {
+        const int ni = ci + di[s], nj = cj + dj[s];
+        if (ni < 0 || ni >= M.nx || nj < 0 || nj >= M.ny || M.kept[(size_t)ni * M.ny + nj]) continue;
+        M.face_cell.push_back((int32_t)c);
+        M.face_side.push_back((uint8_t)s);
+      }
+    }
+    // every kept cell of the strip holds an owned DoF, so none of its faces can be missing from the list
+    int64_t strip_cells = 0;
+    for (int ci = M.ccol[M.rank]; ci < M.ccol[M.rank + 1]; ++ci)
+      for (int cj = 0; cj < M.ny; ++cj) strip_cells += M.kept[(size_t)ci * M.ny + cj];
+    int64_t listed = 0;
+    for (uint8_t f : M.cell_in_strip) listed += f;
+    if (listed != strip_cells) return -5;
   }
   if (p->mode == 1) {
 #pragma omp parallel for schedule(static)
@@ -851,6 +902,12 @@ const int32_t *nsp_cell_u_nodes(const nsp_mesh *m) { return m->cell_u_nodes.data
 const int32_t *nsp_cell_p_dofs(const nsp_mesh *m) { return m->cell_p_dofs.data(); }
 const uint8_t *nsp_cell_flags(const nsp_mesh *m) { return m->cell_flags.data(); }
 int32_t nsp_cell_of_dof0(const nsp_mesh *m) { return m->cell_of_dof0; }
+const int32_t *nsp_cell_ij(const nsp_mesh *m) { return m->cell_ij.data(); }
+const uint8_t *nsp_cell_in_strip(const nsp_mesh *m) { return m->cell_in_strip.data(); }
+int64_t nsp_n_obstacle_faces(const nsp_mesh *m) { return (int64_t)m->face_cell.size(); }
+const int32_t *nsp_face_cell(const nsp_mesh *m) { return m->face_cell.data(); }
+const uint8_t *nsp_face_side(const nsp_mesh *m) { return m->face_side.data(); }
+void nsp_face_tables(const nsp_mesh *m, double *out) { std::memcpy(out, m->T.face, sizeof(m->T.face)); }
 
 // Support points of this rank's owned DoFs (DoFTools::map_dofs_to_support_points): out_xy[2 d], out_xy[2 d + 1] for
 // owned DoF d of the space (0 velocity: both components of a node share the point; 1 pressure).

@@ -1,4 +1,6 @@
 """Consumers of the solution, host side: lift / drag over the obstacle boundary and VTU output.
+`lift_drag` and `write_vtu` work on downloaded global vectors and are the yardsticks of the device path (`nsk_forces`,
+`nsk_state_get_patches` + `write_vtu_patches`), which the drivers use.
 
 Reference: `NSSolverStationary::compute_lift_drag()`, `compute_lift_coeff()`, `compute_drag_coeff()`, `output()`
 (lab_new/src/NSSolverStationary.cpp:765-800, 802-897, 905-933) and the NSSolver twins (NSSolver.cpp:761-797,
@@ -207,6 +209,99 @@ def write_vtu(directory, name, counter, nx, ny, u, p, n_digits=None, rank=0, nra
 </DataArray>
 <DataArray type="Float64" Name="partitioning" format="ascii">
 {" ".join(str(float(rank)) for _ in range(n_pts))}
+</DataArray>
+</PointData>
+</Piece>
+</UnstructuredGrid>
+</VTKFile>
+"""
+    os.makedirs(directory, exist_ok=True)
+    with open(os.path.join(directory, piece), "w") as f:
+        f.write(xml)
+    if rank != 0:
+        return os.path.join(directory, piece)
+    pieces = "\n".join(f'<Piece Source="{name}_{cnt}.{r}.vtu"/>' for r in range(nranks))
+    pvtu = f"""<?xml version="1.0"?>
+<VTKFile type="PUnstructuredGrid" version="0.1" byte_order="LittleEndian">
+<PUnstructuredGrid GhostLevel="0">
+<PPointData Scalars="scalars">
+<PDataArray type="Float64" Name="velocity" NumberOfComponents="3" format="ascii"/>
+<PDataArray type="Float64" Name="pressure" format="ascii"/>
+<PDataArray type="Float64" Name="partitioning" format="ascii"/>
+</PPointData>
+<PPoints>
+<PDataArray type="Float64" NumberOfComponents="3"/>
+</PPoints>
+{pieces}
+</PUnstructuredGrid>
+</VTKFile>
+"""
+    with open(os.path.join(directory, f"{name}_{cnt}.pvtu"), "w") as f:
+        f.write(pvtu)
+    return os.path.join(directory, piece)
+
+
+def _join_rows(a):
+    """`write_vtu`'s number formatting (`.12g`) of a 2-D array: one row per line, entries separated by blanks."""
+    t = np.char.mod("%.12g", np.asarray(a, float))
+    out = t[:, 0]
+    for k in range(1, t.shape[1]):
+        out = np.char.add(np.char.add(out, " "), t[:, k])
+    return "\n".join(out.tolist())
+
+
+def write_vtu_patches(directory, name, counter, ij, hx, hy, vel, prs, n_digits=None, rank=0, nranks=1):
+    """The files `write_vtu` writes, byte for byte, from per-cell patches instead of global vectors: `ij` [n, 2] the lattice
+    positions of this rank's cells in (i, j) order, `vel` [n, 4, 2] and `prs` [n, 4] the state at their vertices (0,0), (1,0),
+    (0,1), (1,1) (`LinearSolver.state_patches`).  No loop over the cells in Python."""
+    ij = np.asarray(ij, np.int64).reshape(-1, 2)
+    vel = np.asarray(vel, float).reshape(-1, 4, 2)
+    prs = np.asarray(prs, float).reshape(-1, 4)
+    n_cells = len(ij)
+    if vel.shape[0] != n_cells or prs.shape[0] != n_cells:
+        raise ValueError("patches do not match the cell list")
+    if not (np.isfinite(vel).all() and np.isfinite(prs).all()):
+        raise ValueError("VTU output touched an entry this rank does not hold (owned + ghost DoFs)")
+    n_pts = 4 * n_cells
+    da, db = np.array([0, 1, 0, 1]), np.array([0, 0, 1, 1])          # deal.II vertex order of a patch
+    zero = np.zeros((n_pts, 1))
+    pts = np.concatenate([((ij[:, :1] + da).reshape(-1, 1)) * hx, ((ij[:, 1:] + db).reshape(-1, 1)) * hy, zero], axis=1)
+    cnt = str(counter) if n_digits is None else str(counter).zfill(n_digits)
+    piece = f"{name}_{cnt}.{rank}.vtu"
+    c4 = 4 * np.arange(n_cells).reshape(-1, 1)
+    ints = lambda a: np.char.mod("%d", a)                            # noqa: E731
+    conn = ints(c4 + np.array([0, 1, 3, 2]))                         # VTK_QUAD ordering
+    conn = "\n".join(np.char.add(np.char.add(np.char.add(conn[:, 0], " "), np.char.add(conn[:, 1], " ")),
+                                 np.char.add(np.char.add(conn[:, 2], " "), conn[:, 3])).tolist()) if n_cells else ""
+    xml = f"""<?xml version="1.0" ?>
+<VTKFile type="UnstructuredGrid" version="0.1" byte_order="LittleEndian">
+<UnstructuredGrid>
+<Piece NumberOfPoints="{n_pts}" NumberOfCells="{n_cells}">
+<Points>
+<DataArray type="Float64" NumberOfComponents="3" format="ascii">
+{_join_rows(pts) if n_cells else ""}
+</DataArray>
+</Points>
+<Cells>
+<DataArray type="Int32" Name="connectivity" format="ascii">
+{conn}
+</DataArray>
+<DataArray type="Int32" Name="offsets" format="ascii">
+{" ".join(ints(4 * np.arange(1, n_cells + 1)).tolist())}
+</DataArray>
+<DataArray type="UInt8" Name="types" format="ascii">
+{" ".join(["9"] * n_cells)}
+</DataArray>
+</Cells>
+<PointData Scalars="scalars">
+<DataArray type="Float64" Name="velocity" NumberOfComponents="3" format="ascii">
+{_join_rows(np.concatenate([vel.reshape(-1, 2), zero], axis=1)) if n_cells else ""}
+</DataArray>
+<DataArray type="Float64" Name="pressure" format="ascii">
+{_join_rows(prs.reshape(-1, 1)) if n_cells else ""}
+</DataArray>
+<DataArray type="Float64" Name="partitioning" format="ascii">
+{" ".join([str(float(rank))] * n_pts)}
 </DataArray>
 </PointData>
 </Piece>

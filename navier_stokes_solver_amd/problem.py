@@ -61,7 +61,8 @@ def lib() -> C.CDLL:
         for f, t in (("nsp_rhs_u", C.c_double), ("nsp_rhs_p", C.c_double), ("nsp_x0_u", C.c_double),
                      ("nsp_x0_p", C.c_double), ("nsp_ghost_u", C.c_int32), ("nsp_ghost_p", C.c_int32),
                      ("nsp_dirichlet_u", C.c_uint8), ("nsp_cell_u_nodes", C.c_int32), ("nsp_cell_p_dofs", C.c_int32),
-                     ("nsp_cell_flags", C.c_uint8)):
+                     ("nsp_cell_flags", C.c_uint8), ("nsp_cell_ij", C.c_int32), ("nsp_cell_in_strip", C.c_uint8),
+                     ("nsp_face_cell", C.c_int32), ("nsp_face_side", C.c_uint8)):
             getattr(L, f).restype = C.POINTER(t)
             getattr(L, f).argtypes = [C.c_void_p]
         L.nsp_n_cells_local.restype = C.c_int64
@@ -69,6 +70,9 @@ def lib() -> C.CDLL:
         L.nsp_cell_of_dof0.restype = C.c_int32
         L.nsp_cell_of_dof0.argtypes = [C.c_void_p]
         L.nsp_cell_tables.argtypes = [C.c_void_p, C.c_void_p]
+        L.nsp_n_obstacle_faces.restype = C.c_int64
+        L.nsp_n_obstacle_faces.argtypes = [C.c_void_p]
+        L.nsp_face_tables.argtypes = [C.c_void_p, C.c_void_p]
         _LIB = L
     return _LIB
 
@@ -123,6 +127,12 @@ class LocalProblem:
     cell_flags: np.ndarray = None     # [n_cells] bit 0: outlet face
     cell_of_dof0: int = -1
     cell_tables: np.ndarray = None    # 944 doubles, see nsk_problem.h
+    # consumers of the solution (lift / drag, VTU patches), see nsk_problem.h
+    cell_ij: np.ndarray = None        # [n_cells, 2] lattice position of every local cell
+    cell_in_strip: np.ndarray = None  # [n_cells] 1: a cell of this rank's strip of cell columns
+    face_cell: np.ndarray = None      # [n_faces] local cell of every obstacle face of the strip, sorted by (i, j, side)
+    face_side: np.ndarray = None      # [n_faces] 0: neighbour at i-1, 1: i+1, 2: j-1, 3: j+1
+    face_tables: np.ndarray = None    # 672 doubles
     simplex: dict = None              # P2/P1 triangles instead (simplex.device_handoff): nsk_assembly_set_simplex
     support_u: np.ndarray = None      # [n_u, 2] support points of the owned velocity DoFs (map_dofs_to_support_points)
     support_p: np.ndarray = None      # [n_p, 2]
@@ -236,6 +246,14 @@ def generate(nx: int, ny: int, *, nu: float, mode: int = 1, state=1, inlet_bc: i
         tab = np.empty(944)
         L.nsp_cell_tables(h, tab.ctypes.data)
         out.cell_tables = tab
+        out.cell_ij = _arr(L.nsp_cell_ij(h), nc * 2, np.int32, True).reshape(nc, 2)
+        out.cell_in_strip = _arr(L.nsp_cell_in_strip(h), nc, np.uint8, True)
+        nf = int(L.nsp_n_obstacle_faces(h))
+        out.face_cell = _arr(L.nsp_face_cell(h), nf, np.int32, True)
+        out.face_side = _arr(L.nsp_face_side(h), nf, np.uint8, True)
+        ftab = np.empty(672)
+        L.nsp_face_tables(h, ftab.ctypes.data)
+        out.face_tables = ftab
         L.nsp_support_points.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         L.nsp_support_points.restype = None
         out.support_u, out.support_p = np.empty((n_u, 2)), np.empty((n_p, 2))

@@ -287,6 +287,19 @@ def lift_drag(sp_: SimplexSpace, u, p, nu):
     return drag, lift
 
 
+def force_edges(sp_: SimplexSpace):
+    """What `nsk_forces_set_edges` takes (include/nsk.h): per id-10 edge its cell, the cell's local edge (the one whose
+    midpoint node is the edge's) and (n_x, n_y, length) with the fluid cell's outward normal."""
+    a, m, b, nx_, ny_, ln, tt = sp_.obstacle
+    cells = np.asarray(tt, np.int64)
+    mid = np.asarray(m, np.int64)
+    local = np.argmax(sp_.cell_u[cells, 3:] == mid[:, None], axis=1) if len(cells) else np.zeros(0, np.int64)
+    if len(cells) and not (sp_.cell_u[cells, 3 + local] == mid).all():
+        raise ValueError("an obstacle edge is not an edge of its cell")
+    nl = np.stack([np.asarray(nx_, float), np.asarray(ny_, float), np.asarray(ln, float)], axis=1).reshape(-1, 3)
+    return (np.ascontiguousarray(cells, np.int32), np.ascontiguousarray(local, np.uint8), np.ascontiguousarray(nl, np.float64))
+
+
 def write_pvtu(path, piece_names):
     """The record naming the ranks' pieces (`write_vtu_with_pvtu_record`, NSSolverStationary.cpp:793-796)."""
     with open(path, "w") as f:

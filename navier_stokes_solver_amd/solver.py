@@ -57,6 +57,7 @@ EXPORTS = [
     "nsk_reset_stats", "nsk_get_history", "nsk_cancel", "nsk_abort_group", "nsk_assembly_set_cells", "nsk_assembly_set_simplex", "nsk_assembly_set_dirichlet", "nsk_state_set", "nsk_state_get",
     "nsk_state_save", "nsk_state_save_old", "nsk_state_update", "nsk_assemble", "nsk_scale_values", "nsk_download_rhs", "nsk_time_assemble", "nsk_time_op", "nsk_profile_begin", "nsk_profile_read", "nsk_profile_end",
     "nsk_debug_spmv_form",
+    "nsk_forces_set_faces", "nsk_forces_set_edges", "nsk_forces", "nsk_state_get_patches",
 ]
 
 
@@ -133,6 +134,10 @@ def lib() -> C.CDLL:
         L.nsk_state_update.argtypes = [vp, C.c_double]
         L.nsk_assemble.argtypes = [vp, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_double)]
         L.nsk_scale_values.argtypes = [vp, C.c_int, C.c_double]
+        L.nsk_forces_set_faces.argtypes = [vp, C.c_int64, i32p, vp, f64p]
+        L.nsk_forces_set_edges.argtypes = [vp, C.c_int64, i32p, vp, f64p]
+        L.nsk_forces.argtypes = [vp, C.c_double, f64p, f64p]
+        L.nsk_state_get_patches.argtypes = [vp, C.c_int64, i32p, f64p, f64p]
         L.nsk_download_rhs.argtypes = [vp, f64p, f64p]
         L.nsk_time_assemble.argtypes = [vp, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_double)]
         L.nsk_amg_info.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
@@ -529,6 +534,35 @@ class LinearSolver:
         nrm = C.c_double()
         self._ck(self.L.nsk_assemble(self.h, int(stokes), nu, inv_dt, p_out, int(inhomogeneous_bc), C.byref(nrm)))
         return nrm.value
+
+    # ---- consumers of the resident state: forces on the obstacle, output patches ----
+    def set_forces(self, pr):
+        """The obstacle faces (boundary id 10) of a generated-mesh LocalProblem and their tabulation; after set_assembly."""
+        fc = np.ascontiguousarray(pr.face_cell, np.int32)
+        fs = np.ascontiguousarray(pr.face_side, np.uint8)
+        tab = _f64(pr.face_tables)
+        self._ck(self.L.nsk_forces_set_faces(self.h, len(fc), fc.ctypes.data, fs.ctypes.data, tab.ctypes.data))
+
+    def set_force_edges(self, space):
+        """The id-10 edges of a P2/P1 space (simplex.force_edges); after set_assembly with a simplex hand-off."""
+        from . import simplex as SX
+        ec, el, nl = SX.force_edges(space)
+        self._ck(self.L.nsk_forces_set_edges(self.h, len(ec), ec.ctypes.data, el.ctypes.data, nl.ctypes.data))
+
+    def forces(self, nu, local=False):
+        """(drag_force, lift_force) over the handed-over faces / edges from the resident state, summed over the ranks
+        (collective); local=True: ((drag, lift), this rank's share)."""
+        tot, loc = np.zeros(2), np.zeros(2)
+        self._ck(self.L.nsk_forces(self.h, float(nu), tot.ctypes.data, loc.ctypes.data))
+        t = (float(tot[0]), float(tot[1]))
+        return (t, (float(loc[0]), float(loc[1]))) if local else t
+
+    def state_patches(self, cells):
+        """(vel [n, 4, 2], prs [n, 4]): the state at the four vertices (0,0), (1,0), (0,1), (1,1) of the listed local cells."""
+        c = np.ascontiguousarray(cells, np.int32)
+        vel, prs = np.empty((len(c), 4, 2)), np.empty((len(c), 4))
+        self._ck(self.L.nsk_state_get_patches(self.h, len(c), c.ctypes.data, vel.ctypes.data, prs.ctypes.data))
+        return vel, prs
 
     def scale_values(self, blk, factor):
         self._ck(self.L.nsk_scale_values(self.h, blk, float(factor)))
