@@ -2606,6 +2606,29 @@ int nsk_debug_pool_counts(nsk_handle h, int32_t *out6) {   // nsk_internal.h
   return 0;
 }
 
+int64_t nsk_debug_asm(nsk_handle h, int what, void *out, int64_t cap) {   // nsk_internal.h
+  NSK_TRY(h)
+  (void)hipSetDevice(h->ctx.device);
+  const auto &A = h->asmd;
+  if (!A.ready || A.simplex || !A.mf_valid) throw Error(-66, "nsk_debug_asm: no Q3/Q2 assembly on the handle (call nsk_assemble)");
+  const void *src = nullptr;
+  size_t bytes = 0;
+  switch (what) {
+    case NSK_DBG_ASM_CQ: src = A.cq.p; bytes = sizeof(double) * (size_t)A.n_cells * kAsmCellDoubles; break;
+    case NSK_DBG_ASM_D0: src = A.d0.p; bytes = sizeof(double); break;
+    case NSK_DBG_ASM_NODE_CELLS: src = A.node_cells.p; bytes = sizeof(int) * A.node_cells.n; break;
+    case NSK_DBG_ASM_NODE_OFF: src = A.node_off.p; bytes = A.node_off.n; break;
+    case NSK_DBG_ASM_NODE_SELF: src = A.node_self.p; bytes = sizeof(int) * A.node_self.n; break;
+    case NSK_DBG_ASM_PDOF_CELLS: src = A.pdof_cells.p; bytes = sizeof(int) * A.pdof_cells.n; break;
+    default: throw Error(-65, "nsk_debug_asm: unknown item");
+  }
+  if (!out || cap < (int64_t)bytes) throw Error(-61, "nsk_debug_asm: out is too small");
+  if (bytes) NSK_HIP(hipMemcpyAsync(out, src, bytes, hipMemcpyDeviceToHost, h->s()));
+  h->ctx.sync();
+  return (int64_t)bytes;
+  NSK_CATCH(h)
+}
+
 int nsk_inner_value_bytes(nsk_handle h, int b, int32_t *bytes) {
   NSK_TRY(h)
   if (b != NSK_BLK_F && b != NSK_BLK_S && b != NSK_BLK_MP) throw Error(-62, "nsk_inner_value_bytes: F, S or M_p");

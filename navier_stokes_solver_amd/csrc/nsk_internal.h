@@ -292,6 +292,17 @@ int nsk_debug_index_width(struct nsk_handle_s *h, int b, int32_t *out3);
 int nsk_debug_spmv_form(int blk_ok, int stream_ok, int inner32, int use_stream, int use_bsr, int mode, int inner);
 /* Work vectors of the handle's three pools: out6 = {allocated, free} of the velocity, the pressure and the block pool. */
 int nsk_debug_pool_counts(struct nsk_handle_s *h, int32_t *out6);
+/* Read-only view of what the last nsk_assemble left on a Q3/Q2 handle (tests/test_gpu_asm_kernels.py): copies
+ * `what` into out (cap: its size in bytes) and launches nothing.  NSK_DBG_ASM_CQ: the state at the quadrature points,
+ * n_cells * 144 doubles ([cell][u0 u1 g00 g01 g10 g11 p uold0 uold1][q]); _D0: the Dirichlet diagonal, 1 double; and what
+ * nsk_assembly_set_cells derived from the connectivity: _NODE_CELLS n_nodes * 4 int32 (cell * 16 + local node, -1 unused),
+ * _NODE_OFF n_nodes * 64 uint8 (block offset of (cell slot k, column node m) in the node's rows), _NODE_SELF n_nodes
+ * int32 (offset of the diagonal block), _PDOF_CELLS n_p * 4 int32 (cell * 9 + local DoF).  Returns the number of bytes
+ * copied; -66 before the first assembly (or when block (0,0) or the cell data were written since) and on simplex handles,
+ * -61 when cap is too small, -65 for an unknown `what`. */
+enum { NSK_DBG_ASM_CQ = 0, NSK_DBG_ASM_D0 = 1, NSK_DBG_ASM_NODE_CELLS = 2, NSK_DBG_ASM_NODE_OFF = 3,
+       NSK_DBG_ASM_NODE_SELF = 4, NSK_DBG_ASM_PDOF_CELLS = 5 };
+int64_t nsk_debug_asm(struct nsk_handle_s *h, int what, void *out, int64_t cap);
 #ifdef __cplusplus
 }
 #endif
