@@ -31,7 +31,8 @@
  *   -48 NSK_OPT_INNER_MATRIX_PRECISION = 32: a value of F, S or M_p is finite in fp64 but outside the range of fp32
  *   -50..-59 bad arguments of the hand-off calls           -60..-66 device assembly / Newton state
  *   -69, -71..-73 forces / output patches from the resident state (-69: no cells, or no faces / edges handed over; -71:
- *        faces on a P2/P1 handle, edges or patches on the other kind; -72: a cell index out of range; -73: no state)
+ *        faces or a record list on a P2/P1 handle, edges or patches on the other kind; -72: a cell index out of range;
+ *        -73: no state); the record calls also -69 without a record list and -60 for subdivisions outside 1..4
  *   -70 single-launch triangular solve gave up waiting AND the per-colour retry failed too (see NSK_OPT_TRI_SYNC_FREE)
  *   -80..-84 AMG set-up (operator too large for 32-bit indices, rows too wide, rounds / estimates that do not end)
  *   -1 any other exception
@@ -404,6 +405,21 @@ int nsk_forces_set_edges(nsk_handle h, int64_t n_edges, const int32_t *edge_cell
 int nsk_forces(nsk_handle h, double nu, double *drag_lift, double *local_drag_lift /* or NULL */);
 int nsk_state_get_patches(nsk_handle h, int64_t n, const int32_t *cells, double *vel /* 8 per cell */,
                           double *prs /* 4 per cell */);
+/* The VTU record in file layout: the bytes of the file's `velocity` and `pressure` arrays, packed on the
+ * device, optionally on subdivided patches (DataOut::build_patches(n_subdivisions)).
+ * nsk_record_set_cells (Q3/Q2 handles, after nsk_assembly_set_cells): the local cells of the record in file order and
+ *   s = subdivisions in 1..4; for s > 1 the tables W_u[pt][n] = L_a(t_k) L_b(t_l) on the GLL nodes (n = b*4 + a) and
+ *   W_p[pt][m] on {0, 1/2, 1} (m = b*3 + a), pt = l (s+1) + k, t_k = k / s (nsp_record_tables); for s = 1 they may be
+ *   NULL.  Cell indices are checked on the host (-72).  The list, the tables and a result buffer of 4 n_points doubles
+ *   stay on the device until nsk_assembly_set_cells / nsk_assembly_set_simplex void them.  n_cells may be 0.
+ * nsk_state_get_record: points numbered cell by cell, pt as above (s = 1: the vertices (0,0), (1,0), (0,1), (1,1));
+ *   vel3 = (u_x, u_y, +0.0) per point, prs one value per point.  n_points must be n_cells (s+1)^2 (-60).  s = 1 copies
+ *   the bits of the state, owned or ghost, as nsk_state_get_patches does; s > 1: value = sum_n W[pt][n] state[n], n
+ *   increasing, one accumulator, no atomics: two calls give the same bits.  P2/P1 handles (one rank) need no list: the
+ *   record is the mesh's vertices, the first n_p velocity nodes and the pressure DoFs; n_points = n_p. */
+int nsk_record_set_cells(nsk_handle h, int64_t n_cells, const int32_t *cells, int subdivisions,
+                         const double *w_u /* (s+1)^2 x 16 */, const double *w_p /* (s+1)^2 x 9 */);
+int nsk_state_get_record(nsk_handle h, int64_t n_points, double *vel3 /* 3 per point */, double *prs /* 1 per point */);
 /* values of a resident block times a factor: pressure_mass is assembled with 1/nu (:404, :450), block (1,0)
  * changes sign between the Stokes and the Newton phase (:397 against :444) */
 int nsk_scale_values(nsk_handle h, int blk, double factor);

@@ -128,6 +128,12 @@ const int32_t *nsp_face_cell(const nsp_mesh *m);
 const uint8_t *nsp_face_side(const nsp_mesh *m);
 void nsp_face_tables(const nsp_mesh *m, double *out672);
 
+/* Tables of the subdivided VTU record (nsk_record_set_cells): for s = subdivisions in 1..4 and the (s+1)^2 points
+ * pt = l (s+1) + k at t_k = k / s of the reference cell, w_u[pt * 16 + b*4 + a] = L_a(t_k) L_b(t_l) on the GLL nodes and
+ * w_p[pt * 9 + b*3 + a] the same on {0, 1/2, 1}.  Rows at the vertices are exact unit vectors.  Returns 0, or -1 for
+ * another s. */
+int nsp_record_tables(const nsp_mesh *m, int32_t subdivisions, double *w_u, double *w_p);
+
 /* Support points of this rank's owned DoFs (what DoFTools::map_dofs_to_support_points gives the reference's caller):
  * out_xy[2 d], out_xy[2 d + 1] = (x, y) of owned DoF d of `space` (0: velocity, both components of a node share the
  * point; 1: pressure).  Valid after nsp_mesh_create; sizes 2 * (u_end - u_begin) and 2 * (p_end - p_begin). */

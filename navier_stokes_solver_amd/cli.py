@@ -105,13 +105,54 @@ def _host_postprocess() -> bool:
     return os.environ.get("NSK_HOST_POSTPROCESS", "0") not in ("", "0")
 
 
-def _device_report(ls, pr, nu, name, counter, n_digits, rank=0, nranks=1):
-    """VTU piece of this rank's strip and the forces, both from the device-resident solution (DESIGN 5q): the patches of
-    the strip's cells (`nsk_state_get_patches`) and `nsk_forces` over the strip's obstacle faces, summed over the ranks
-    inside the library.  Returns (drag_force, lift_force)."""
+def vtu_switches(env, read_mesh=False):
+    """(format, subdivisions) of the VTU record from NSK_VTU_FORMAT=ascii|binary (default ascii) and
+    NSK_VTU_SUBDIVISIONS=1..4 (default 1).  ValueError, with the message the drivers exit on, for another value
+    and for the combinations that do not exist: subdivided patches are interpolated on the device into the binary record of
+    the generated mesh, and the host report (NSK_HOST_POSTPROCESS=1) stays the ASCII yardstick."""
+    fmt, sub = env.get("NSK_VTU_FORMAT", "ascii"), env.get("NSK_VTU_SUBDIVISIONS", "1")
+    if fmt not in ("ascii", "binary"):
+        raise ValueError(f"NSK_VTU_FORMAT={fmt}: the values are ascii and binary")
+    if sub not in ("1", "2", "3", "4"):
+        raise ValueError(f"NSK_VTU_SUBDIVISIONS={sub}: the values are 1, 2, 3 and 4")
+    host = env.get("NSK_HOST_POSTPROCESS", "0") not in ("", "0")
+    if int(sub) > 1:
+        for bad, why in ((fmt == "ascii", "needs NSK_VTU_FORMAT=binary"), (bool(read_mesh), "does not apply to -M (P2/P1 triangles)"),
+                         (host, "does not go with NSK_HOST_POSTPROCESS=1")):
+            if bad:
+                raise ValueError(f"NSK_VTU_SUBDIVISIONS={sub} {why}")
+    if fmt == "binary" and host:
+        raise ValueError("NSK_VTU_FORMAT=binary does not go with NSK_HOST_POSTPROCESS=1")
+    return fmt, int(sub)
+
+
+def _make_record(ls, pr, cfg, rank=0):
+    """NSK_VTU_FORMAT=binary: the record list on the handle (`nsk_record_set_cells`) and the file image of this rank's
+    strip, once per run and rank; None for the ASCII record."""
+    if cfg.get("vtu_format", "ascii") != "binary":
+        return None
     import numpy as np
 
     from . import postprocess as PP
+    own = np.nonzero(pr.cell_in_strip)[0]
+    s = cfg.get("vtu_subdivisions", 1)
+    ls.set_record(own, s)
+    return PP.VtuRecord.quads(pr.cell_ij[own], PP.LX / pr.info["nx"], PP.LY / pr.info["ny"], s, rank)
+
+
+def _device_report(ls, pr, nu, name, counter, n_digits, rank=0, nranks=1, record=None):
+    """VTU piece of this rank's strip and the forces, both from the device-resident solution (DESIGN 5q): the patches of
+    the strip's cells (`nsk_state_get_patches`) and `nsk_forces` over the strip's obstacle faces, summed over the ranks
+    inside the library.  `record` (`_make_record`): the piece as raw appended data, its two arrays filled in place by
+    `nsk_state_get_record`.  Returns (drag_force, lift_force)."""
+    import numpy as np
+
+    from . import postprocess as PP
+    if record is not None:
+        ls.state_record(vel3=record.vel3, prs=record.prs)
+        PP.write_vtu_record(record, os.environ.get("NSK_OUTPUT_DIR", "./"), name, counter, n_digits=n_digits, rank=rank,
+                            nranks=nranks)
+        return ls.forces(nu)
     own = np.nonzero(pr.cell_in_strip)[0]
     vel, prs = ls.state_patches(own)
     PP.write_vtu_patches(os.environ.get("NSK_OUTPUT_DIR", "./"), name, counter, pr.cell_ij[own], PP.LX / pr.info["nx"],
@@ -119,14 +160,14 @@ def _device_report(ls, pr, nu, name, counter, n_digits, rank=0, nranks=1):
     return ls.forces(nu)
 
 
-def _report(backend, nx, ny, nu, inlet_u, name, counter, n_digits, pr=None):
+def _report(backend, nx, ny, nu, inlet_u, name, counter, n_digits, pr=None, record=None):
     """What the reference's main() / time loop does with the solution (testStationary.cpp:133-136,
     NSSolver.cpp:830-833): VTU record, lift and drag forces over boundary id 10, their coefficients.  `pr`: the
     hand-off whose faces were given to the handle (`set_forces`) — then both come from the device-resident solution."""
     from . import postprocess as PP
     print("===============================================")
     if pr is not None and not _host_postprocess():
-        drag, lift = _device_report(backend.ls, pr, nu, name, counter, n_digits)
+        drag, lift = _device_report(backend.ls, pr, nu, name, counter, n_digits, record=record)
     else:
         u, p = backend.solution()
         PP.write_vtu(os.environ.get("NSK_OUTPUT_DIR", "./"), name, counter, nx, ny, u, p, n_digits=n_digits)
@@ -173,18 +214,34 @@ def run_gmsh(cfg, unsteady: bool) -> int:
         _env_options(ls, S)
 
     device_forces = False
+    binary = cfg.get("vtu_format", "ascii") == "binary"
+    records = {}          # NSK_VTU_FORMAT=binary: the pieces' file images, built at the first report
+
+    def write_piece(path, u, p, r=None):
+        if not binary:
+            SX.write_vtu(path, space, u, p, cells=None if r is None else np.nonzero(backend.layout.cell_rank == r)[0])
+            return
+        if r not in records:
+            records[r] = PP.VtuRecord.triangles(space.mesh.nodes, space.cell_p if r is None else
+                                                space.cell_p[backend.layout.cell_rank == r])
+        rec = records[r]
+        if u is None:                       # one rank, device assembly: the vertices' values from the resident state
+            ls.state_record(vel3=rec.vel3, prs=rec.prs)
+        else:
+            rec.vel3[:, 0], rec.vel3[:, 1], rec.prs[:] = u[0:2 * space.n_p:2], u[1:2 * space.n_p:2], p[:space.n_p]
+        rec.write(path)
 
     def report(name, nu, inlet_u):
-        u, p = backend.solution()
+        u, p = (None, None) if binary and device_forces else backend.solution()
         out_dir = os.environ.get("NSK_OUTPUT_DIR", "./")
         if nranks > 1 and not unsteady:     # every rank writes its own piece, rank 0 the record naming them (.cpp:793-796)
             stem = name[:-4]
             pieces = [f"{stem}.{r}.vtu" for r in range(nranks)]
             for r in range(nranks):
-                SX.write_vtu(os.path.join(out_dir, pieces[r]), space, u, p, cells=np.nonzero(backend.layout.cell_rank == r)[0])
+                write_piece(os.path.join(out_dir, pieces[r]), u, p, r)
             SX.write_pvtu(os.path.join(out_dir, stem + ".pvtu"), pieces)
         else:
-            SX.write_vtu(os.path.join(out_dir, name), space, u, p)
+            write_piece(os.path.join(out_dir, name), u, p)
         # (the reference prints this fixed name in both drivers, whatever file DataOut wrote)
         print("===============================================\nOutput written to output-stokes")
         print("===============================================\n===============================================\nComputing lift and drag forces")
@@ -323,8 +380,10 @@ def _rank_main(cfg, unsteady, r, nranks, grp, make_handle, say):
                                   plan=plan)
 
         host_report = _host_postprocess()
+        record = None
         if not host_report:
             ls.set_forces(first)
+            record = _make_record(ls, first, cfg, rank=r)
 
         def report(nu, inlet_u, name, counter, n_digits):
             say("===============================================")
@@ -338,7 +397,7 @@ def _rank_main(cfg, unsteady, r, nranks, grp, make_handle, say):
                 drag, lift = sum(f[0] for f in forces), sum(f[1] for f in forces)
             else:
                 # rank-local: the strip's patches and faces from the resident state; nsk_forces sums over the ranks
-                drag, lift = _device_report(ls, first, nu, name, counter, n_digits, rank=r, nranks=nranks)
+                drag, lift = _device_report(ls, first, nu, name, counter, n_digits, rank=r, nranks=nranks, record=record)
             say("Output written to output-stokes")
             say("===============================================")
             say("===============================================\nComputing lift and drag forces")
@@ -446,6 +505,12 @@ def run_processes(cfg, unsteady: bool) -> int:
 def run(cfg, unsteady: bool) -> int:
     from . import problem as P
     from . import solver as S
+    if cfg.get("vtu_format", "ascii") == "binary":
+        s = cfg.get("vtu_subdivisions", 1)
+        # (-M on several ranks or with NSK_HOST_ASSEMBLY: the values come from the host backend)
+        host = cfg["read_mesh"] and (int(os.environ.get("NSK_RANKS", "1")) > 1 or bool(os.environ.get("NSK_HOST_ASSEMBLY")))
+        print("[nsk] NSK_VTU_FORMAT=binary: the VTU record as raw appended data" + ("" if host else ", packed on the device")
+              + (f", {s} x {s} patches per cell" if s > 1 else ""))
     if cfg["read_mesh"]:
         return run_gmsh(cfg, unsteady)
     if cfg["prec"] not in PRECS:
@@ -472,11 +537,12 @@ def run(cfg, unsteady: bool) -> int:
         first_system = P.generate(nx, ny, nu=0.1, mode=0, state=0, inlet_bc=1, U=0.1)   # first level: nu = 1/10
         backend = N.DeviceBackend(ls, first_system, cfg["solver"], cfg["prec"], cfg["tol"])
         ls.set_forces(first_system)
+        record = _make_record(ls, first_system, cfg)
         t0 = time.time()
         try:
             N.solve_newton(backend, cfg["Re"])
             _report(backend, nx, ny, 1.0 / max(l for l in _levels(10.0, 20.0, cfg["Re"])), 1.0, "output-stokes", 0, None,
-                    pr=first_system)
+                    pr=first_system, record=record)
         finally:
             dt = time.time() - t0
             n = info["n_u_global"] + info["n_p_global"]
@@ -494,11 +560,13 @@ def run(cfg, unsteady: bool) -> int:
     backend = N.DeviceBackend(ls, first_system, cfg["solver"], cfg["prec"], cfg["tol"], max_iter=100000,
                               inv_dt=1.0 / cfg["dt"])
     ls.set_forces(first_system)
+    record = _make_record(ls, first_system, cfg)
     t0 = time.time()
     try:
         nu_last = 1.0 / max(_levels(1.0, 10.0, cfg["Re"]))
         N.time_loop(backend, cfg["T"], cfg["dt"], cfg["Re"],
-                    after_step=lambda step: _report(backend, nx, ny, nu_last, 0.3, "output", step, 3, pr=first_system))
+                    after_step=lambda step: _report(backend, nx, ny, nu_last, 0.3, "output", step, 3, pr=first_system,
+                                                    record=record))
     finally:
         dt = time.time() - t0
         n = info["n_u_global"] + info["n_p_global"]
@@ -518,6 +586,11 @@ def main(argv=None) -> int:
     cfg, rc = parse(argv[1:], unsteady)
     if cfg is None:
         return rc
+    try:
+        cfg["vtu_format"], cfg["vtu_subdivisions"] = vtu_switches(os.environ, cfg["read_mesh"])
+    except ValueError as e:
+        sys.stderr.write(f"Error: {e}\n")
+        return 1
     if "TORCHELASTIC_RUN_ID" in os.environ and int(os.environ.get("RANK", "0")) != 0:
         import contextlib
         with open(os.devnull, "w") as null, contextlib.redirect_stdout(null):   # pcout: rank 0 speaks (errors go to stderr)

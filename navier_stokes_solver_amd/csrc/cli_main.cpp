@@ -11,7 +11,8 @@
 //   NSSolver runs the reference's time loop (NSSolver::solve(), NSSolver.cpp:799-837) with one solve_newton()
 //   (NSSolver.cpp:674-754) per step; the device assembly carries the mass term and the solution_old term.
 //   Both then do what the reference's main() / time loop does with the solution (testStationary.cpp:133-136,
-//   NSSolver.cpp:830-833): the VTU record (vtu_patches.hpp, from nsk_state_get_patches) and the lift / drag coefficients
+//   NSSolver.cpp:830-833): the VTU record (vtu_patches.hpp, from nsk_state_get_patches or,
+//   with NSK_VTU_FORMAT=binary, nsk_state_get_record) and the lift / drag coefficients
 //   of the cylinder (nsk_forces) — once after solve_newton(), once per time step; SURVEY 8f row 4.
 //
 // Built twice from this file: -DNSK_UNSTEADY=0 -> StationaryNSSolver, -DNSK_UNSTEADY=1 -> NSSolver.
@@ -23,6 +24,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
+#include <memory>
 #include <stdexcept>
 #include <vector>
 
@@ -54,12 +56,33 @@ static void check(nsk_handle h, int rc, const char *what) {
 
 // What both drivers do with a converged solution: NSSolverStationary::output() + compute_lift_drag() and the coefficient
 // lines of compute_lift_coeff() / compute_drag_coeff() (.cpp:765-919), from the device-resident solution.
+// NSK_VTU_FORMAT=ascii|binary (default ascii) and NSK_VTU_SUBDIVISIONS=1..4 (default 1), DESIGN 5s: the switches of the
+// Python drivers.  Returns the message to exit on, or an empty string.
+struct VtuSwitches {
+  bool binary = false;
+  int subdivisions = 1;
+};
+static std::string vtu_switches(VtuSwitches &out) {
+  const char *f = std::getenv("NSK_VTU_FORMAT"), *s = std::getenv("NSK_VTU_SUBDIVISIONS"), *hp = std::getenv("NSK_HOST_POSTPROCESS");
+  const std::string fmt = f ? f : "ascii", sub = s ? s : "1";
+  if (fmt != "ascii" && fmt != "binary") return "NSK_VTU_FORMAT=" + fmt + ": the values are ascii and binary";
+  if (sub != "1" && sub != "2" && sub != "3" && sub != "4") return "NSK_VTU_SUBDIVISIONS=" + sub + ": the values are 1, 2, 3 and 4";
+  const bool host = hp && *hp && std::string(hp) != "0";
+  out.binary = fmt == "binary";
+  out.subdivisions = sub[0] - '0';
+  if (out.subdivisions > 1 && !out.binary) return "NSK_VTU_SUBDIVISIONS=" + sub + " needs NSK_VTU_FORMAT=binary";
+  if (out.subdivisions > 1 && host) return "NSK_VTU_SUBDIVISIONS=" + sub + " does not go with NSK_HOST_POSTPROCESS=1";
+  if (out.binary && host) return "NSK_VTU_FORMAT=binary does not go with NSK_HOST_POSTPROCESS=1";
+  return "";
+}
+
 struct Report {
   nsk_handle h;
   double nu, inlet_u, hx, hy;
   std::vector<int32_t> cells, ij;     // this rank's strip: local cell ids and their (i, j)
   std::vector<double> vel, prs;
-  Report(nsk_handle h_, const nsp_mesh *mesh, const nsp_info &info, double nu_, double inlet_u_)
+  std::unique_ptr<vtu::Record> record;   // NSK_VTU_FORMAT=binary: the file image, built once
+  Report(nsk_handle h_, const nsp_mesh *mesh, const nsp_info &info, double nu_, double inlet_u_, const VtuSwitches &sw)
       : h(h_), nu(nu_), inlet_u(inlet_u_), hx(2.2 / info.nx), hy(0.41 / info.ny) {
     const int64_t nc = nsp_n_cells_local(mesh);
     const int32_t *cij = nsp_cell_ij(mesh);
@@ -72,13 +95,25 @@ struct Report {
     nsp_face_tables(mesh, tab);
     check(h, nsk_forces_set_faces(h, nsp_n_obstacle_faces(mesh), nsp_face_cell(mesh), nsp_face_side(mesh), tab),
           "nsk_forces_set_faces");
+    if (sw.binary) {
+      const int s = sw.subdivisions;
+      std::vector<double> wu((size_t)(s + 1) * (s + 1) * 16), wp((size_t)(s + 1) * (s + 1) * 9);
+      if (nsp_record_tables(mesh, s, wu.data(), wp.data()) != 0) throw std::runtime_error("nsp_record_tables failed");
+      check(h, nsk_record_set_cells(h, (int64_t)cells.size(), cells.data(), s, wu.data(), wp.data()), "nsk_record_set_cells");
+      record = vtu::quad_record((int64_t)cells.size(), ij.data(), hx, hy, s, 0);
+    }
   }
   void operator()(const char *name, unsigned counter, int n_digits) {
     std::cout << "===============================================" << std::endl;
-    check(h, nsk_state_get_patches(h, (int64_t)cells.size(), cells.data(), vel.data(), prs.data()), "nsk_state_get_patches");
     const char *dir = std::getenv("NSK_OUTPUT_DIR");
-    vtu::write_patches(dir ? dir : "./", name, vtu::counter_text(counter, n_digits), (int64_t)cells.size(), ij.data(), hx, hy,
-                       vel.data(), prs.data(), 0, 1);
+    if (record) {   // the two arrays of the file, filled in place, and one write
+      check(h, nsk_state_get_record(h, record->n_points(), record->vel3(), record->prs()), "nsk_state_get_record");
+      record->write(dir ? dir : "./", name, vtu::counter_text(counter, n_digits), 0, 1);
+    } else {
+      check(h, nsk_state_get_patches(h, (int64_t)cells.size(), cells.data(), vel.data(), prs.data()), "nsk_state_get_patches");
+      vtu::write_patches(dir ? dir : "./", name, vtu::counter_text(counter, n_digits), (int64_t)cells.size(), ij.data(), hx, hy,
+                         vel.data(), prs.data(), 0, 1);
+    }
     std::cout << "Output written to output-stokes" << std::endl;   // the reference prints this name in both drivers
     std::cout << "===============================================" << std::endl;
     std::cout << "===============================================\nComputing lift and drag forces" << std::endl;
@@ -322,6 +357,14 @@ int main(int argc, char *argv[]) {
     return 1;
   }
 
+  VtuSwitches vtu_sw;
+  {
+    std::string msg = vtu_switches(vtu_sw);
+    if (msg.empty() && vtu_sw.subdivisions > 1 && read_mesh_from_file)
+      msg = "NSK_VTU_SUBDIVISIONS=" + std::to_string(vtu_sw.subdivisions) + " does not apply to -M (P2/P1 triangles)";
+    if (!msg.empty()) { std::cerr << "Error: " << msg << "\n"; return 1; }
+  }
+
   std::cout << "--------- CONFIGURATION PARAMETERS --------- \n";
   if (NSK_UNSTEADY) std::cout << "Time span: " << time_span << "\nTime step: " << time_step << "\n";
   std::cout << "Mesh size: " << mesh_size_x << "x" << mesh_size_y << "\nReynolds number: " << Re << "\nSolver type: ";
@@ -337,6 +380,11 @@ int main(int argc, char *argv[]) {
   if (read_mesh_from_file) {
     std::cerr << "-M (gmsh P2/P1 mesh from file): host assembly lives in the Python driver — python -m navier_stokes_solver_amd.cli StationaryNSSolver -M FILE ...\n";
     return 1;
+  }
+  if (vtu_sw.binary) {
+    std::printf("[nsk] NSK_VTU_FORMAT=binary: the VTU record as raw appended data, packed on the device");
+    if (vtu_sw.subdivisions > 1) std::printf(", %d x %d patches per cell", vtu_sw.subdivisions, vtu_sw.subdivisions);
+    std::printf("\n");
   }
   nsk_handle h = nullptr;
   nsp_mesh *mesh = nullptr;
@@ -403,7 +451,7 @@ int main(int argc, char *argv[]) {
       // drivers report with
       double last_Re = NSK_UNSTEADY ? 1.0 : 10.0;
       while (last_Re + (NSK_UNSTEADY ? 10.0 : 20.0) <= Re) last_Re += NSK_UNSTEADY ? 10.0 : 20.0;
-      Report report(h, mesh, info, 1.0 / last_Re, NSK_UNSTEADY ? 0.3 : 1.0);
+      Report report(h, mesh, info, 1.0 / last_Re, NSK_UNSTEADY ? 0.3 : 1.0, vtu_sw);
       const auto t0 = std::chrono::steady_clock::now();
       if (NSK_UNSTEADY) drv.time_loop(time_span, time_step, Re, report);
       else {

@@ -50,6 +50,11 @@ void forces_faces(hipStream_t s, const AsmMesh &M, long n_faces, const int *face
 // (u_x, u_y) [8 per cell] and p [4 per cell] at the four vertices of the listed cells: the bits of the state
 void state_patches(hipStream_t s, const AsmMesh &M, long n, const int *cells, const double *su, const double *sp, double *vel,
                    double *prs);
+// The VTU record in file layout: for the listed cells and pt = l (s + 1) + k, s = subdivisions in 1..4,
+// (u_x, u_y, +0.0) into vel3 and p into prs.  s = 1: the bits of the state at the vertices; s > 1: the sums over the
+// cell's 16 nodes / 9 DoFs with wu[(s+1)^2][16], wp[(s+1)^2][9], n increasing, one accumulator.  One launch, no atomics.
+void state_record(hipStream_t s, const AsmMesh &M, long n_cells, int subdivisions, const int *cells, const double *wu,
+                  const double *wp, const double *su, const double *sp, double *vel3, double *prs);
 
 // ---- P2/P1 on triangles (general cells; the reference's -M path) ----
 struct SimplexMesh {  // device pointers
@@ -75,5 +80,7 @@ void simplex_assemble(hipStream_t s, const SimplexMesh &M, const double *su, con
 // forces over the id-10 edges: edge_cell, edge_local (the cell's local edge 0-2), edge_nl = (nx, ny, length) per edge
 void forces_edges(hipStream_t s, const SimplexMesh &M, long n_edges, const int *edge_cell, const unsigned char *edge_local,
                   const double *edge_nl, const double *su, const double *sp, double nu, double *slots, double *out2);
+// the record of the mesh's vertices: the first n_points velocity nodes and pressure DoFs, (u_x, u_y, +0.0) and p
+void simplex_record(hipStream_t s, long n_points, const double *su, const double *sp, double *vel3, double *prs);
 
 }  // namespace nsk

@@ -360,6 +360,55 @@ __global__ __launch_bounds__(BLK) void state_patches_kernel(long n, const int *_
   prs[t] = sp[cell_p[cell * 9 + pn]];
 }
 
+// The VTU record in file layout: per point (u_x, u_y, +0.0) into vel3 and p into prs, the points numbered
+// cell by cell, pt = l (s + 1) + k inside a cell.  One thread per point.
+// s = 1: the vertices of state_patches_kernel, copied.
+__global__ __launch_bounds__(BLK) void state_record_copy_kernel(long n_points, const int *__restrict__ cells,
+                                                                const int *__restrict__ cell_u, const int *__restrict__ cell_p,
+                                                                const double *__restrict__ su, const double *__restrict__ sp,
+                                                                double *__restrict__ vel3, double *__restrict__ prs) {
+  const long t = (long)blockIdx.x * BLK + threadIdx.x;
+  if (t >= n_points) return;
+  const long cell = cells[t >> 2];
+  const int v = (int)(t & 3);
+  const int un = v == 0 ? 0 : v == 1 ? 3 : v == 2 ? 12 : 15, pn = v == 0 ? 0 : v == 1 ? 2 : v == 2 ? 6 : 8;
+  const int node = cell_u[cell * 16 + un];
+  const double2 uv = *reinterpret_cast<const double2 *>(su + 2 * (size_t)node);
+  vel3[3 * t] = uv.x;
+  vel3[3 * t + 1] = uv.y;
+  vel3[3 * t + 2] = 0.0;
+  prs[t] = sp[cell_p[cell * 9 + pn]];
+}
+
+// s > 1: build_patches(n_subdivisions) — the cell's 16 velocity nodes and 9 pressure DoFs interpolated at the ppc =
+// (s + 1)^2 lattice points of the cell with the tables wu[pt][16], wp[pt][9] (postprocess.record_tables).  One chain per
+// value, n increasing, one accumulator: two calls give the same bits, and a table row that is a unit vector (a vertex
+// point) returns the entry of the state.
+__global__ __launch_bounds__(BLK) void state_record_kernel(long n_points, int ppc, const int *__restrict__ cells,
+                                                           const int *__restrict__ cell_u, const int *__restrict__ cell_p,
+                                                           const double *__restrict__ wu, const double *__restrict__ wp,
+                                                           const double *__restrict__ su, const double *__restrict__ sp,
+                                                           double *__restrict__ vel3, double *__restrict__ prs) {
+  const long t = (long)blockIdx.x * BLK + threadIdx.x;
+  if (t >= n_points) return;
+  const long cell = cells[t / ppc];
+  const int pt = (int)(t % ppc);
+  const double *W = wu + pt * 16;
+  double ux = 0.0, uy = 0.0, p = 0.0;
+  for (int n = 0; n < 16; ++n) {
+    const int node = cell_u[cell * 16 + n];
+    const double2 uv = *reinterpret_cast<const double2 *>(su + 2 * (size_t)node);
+    ux += W[n] * uv.x;
+    uy += W[n] * uv.y;
+  }
+  const double *Wp = wp + pt * 9;
+  for (int m = 0; m < 9; ++m) p += Wp[m] * sp[cell_p[cell * 9 + m]];
+  vel3[3 * t] = ux;
+  vel3[3 * t + 1] = uy;
+  vel3[3 * t + 2] = 0.0;
+  prs[t] = p;
+}
+
 }  // namespace
 
 static void forces_sum(hipStream_t s, long n_slots, const double *slots, double *out2) {
@@ -416,6 +465,19 @@ void asm_rhs_u(hipStream_t s, const AsmMesh &M, const double *cq, double nu, dou
 void asm_rhs_p(hipStream_t s, const AsmMesh &M, const double *cq, int stokes, double *rhs) {
   if (M.n_pdofs > 0)
     hipLaunchKernelGGL(asm_rhs_p_kernel, dim3((unsigned)((M.n_pdofs + BLK - 1) / BLK)), dim3(BLK), 0, s, M, cq, stokes, rhs);
+}
+
+void state_record(hipStream_t s, const AsmMesh &M, long n_cells, int subdivisions, const int *cells, const double *wu,
+                  const double *wp, const double *su, const double *sp, double *vel3, double *prs) {
+  const int ppc = (subdivisions + 1) * (subdivisions + 1);
+  const long n_points = n_cells * ppc;
+  if (n_points <= 0) return;
+  const dim3 grid((unsigned)((n_points + BLK - 1) / BLK));
+  if (subdivisions == 1)
+    hipLaunchKernelGGL(state_record_copy_kernel, grid, dim3(BLK), 0, s, n_points, cells, M.cell_u, M.cell_p, su, sp, vel3, prs);
+  else
+    hipLaunchKernelGGL(state_record_kernel, grid, dim3(BLK), 0, s, n_points, ppc, cells, M.cell_u, M.cell_p, wu, wp, su, sp,
+                       vel3, prs);
 }
 
 }  // namespace nsk
@@ -641,7 +703,26 @@ __global__ __launch_bounds__(256) void forces_edges_kernel(long n_edges, const i
   slots[2 * t + 1] = -(s01 * nx + s11 * ny) * w;
 }
 
+// The VTU record of a P2/P1 mesh in file layout: the mesh's vertices are the first n_points velocity nodes
+// and the pressure DoFs (simplex.py's numbering) — a strided copy, (u_x, u_y, +0.0) per vertex.
+__global__ __launch_bounds__(256) void simplex_record_kernel(long n_points, const double *__restrict__ su,
+                                                             const double *__restrict__ spv, double *__restrict__ vel3,
+                                                             double *__restrict__ prs) {
+  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n_points) return;
+  vel3[3 * t] = su[2 * t];
+  vel3[3 * t + 1] = su[2 * t + 1];
+  vel3[3 * t + 2] = 0.0;
+  prs[t] = spv[t];
+}
+
 }  // namespace
+
+void simplex_record(hipStream_t s, long n_points, const double *su, const double *sp, double *vel3, double *prs) {
+  if (n_points > 0)
+    hipLaunchKernelGGL(simplex_record_kernel, dim3((unsigned)((n_points + 255) / 256)), dim3(256), 0, s, n_points, su, sp, vel3,
+                       prs);
+}
 
 void forces_edges(hipStream_t s, const SimplexMesh &M, long n_edges, const int *edge_cell, const unsigned char *edge_local,
                   const double *edge_nl, const double *su, const double *sp, double nu, double *slots, double *out2) {

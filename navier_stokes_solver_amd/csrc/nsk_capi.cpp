@@ -267,6 +267,12 @@ struct nsk_handle_s {
     DBuf<int> face_cell;
     DBuf<unsigned char> face_side;
     DBuf<double> face_tab, force_slots, force_out;   // 672 doubles | (nx, ny, length) per edge; 2 per point; local + total
+    // the VTU record in file layout (nsk_record_set_cells / nsk_state_get_record): void with the cell data
+    bool record_set = false;
+    long rec_cells = 0;
+    int rec_sub = 1;
+    DBuf<int> rec_cell;
+    DBuf<double> rec_wu, rec_wp, rec_out;   // (s+1)^2 x 16, (s+1)^2 x 9; 3 + 1 doubles per point (P2/P1: per vertex)
   } asmd;
   int matrix_free_f = 0;        // NSK_OPT_INNER_MATRIX_FREE_F
   bool matfree_wanted = false;  // what the last set-up took of it (the option or NSK_INNER_MATRIX_FREE_F)
@@ -1600,6 +1606,7 @@ int nsk_assembly_set_cells(nsk_handle h, int64_t n_cells, const int32_t *cell_u_
   A.d0.alloc(1);
   A.mf_valid = false;   // (cq of another mesh)
   A.forces_set = false;   // (faces index the cells of another mesh)
+  A.record_set = false;   // (so does the record's list)
   if (!A.sol_u) {
     A.sol_u = h->pool_u.get(true); A.eval_u = h->pool_u.get(true); A.old_u = h->pool_u.get(true);
     A.sol_p = h->pool_p.get(true); A.eval_p = h->pool_p.get(true);
@@ -1753,6 +1760,8 @@ int nsk_assembly_set_simplex(nsk_handle h, int64_t n_cells, const int32_t *cell_
   h->ctx.sync();
   A.mf_valid = false;
   A.forces_set = false;   // (edges index the cells of another mesh)
+  A.record_set = false;
+  A.rec_out.release();
   A.simplex = true;
   A.ready = true;
   return 0;
@@ -1914,6 +1923,69 @@ int nsk_state_get_patches(nsk_handle h, int64_t n, const int32_t *cells, double 
   state_patches(s, h->asm_view(), (long)n, dc.p, A.sol_u, A.sol_p, dv.p, dv.p + (size_t)n * 8);
   NSK_HIP(hipMemcpyAsync(vel, dv.p, sizeof(double) * (size_t)n * 8, hipMemcpyDeviceToHost, s));
   NSK_HIP(hipMemcpyAsync(prs, dv.p + (size_t)n * 8, sizeof(double) * (size_t)n * 4, hipMemcpyDeviceToHost, s));
+  h->ctx.sync();
+  return 0;
+  NSK_CATCH(h)
+}
+
+int nsk_record_set_cells(nsk_handle h, int64_t n_cells, const int32_t *cells, int subdivisions, const double *w_u,
+                         const double *w_p) {
+  NSK_TRY(h)
+  (void)hipSetDevice(h->ctx.device);
+  auto &A = h->asmd;
+  if (!A.ready) throw Error(-69, "nsk_record_set_cells: no cells on the handle (call nsk_assembly_set_cells first)");
+  if (A.simplex) throw Error(-71, "nsk_record_set_cells: the handle holds P2/P1 triangles (their record is the mesh's vertices)");
+  if (subdivisions < 1 || subdivisions > 4) throw Error(-60, "nsk_record_set_cells: subdivisions outside 1..4");
+  if (n_cells < 0 || (n_cells > 0 && !cells) || (subdivisions > 1 && (!w_u || !w_p)))
+    throw Error(-60, "nsk_record_set_cells: bad arguments");
+  const int64_t ppc = (int64_t)(subdivisions + 1) * (subdivisions + 1);
+  if (n_cells > INT64_MAX / (4 * ppc * (int64_t)sizeof(double))) throw Error(-60, "nsk_record_set_cells: bad arguments");
+  // what the kernel indexes with: checked on the host before anything is launched
+  for (int64_t c = 0; c < n_cells; ++c)
+    if (cells[c] < 0 || cells[c] >= A.n_cells) throw Error(-72, "nsk_record_set_cells: cell index out of range");
+  hipStream_t s = h->s();
+  A.record_set = false;
+  A.rec_cell.upload(cells, (size_t)n_cells, s);
+  if (subdivisions > 1) {
+    A.rec_wu.upload(w_u, (size_t)ppc * 16, s);
+    A.rec_wp.upload(w_p, (size_t)ppc * 9, s);
+  } else {
+    A.rec_wu.release();
+    A.rec_wp.release();
+  }
+  A.rec_out.alloc((size_t)std::max<int64_t>(1, n_cells * ppc * 4));
+  h->ctx.sync();
+  A.rec_cells = (long)n_cells;
+  A.rec_sub = subdivisions;
+  A.record_set = true;
+  return 0;
+  NSK_CATCH(h)
+}
+
+int nsk_state_get_record(nsk_handle h, int64_t n_points, double *vel3, double *prs) {
+  NSK_TRY(h)
+  (void)hipSetDevice(h->ctx.device);
+  auto &A = h->asmd;
+  if (!A.ready) throw Error(-69, "nsk_state_get_record: no cells on the handle");
+  if (!A.simplex && !A.record_set) throw Error(-69, "nsk_state_get_record: no record list handed over (nsk_record_set_cells)");
+  if (!A.state_set) throw Error(-73, "nsk_state_get_record: no state on the device");
+  const int64_t want = A.simplex ? (int64_t)h->n_p() : (int64_t)A.rec_cells * (A.rec_sub + 1) * (A.rec_sub + 1);
+  if (n_points != want || (n_points > 0 && (!vel3 || !prs)))
+    throw Error(-60, "nsk_state_get_record: bad arguments (n_points is not the record's number of points)");
+  if (n_points == 0) return 0;
+  hipStream_t s = h->s();
+  if (A.simplex) {
+    // the vertices are the first n_p velocity nodes (simplex.py's numbering); one rank: the state is [owned]
+    if (h->ctx.comm.nranks > 1 || 2 * n_points > (int64_t)h->n_u())
+      throw Error(-60, "nsk_state_get_record: the P2/P1 record covers one rank with the vertices numbered first");
+    if (A.rec_out.n != (size_t)n_points * 4) A.rec_out.alloc((size_t)n_points * 4);
+    simplex_record(s, (long)n_points, A.sol_u, A.sol_p, A.rec_out.p, A.rec_out.p + (size_t)n_points * 3);
+  } else {
+    state_record(s, h->asm_view(), A.rec_cells, A.rec_sub, A.rec_cell.p, A.rec_wu.p, A.rec_wp.p, A.sol_u, A.sol_p, A.rec_out.p,
+                 A.rec_out.p + (size_t)n_points * 3);
+  }
+  NSK_HIP(hipMemcpyAsync(vel3, A.rec_out.p, sizeof(double) * (size_t)n_points * 3, hipMemcpyDeviceToHost, s));
+  NSK_HIP(hipMemcpyAsync(prs, A.rec_out.p + (size_t)n_points * 3, sizeof(double) * (size_t)n_points, hipMemcpyDeviceToHost, s));
   h->ctx.sync();
   return 0;
   NSK_CATCH(h)

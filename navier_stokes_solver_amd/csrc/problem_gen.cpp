@@ -908,6 +908,24 @@ int64_t nsp_n_obstacle_faces(const nsp_mesh *m) { return (int64_t)m->face_cell.s
 const int32_t *nsp_face_cell(const nsp_mesh *m) { return m->face_cell.data(); }
 const uint8_t *nsp_face_side(const nsp_mesh *m) { return m->face_side.data(); }
 void nsp_face_tables(const nsp_mesh *m, double *out) { std::memcpy(out, m->T.face, sizeof(m->T.face)); }
+int nsp_record_tables(const nsp_mesh *m, int32_t s, double *w_u, double *w_p) {
+  if (!m || s < 1 || s > 4 || !w_u || !w_p) return -1;
+  double l3[5][4], l2[5][3], dd[4];
+  for (int k = 0; k <= s; ++k) {
+    const double t = (double)k / (double)s;
+    lagrange(m->T.gll, 4, t, l3[k], dd);
+    lagrange(m->T.q2, 3, t, l2[k], dd);
+  }
+  for (int l = 0; l <= s; ++l)
+    for (int k = 0; k <= s; ++k) {
+      const int pt = l * (s + 1) + k;
+      for (int b = 0; b < 4; ++b)
+        for (int a = 0; a < 4; ++a) w_u[pt * 16 + b * 4 + a] = l3[k][a] * l3[l][b];
+      for (int b = 0; b < 3; ++b)
+        for (int a = 0; a < 3; ++a) w_p[pt * 9 + b * 3 + a] = l2[k][a] * l2[l][b];
+    }
+  return 0;
+}
 
 // Support points of this rank's owned DoFs (DoFTools::map_dofs_to_support_points): out_xy[2 d], out_xy[2 d + 1] for
 // owned DoF d of the space (0 velocity: both components of a node share the point; 1 pressure).

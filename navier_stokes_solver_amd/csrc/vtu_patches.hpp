@@ -5,13 +5,16 @@
 // build_patches() does, every cell is one patch with its own four vertices; point data `velocity` (3 components, z = 0),
 // `pressure`, `partitioning`.  ASCII XML in exactly the layout of the Python writer (postprocess.write_vtu_patches):
 // numbers as %.12g, one point per line.  The values come from nsk_state_get_patches: per cell (u_x, u_y) and p at the
-// vertices (0,0), (1,0), (0,1), (1,1).
+// vertices (0,0), (1,0), (0,1), (1,1).  NSK_VTU_FORMAT=binary: the same piece as raw appended data (Record, below).
 #pragma once
 #include <cstdint>
 #include <cstdio>
+#include <cstring>
 #include <filesystem>
+#include <memory>
 #include <stdexcept>
 #include <string>
+#include <vector>
 
 namespace vtu {
 
@@ -20,6 +23,23 @@ inline std::string counter_text(unsigned counter, int n_digits) {
   if (n_digits > 0) std::snprintf(buf, sizeof(buf), "%0*u", n_digits, counter);
   else std::snprintf(buf, sizeof(buf), "%u", counter);
   return buf;
+}
+
+// the record <name>_<cnt>.pvtu naming the pieces of all ranks
+inline void write_pvtu(const std::filesystem::path &dir, const std::string &name, const std::string &cnt, int nranks) {
+  const std::string record = (dir / (name + "_" + cnt + ".pvtu")).string();
+  std::FILE *f = std::fopen(record.c_str(), "w");
+  if (!f) throw std::runtime_error("cannot write " + record);
+  std::fprintf(f, "<?xml version=\"1.0\"?>\n<VTKFile type=\"PUnstructuredGrid\" version=\"0.1\" byte_order=\"LittleEndian\">\n"
+                  "<PUnstructuredGrid GhostLevel=\"0\">\n<PPointData Scalars=\"scalars\">\n"
+                  "<PDataArray type=\"Float64\" Name=\"velocity\" NumberOfComponents=\"3\" format=\"ascii\"/>\n"
+                  "<PDataArray type=\"Float64\" Name=\"pressure\" format=\"ascii\"/>\n"
+                  "<PDataArray type=\"Float64\" Name=\"partitioning\" format=\"ascii\"/>\n</PPointData>\n<PPoints>\n"
+                  "<PDataArray type=\"Float64\" NumberOfComponents=\"3\"/>\n</PPoints>\n");
+  for (int r = 0; r < nranks; ++r)
+    std::fprintf(f, "%s<Piece Source=\"%s_%s.%d.vtu\"/>", r ? "\n" : "", name.c_str(), cnt.c_str(), r);
+  std::fprintf(f, "\n</PUnstructuredGrid>\n</VTKFile>\n");
+  if (std::fclose(f) != 0) throw std::runtime_error("cannot write " + record);
 }
 
 // ij: (i, j) per cell; vel: 8 doubles per cell; prs: 4 per cell.  Returns the path of the piece.
@@ -56,21 +76,123 @@ inline std::string write_patches(const std::string &directory, const std::string
   for (long long p = 0; p < n_pts; ++p) std::fprintf(f, "%s%d.0", p ? " " : "", rank);
   std::fprintf(f, "\n</DataArray>\n</PointData>\n</Piece>\n</UnstructuredGrid>\n</VTKFile>\n");
   if (std::fclose(f) != 0) throw std::runtime_error("cannot write " + piece);
-  if (rank != 0) return piece;
-  const std::string record = (dir / (name + "_" + cnt + ".pvtu")).string();
-  f = std::fopen(record.c_str(), "w");
-  if (!f) throw std::runtime_error("cannot write " + record);
-  std::fprintf(f, "<?xml version=\"1.0\"?>\n<VTKFile type=\"PUnstructuredGrid\" version=\"0.1\" byte_order=\"LittleEndian\">\n"
-                  "<PUnstructuredGrid GhostLevel=\"0\">\n<PPointData Scalars=\"scalars\">\n"
-                  "<PDataArray type=\"Float64\" Name=\"velocity\" NumberOfComponents=\"3\" format=\"ascii\"/>\n"
-                  "<PDataArray type=\"Float64\" Name=\"pressure\" format=\"ascii\"/>\n"
-                  "<PDataArray type=\"Float64\" Name=\"partitioning\" format=\"ascii\"/>\n</PPointData>\n<PPoints>\n"
-                  "<PDataArray type=\"Float64\" NumberOfComponents=\"3\"/>\n</PPoints>\n");
-  for (int r = 0; r < nranks; ++r)
-    std::fprintf(f, "%s<Piece Source=\"%s_%s.%d.vtu\"/>", r ? "\n" : "", name.c_str(), cnt.c_str(), r);
-  std::fprintf(f, "\n</PUnstructuredGrid>\n</VTKFile>\n");
-  if (std::fclose(f) != 0) throw std::runtime_error("cannot write " + record);
+  if (rank == 0) write_pvtu(dir, name, cnt, nranks);
   return piece;
+}
+
+// The piece as VTK XML with raw appended data (postprocess.VtuRecord writes the same bytes from the same
+// arrays): the XML header, then after <AppendedData encoding="raw"> and `_` the blocks — a UInt64 byte count and that many
+// bytes each — points, velocity, pressure, [partitioning,] connectivity, offsets, types.  The header is padded with blanks
+// so that the first block starts at a multiple of 8 in the file.  Built once per run and rank with everything but velocity
+// and pressure filled in; a report fills vel3() / prs() (nsk_state_get_record) and writes the image with one write.
+class Record {
+ public:
+  // points: 3 doubles per point; rank < 0: no partitioning array
+  Record(int64_t n_points, const double *points, const std::vector<int32_t> &conn, const std::vector<int32_t> &offsets,
+         const std::vector<uint8_t> &types, int rank, const char *declaration = "<?xml version=\"1.0\" ?>",
+         const char *point_data = "Scalars=\"scalars\"")
+      : n_points_(n_points) {
+    const size_t n = (size_t)n_points, m = offsets.size();
+    if (types.size() != m) throw std::runtime_error("vtu::Record: offsets and types do not match");
+    const bool part = rank >= 0;
+    // byte counts in block order
+    const size_t bytes[7] = {24 * n, 24 * n, 8 * n, part ? 8 * n : 0, 4 * conn.size(), 4 * m, m};
+    size_t at[7], pos = 0;
+    for (int b = 0; b < 7; ++b) {
+      at[b] = pos;
+      if (b != 3 || part) pos += 8 + bytes[b];
+    }
+    auto arr = [&](const char *type, const char *name, const char *extra, int b) {
+      return std::string("<DataArray type=\"") + type + "\"" + (name ? std::string(" Name=\"") + name + "\"" : std::string()) +
+             extra + " format=\"appended\" offset=\"" + std::to_string(at[b]) + "\"/>\n";
+    };
+    std::string head = std::string(declaration) +
+                       "\n<VTKFile type=\"UnstructuredGrid\" version=\"1.0\" byte_order=\"LittleEndian\" "
+                       "header_type=\"UInt64\">\n<UnstructuredGrid>\n<Piece NumberOfPoints=\"" +
+                       std::to_string(n) + "\" NumberOfCells=\"" + std::to_string(m) + "\">\n<Points>\n" +
+                       arr("Float64", nullptr, " NumberOfComponents=\"3\"", 0) + "</Points>\n<Cells>\n" +
+                       arr("Int32", "connectivity", "", 4) + arr("Int32", "offsets", "", 5) + arr("UInt8", "types", "", 6) +
+                       "</Cells>\n<PointData " + point_data + ">\n" +
+                       arr("Float64", "velocity", " NumberOfComponents=\"3\"", 1) + arr("Float64", "pressure", "", 2) +
+                       (part ? arr("Float64", "partitioning", "", 3) : std::string()) +
+                       "</PointData>\n</Piece>\n</UnstructuredGrid>\n";
+    const std::string opening = "<AppendedData encoding=\"raw\">\n_", closing = "\n</AppendedData>\n</VTKFile>\n";
+    head += std::string((8 - (head.size() + opening.size()) % 8) % 8, ' ') + opening;
+    const size_t start = head.size();
+    // 8-byte words, so that vel3() and prs() are aligned doubles (start and every Float64 block are multiples of 8)
+    size_ = start + pos + closing.size();
+    image_.assign((size_ + 7) / 8, 0);
+    char *im = reinterpret_cast<char *>(image_.data());
+    std::memcpy(im, head.data(), start);
+    std::memcpy(im + start + pos, closing.data(), closing.size());
+    const std::vector<double> partv(part ? n : 0, (double)rank);
+    const void *src[7] = {points, nullptr, nullptr, partv.data(), conn.data(), offsets.data(), types.data()};
+    for (int b = 0; b < 7; ++b) {
+      if (b == 3 && !part) continue;
+      const uint64_t count = bytes[b];
+      std::memcpy(im + start + at[b], &count, 8);
+      if (src[b] && count) std::memcpy(im + start + at[b] + 8, src[b], count);
+    }
+    vel3_ = reinterpret_cast<double *>(im + start + at[1] + 8);
+    prs_ = reinterpret_cast<double *>(im + start + at[2] + 8);
+  }
+  Record(const Record &) = delete;
+  Record &operator=(const Record &) = delete;
+
+  int64_t n_points() const { return n_points_; }
+  double *vel3() { return vel3_; }   // 3 per point: the file's velocity array
+  double *prs() { return prs_; }     // 1 per point: the file's pressure array
+  const char *data() const { return reinterpret_cast<const char *>(image_.data()); }
+  size_t size() const { return size_; }
+
+  void write(const std::string &path) const {
+    std::FILE *f = std::fopen(path.c_str(), "wb");
+    if (!f) throw std::runtime_error("cannot write " + path);
+    const bool ok = std::fwrite(data(), 1, size_, f) == size_;
+    if (std::fclose(f) != 0 || !ok) throw std::runtime_error("cannot write " + path);
+  }
+  // the files of write_patches: the piece <name>_<cnt>.<rank>.vtu and, on rank 0, the same .pvtu
+  std::string write(const std::string &directory, const std::string &name, const std::string &cnt, int rank, int nranks) const {
+    namespace fs = std::filesystem;
+    const fs::path dir(directory.empty() ? "./" : directory);
+    fs::create_directories(dir);
+    const std::string piece = (dir / (name + "_" + cnt + "." + std::to_string(rank) + ".vtu")).string();
+    write(piece);
+    if (rank == 0) write_pvtu(dir, name, cnt, nranks);
+    return piece;
+  }
+
+ private:
+  int64_t n_points_;
+  size_t size_ = 0;
+  std::vector<uint64_t> image_;
+  double *vel3_ = nullptr, *prs_ = nullptr;
+};
+
+// The piece of the generated mesh's cells ij in file order with s = subdivisions in 1..4: per cell (s+1)^2 points
+// ((i + k/s) hx, (j + l/s) hy, 0), pt = l (s+1) + k, and s^2 VTK_QUADs base + l (s+1) + k, +1, +(s+1)+1, +(s+1) — for s = 1
+// the points and the `0 1 3 2` of write_patches.
+inline std::unique_ptr<Record> quad_record(int64_t n_cells, const int32_t *ij, double hx, double hy, int s, int rank) {
+  if (s < 1 || s > 4) throw std::runtime_error("vtu::quad_record: subdivisions outside 1..4");
+  const int64_t ppc = (int64_t)(s + 1) * (s + 1), n_points = n_cells * ppc, n_quads = n_cells * s * s;
+  std::vector<double> pts(3 * (size_t)n_points, 0.0);
+  std::vector<int32_t> conn(4 * (size_t)n_quads), offs((size_t)n_quads);
+  for (int64_t c = 0; c < n_cells; ++c) {
+    for (int l = 0; l <= s; ++l)
+      for (int k = 0; k <= s; ++k) {
+        double *o = &pts[3 * (size_t)(c * ppc + l * (s + 1) + k)];
+        o[0] = ((double)ij[2 * c] + (double)k / (double)s) * hx;
+        o[1] = ((double)ij[2 * c + 1] + (double)l / (double)s) * hy;
+      }
+    for (int l = 0; l < s; ++l)
+      for (int k = 0; k < s; ++k) {
+        const int32_t first = (int32_t)(c * ppc + l * (s + 1) + k);
+        int32_t *o = &conn[4 * (size_t)(c * s * s + l * s + k)];   // VTK_QUAD ordering
+        o[0] = first; o[1] = first + 1; o[2] = first + s + 2; o[3] = first + s + 1;
+      }
+  }
+  for (int64_t q = 0; q < n_quads; ++q) offs[(size_t)q] = (int32_t)(4 * (q + 1));
+  return std::make_unique<Record>(n_points, pts.data(), conn, offs, std::vector<uint8_t>((size_t)n_quads, 9), rank);
 }
 
 }  // namespace vtu

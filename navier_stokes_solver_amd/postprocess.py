@@ -250,6 +250,28 @@ def _join_rows(a):
     return "\n".join(out.tolist())
 
 
+def _write_pvtu(directory, name, cnt, nranks):
+    """The record `<name>_<cnt>.pvtu` naming the pieces of all ranks, as `write_vtu` writes it."""
+    pieces = "\n".join(f'<Piece Source="{name}_{cnt}.{r}.vtu"/>' for r in range(nranks))
+    pvtu = f"""<?xml version="1.0"?>
+<VTKFile type="PUnstructuredGrid" version="0.1" byte_order="LittleEndian">
+<PUnstructuredGrid GhostLevel="0">
+<PPointData Scalars="scalars">
+<PDataArray type="Float64" Name="velocity" NumberOfComponents="3" format="ascii"/>
+<PDataArray type="Float64" Name="pressure" format="ascii"/>
+<PDataArray type="Float64" Name="partitioning" format="ascii"/>
+</PPointData>
+<PPoints>
+<PDataArray type="Float64" NumberOfComponents="3"/>
+</PPoints>
+{pieces}
+</PUnstructuredGrid>
+</VTKFile>
+"""
+    with open(os.path.join(directory, f"{name}_{cnt}.pvtu"), "w") as f:
+        f.write(pvtu)
+
+
 def write_vtu_patches(directory, name, counter, ij, hx, hy, vel, prs, n_digits=None, rank=0, nranks=1):
     """The files `write_vtu` writes, byte for byte, from per-cell patches instead of global vectors: `ij` [n, 2] the lattice
     positions of this rank's cells in (i, j) order, `vel` [n, 4, 2] and `prs` [n, 4] the state at their vertices (0,0), (1,0),
@@ -313,22 +335,121 @@ def write_vtu_patches(directory, name, counter, ij, hx, hy, vel, prs, n_digits=N
         f.write(xml)
     if rank != 0:
         return os.path.join(directory, piece)
-    pieces = "\n".join(f'<Piece Source="{name}_{cnt}.{r}.vtu"/>' for r in range(nranks))
-    pvtu = f"""<?xml version="1.0"?>
-<VTKFile type="PUnstructuredGrid" version="0.1" byte_order="LittleEndian">
-<PUnstructuredGrid GhostLevel="0">
-<PPointData Scalars="scalars">
-<PDataArray type="Float64" Name="velocity" NumberOfComponents="3" format="ascii"/>
-<PDataArray type="Float64" Name="pressure" format="ascii"/>
-<PDataArray type="Float64" Name="partitioning" format="ascii"/>
-</PPointData>
-<PPoints>
-<PDataArray type="Float64" NumberOfComponents="3"/>
-</PPoints>
-{pieces}
-</PUnstructuredGrid>
-</VTKFile>
-"""
-    with open(os.path.join(directory, f"{name}_{cnt}.pvtu"), "w") as f:
-        f.write(pvtu)
+    _write_pvtu(directory, name, cnt, nranks)
     return os.path.join(directory, piece)
+
+
+# ---- the record as VTK XML with raw appended data ----
+def record_tables(s):
+    """(w_u [(s+1)^2, 16], w_p [(s+1)^2, 9]) of `nsk_record_set_cells`: the Q3 (GLL nodes) and Q2 bases of a cell at its
+    (s+1)^2 lattice points, pt = l (s+1) + k at (k / s, l / s); w_u[pt, b*4 + a] = L_a(t_k) L_b(t_l), each entry the
+    double product of two `_lagrange` values (csrc/problem_gen.cpp::nsp_record_tables gives the same bits)."""
+    if s not in (1, 2, 3, 4):
+        raise ValueError("subdivisions must be 1, 2, 3 or 4")
+    t = np.arange(s + 1) / s
+    out = []
+    for nodes in (_GLL, _Q2):
+        a = _lagrange(nodes, t)[0].T                                   # [point, basis]
+        n = len(nodes)
+        out.append((a[None, :, None, :] * a[:, None, :, None]).reshape((s + 1) ** 2, n * n))    # [l, k, b, a]
+    return out[0], out[1]
+
+
+class VtuRecord:
+    """The image of one `.vtu` piece in VTK's XML format with raw appended data, built once per run and rank: the XML
+    header, then after `<AppendedData encoding="raw">` and `_` the blocks — a UInt64 byte count and that many bytes each —
+    points, `velocity`, `pressure`, [`partitioning`,] `connectivity`, `offsets`, `types`.  The header is padded with blanks
+    so that the first block starts at a multiple of 8 in the file.  Everything but `velocity` and `pressure` is filled in
+    here; `vel3` [n, 3] and `prs` [n] are views of the image at those two blocks — a report fills them
+    (`LinearSolver.state_record(vel3=..., prs=...)`) and writes the image with one write."""
+
+    def __init__(self, points, connectivity, offsets, types, partitioning=None, declaration='<?xml version="1.0" ?>',
+                 point_data='Scalars="scalars"'):
+        pts = np.ascontiguousarray(points, np.float64).reshape(-1, 3)
+        conn = np.ascontiguousarray(connectivity, np.int32).reshape(-1)
+        offs = np.ascontiguousarray(offsets, np.int32).reshape(-1)
+        typ = np.ascontiguousarray(types, np.uint8).reshape(-1)
+        n, m = len(pts), len(offs)
+        if len(typ) != m:
+            raise ValueError("offsets and types do not match")
+        blocks = [("points", pts), ("velocity", 24 * n), ("pressure", 8 * n)]
+        if partitioning is not None:
+            blocks.append(("partitioning", np.full(n, float(partitioning))))
+        blocks += [("connectivity", conn), ("offsets", offs), ("types", typ)]
+        at, pos = {}, 0
+        for key, b in blocks:
+            at[key] = pos
+            pos += 8 + (b if isinstance(b, int) else b.nbytes)
+        arr = lambda typ_, key, extra="": (f'<DataArray type="{typ_}"' + (f' Name="{key}"' if key != "points" else "") +   # noqa: E731
+                                           f'{extra} format="appended" offset="{at[key]}"/>\n')
+        head = (f'{declaration}\n<VTKFile type="UnstructuredGrid" version="1.0" byte_order="LittleEndian" header_type="UInt64">\n'
+                f'<UnstructuredGrid>\n<Piece NumberOfPoints="{n}" NumberOfCells="{m}">\n<Points>\n'
+                + arr("Float64", "points", ' NumberOfComponents="3"') + "</Points>\n<Cells>\n" + arr("Int32", "connectivity")
+                + arr("Int32", "offsets") + arr("UInt8", "types") + f"</Cells>\n<PointData {point_data}>\n"
+                + arr("Float64", "velocity", ' NumberOfComponents="3"') + arr("Float64", "pressure")
+                + (arr("Float64", "partitioning") if partitioning is not None else "")
+                + "</PointData>\n</Piece>\n</UnstructuredGrid>\n")
+        opening = '<AppendedData encoding="raw">\n_'
+        head += " " * (-(len(head) + len(opening)) % 8) + opening
+        closing = b"\n</AppendedData>\n</VTKFile>\n"
+        start = len(head)
+        self.image = np.zeros(start + pos + len(closing), np.uint8)
+        self.image[:start] = np.frombuffer(head.encode("ascii"), np.uint8)
+        self.image[start + pos:] = np.frombuffer(closing, np.uint8)
+        for key, b in blocks:
+            o = start + at[key]
+            nbytes = b if isinstance(b, int) else b.nbytes
+            self.image[o:o + 8] = np.frombuffer(np.uint64(nbytes).tobytes(), np.uint8)
+            if not isinstance(b, int):
+                self.image[o + 8:o + 8 + nbytes] = b.reshape(-1).view(np.uint8)
+        self.n_points, self.n_cells = n, m
+        self.vel3 = self.image[start + at["velocity"] + 8:start + at["velocity"] + 8 + 24 * n].view(np.float64).reshape(n, 3)
+        self.prs = self.image[start + at["pressure"] + 8:start + at["pressure"] + 8 + 8 * n].view(np.float64)
+
+    @classmethod
+    def quads(cls, ij, hx, hy, subdivisions=1, rank=0):
+        """The piece of the generated mesh's cells `ij` [n, 2] in file order: per cell (s+1)^2 points ((i + k/s) hx,
+        (j + l/s) hy, 0), pt = l (s+1) + k, and s^2 VTK_QUADs base + l (s+1) + k, +1, +(s+1)+1, +(s+1) — for s = 1 the
+        points and the `0 1 3 2` of `write_vtu_patches`."""
+        s = int(subdivisions)
+        if s not in (1, 2, 3, 4):
+            raise ValueError("subdivisions must be 1, 2, 3 or 4")
+        ij = np.asarray(ij, np.int64).reshape(-1, 2)
+        n_cells, ppc = len(ij), (s + 1) ** 2
+        t = np.arange(s + 1) / s
+        pts = np.zeros((n_cells, s + 1, s + 1, 3))                                  # [cell, l, k]
+        pts[..., 0] = ((ij[:, 0, None] + t[None, :]) * hx)[:, None, :]
+        pts[..., 1] = ((ij[:, 1, None] + t[None, :]) * hy)[:, :, None]
+        l, k = np.divmod(np.arange(s * s), s)
+        first = (l * (s + 1) + k)[:, None] + np.array([0, 1, s + 2, s + 1])        # VTK_QUAD ordering
+        conn = ppc * np.arange(n_cells)[:, None, None] + first[None]
+        n_quads = n_cells * s * s
+        return cls(pts.reshape(-1, 3), conn, 4 * np.arange(1, n_quads + 1), np.full(n_quads, 9), partitioning=rank)
+
+    @classmethod
+    def triangles(cls, nodes, cells):
+        """The piece `simplex.write_vtu` writes: all vertices `nodes` [n, 2], the piece's linear triangles `cells` [m, 3]."""
+        nodes = np.asarray(nodes, float).reshape(-1, 2)
+        cells = np.asarray(cells).reshape(-1, 3)
+        pts = np.concatenate([nodes, np.zeros((len(nodes), 1))], axis=1)
+        return cls(pts, cells, 3 * np.arange(1, len(cells) + 1), np.full(len(cells), 5), declaration='<?xml version="1.0"?>',
+                   point_data='Vectors="velocity" Scalars="pressure"')
+
+    def write(self, path):
+        """The image as it stands, with one write."""
+        if not (np.isfinite(self.vel3).all() and np.isfinite(self.prs).all()):
+            raise ValueError("VTU output touched an entry this rank does not hold (owned + ghost DoFs)")
+        with open(path, "wb") as f:
+            f.write(self.image)
+        return path
+
+
+def write_vtu_record(record, directory, name, counter, n_digits=None, rank=0, nranks=1):
+    """The files of `write_vtu_patches` with the piece as `record`'s image (a `VtuRecord` whose `vel3` / `prs` hold the
+    values): `<name>_<counter>.<rank>.vtu` and, on rank 0, the same `.pvtu`, byte for byte."""
+    cnt = str(counter) if n_digits is None else str(counter).zfill(n_digits)
+    os.makedirs(directory, exist_ok=True)
+    piece = record.write(os.path.join(directory, f"{name}_{cnt}.{rank}.vtu"))
+    if rank == 0:
+        _write_pvtu(directory, name, cnt, nranks)
+    return piece

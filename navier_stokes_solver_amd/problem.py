@@ -73,6 +73,8 @@ def lib() -> C.CDLL:
         L.nsp_n_obstacle_faces.restype = C.c_int64
         L.nsp_n_obstacle_faces.argtypes = [C.c_void_p]
         L.nsp_face_tables.argtypes = [C.c_void_p, C.c_void_p]
+        L.nsp_record_tables.restype = C.c_int
+        L.nsp_record_tables.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
         _LIB = L
     return _LIB
 

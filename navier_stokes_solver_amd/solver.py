@@ -58,6 +58,7 @@ EXPORTS = [
     "nsk_state_save", "nsk_state_save_old", "nsk_state_update", "nsk_assemble", "nsk_scale_values", "nsk_download_rhs", "nsk_time_assemble", "nsk_time_op", "nsk_profile_begin", "nsk_profile_read", "nsk_profile_end",
     "nsk_debug_spmv_form",
     "nsk_forces_set_faces", "nsk_forces_set_edges", "nsk_forces", "nsk_state_get_patches",
+    "nsk_record_set_cells", "nsk_state_get_record",
 ]
 
 
@@ -138,6 +139,8 @@ def lib() -> C.CDLL:
         L.nsk_forces_set_edges.argtypes = [vp, C.c_int64, i32p, vp, f64p]
         L.nsk_forces.argtypes = [vp, C.c_double, f64p, f64p]
         L.nsk_state_get_patches.argtypes = [vp, C.c_int64, i32p, f64p, f64p]
+        L.nsk_record_set_cells.argtypes = [vp, C.c_int64, i32p, C.c_int, f64p, f64p]
+        L.nsk_state_get_record.argtypes = [vp, C.c_int64, f64p, f64p]
         L.nsk_download_rhs.argtypes = [vp, f64p, f64p]
         L.nsk_time_assemble.argtypes = [vp, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_double)]
         L.nsk_amg_info.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
@@ -563,6 +566,30 @@ class LinearSolver:
         vel, prs = np.empty((len(c), 4, 2)), np.empty((len(c), 4))
         self._ck(self.L.nsk_state_get_patches(self.h, len(c), c.ctypes.data, vel.ctypes.data, prs.ctypes.data))
         return vel, prs
+
+    def set_record(self, cells, subdivisions=1, tables=None):
+        """The local cells of the VTU record in file order and the subdivisions s in 1..4; after set_assembly on
+        a Q3/Q2 handle.  `tables`: (w_u, w_p) of `postprocess.record_tables(s)` — built here when s > 1 and none is given."""
+        c = np.ascontiguousarray(cells, np.int32)
+        s = int(subdivisions)
+        if tables is None and 1 < s <= 4:
+            from . import postprocess as PP
+            tables = PP.record_tables(s)
+        wu, wp = (None, None) if tables is None else (_f64(tables[0]), _f64(tables[1]))
+        self._ck(self.L.nsk_record_set_cells(self.h, len(c), c.ctypes.data, s, None if wu is None else wu.ctypes.data,
+                                             None if wp is None else wp.ctypes.data))
+
+    def state_record(self, n_points=None, vel3=None, prs=None):
+        """(vel3 [n_points, 3], prs [n_points]): the `velocity` and `pressure` arrays of the record in file layout, from the
+        resident state.  `vel3`, `prs`: contiguous float64 arrays to fill instead (the positions inside a file image)."""
+        if vel3 is None:
+            vel3, prs = np.empty((int(n_points), 3)), np.empty(int(n_points))
+        if vel3.dtype != np.float64 or prs.dtype != np.float64 or not (vel3.flags.c_contiguous and prs.flags.c_contiguous) \
+                or vel3.size != 3 * prs.size:
+            raise ValueError("state_record: vel3 [n, 3] and prs [n] must be contiguous float64 arrays")
+        self._ck(self.L.nsk_state_get_record(self.h, prs.size, vel3.ctypes.data,
+                                             prs.ctypes.data))
+        return vel3, prs
 
     def scale_values(self, blk, factor):
         self._ck(self.L.nsk_scale_values(self.h, blk, float(factor)))
