@@ -17,7 +17,7 @@ O = sum uold_j phi_j at the 16 points of a cell (the nine fields of `cq`):
     d0             = share of cell `cell_of_dof0` in F[(its node 0, 0), (its node 0, 0)]   (signed, as asm_d0 leaves it)
     Dirichlet rows: F cleared with |d0| on the diagonal, rhs = |d0| bc, x0 = bc.
 
-THE OLD-STATE RULE (nsk_capi.cpp, nsk_assemble: `asm_rhs_u(.., A.have_old ? inv_dt : 0.0, ..)` and
+THE OLD-STATE RULE (nsk_capi_assembly.cpp, nsk_assemble: `asm_rhs_u(.., A.have_old ? inv_dt : 0.0, ..)` and
 `asm_cell_state(.., A.have_old ? A.old_u : nullptr, ..)`): without a saved old state (so = None) the residual has no
 time term, whatever inv_dt, the matrix keeps inv_dt M, and fields 7, 8 of cq are 0; with one, fields 7, 8 hold O and the
 residual's time term is inv_dt (U - O), which at inv_dt == 0 is nothing.  The Stokes phase (.cpp:383-406, :455-458)

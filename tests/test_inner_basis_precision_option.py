@@ -36,15 +36,17 @@ def test_the_getter_is_declared_listed_and_wrapped():
 def test_the_environment_override_is_read_once_and_takes_32_or_64_only():
     """The library's own parsing, as for the two other precision options: a function-local static (read once per
     process), atoi, and every value but 32 and 64 counts as unset."""
-    src = _read("navier_stokes_solver_amd", "csrc", "nsk_capi.cpp")
+    csrc = {n: _read("navier_stokes_solver_amd", "csrc", n)
+            for n in ("nsk_handle.hpp", "nsk_precond.cpp", "nsk_capi.cpp", "nsk_capi_assembly.cpp", "nsk_debug.cpp")}
+    src = csrc["nsk_precond.cpp"]
     m = re.search(r"static const int (\w+) = \[\] \{\s*const char \*e = std::getenv\(\"NSK_INNER_BASIS_PRECISION\"\);"
                   r"\s*const int v = e \? std::atoi\(e\) : 0;\s*return v == 32 \|\| v == 64 \? v : 0;\s*\}\(\);", src)
     assert m, "NSK_INNER_BASIS_PRECISION is not parsed the way NSK_INNER_MATRIX_PRECISION is"
     name = m.group(1)
     assert re.search(rf"\({name} \? {name} : inner_basis_precision\) == 32", src)
-    assert src.count('getenv("NSK_INNER_BASIS_PRECISION")') == 1
+    assert "\n".join(csrc.values()).count('getenv("NSK_INNER_BASIS_PRECISION")') == 1
     # the option itself: 64 or 32, anything else is error -61
-    assert re.search(r"case NSK_OPT_INNER_BASIS_PRECISION:\s*if \(v != 64\.0 && v != 32\.0\) throw Error\(-61,", src)
+    assert re.search(r"case NSK_OPT_INNER_BASIS_PRECISION:\s*if \(v != 64\.0 && v != 32\.0\) throw Error\(-61,", csrc["nsk_capi.cpp"])
 
 
 def test_both_drivers_print_the_line():

@@ -12,6 +12,14 @@ def _read(*parts):
         return f.read()
 
 
+def _csrc(*names):
+    return "\n".join(_read("navier_stokes_solver_amd", "csrc", n) for n in names)
+
+
+# the handle, the preconditioners and the three files of entry points: counts are taken over all of them
+HANDLE_FILES = ("nsk_handle.hpp", "nsk_precond.cpp", "nsk_capi.cpp", "nsk_capi_assembly.cpp", "nsk_debug.cpp")
+
+
 def test_option_value_matches_the_header_and_is_documented():
     from navier_stokes_solver_amd import solver as S
     h = _read("include", "nsk.h")
@@ -45,21 +53,21 @@ def test_the_entry_points_are_declared_listed_and_wrapped():
 def test_the_environment_override_is_read_once_and_takes_0_or_1_only():
     """A function-local static (read once per process), as the three precision switches are read; exactly "0" or "1",
     anything else counts as unset."""
-    src = _read("navier_stokes_solver_amd", "csrc", "nsk_capi.cpp")
+    src, capi, every = _csrc("nsk_precond.cpp"), _csrc("nsk_capi.cpp"), _csrc(*HANDLE_FILES)
     m = re.search(r"static const int (\w+) = \[\] \{\s*const char \*e = std::getenv\(\"NSK_INNER_MATRIX_FREE_F\"\);"
                   r"\s*if \(e && e\[0\] == '0' && !e\[1\]\) return 0;\s*if \(e && e\[0\] == '1' && !e\[1\]\) return 1;"
                   r"\s*return -1;\s*\}\(\);", src)
     assert m, "NSK_INNER_MATRIX_FREE_F is not parsed by a function-local static that takes 0 or 1 only"
     name = m.group(1)
     assert re.search(rf"matfree_wanted = \({name} >= 0 \? {name} : matrix_free_f\) == 1;", src)
-    assert src.count('getenv("NSK_INNER_MATRIX_FREE_F")') == 1
-    assert re.search(r"case NSK_OPT_INNER_MATRIX_FREE_F:\s*if \(v != 0\.0 && v != 1\.0\) throw Error\(-61,", src)
+    assert every.count('getenv("NSK_INNER_MATRIX_FREE_F")') == 1
+    assert re.search(r"case NSK_OPT_INNER_MATRIX_FREE_F:\s*if \(v != 0\.0 && v != 1\.0\) throw Error\(-61,", capi)
     # the fallback announces itself, once per handle
-    assert src.count("[nsk] warning: NSK_OPT_INNER_MATRIX_FREE_F = 1") == 1 and "matfree_warned = true;" in src
+    assert every.count("[nsk] warning: NSK_OPT_INNER_MATRIX_FREE_F = 1") == 1 and "matfree_warned = true;" in every
 
 
 def test_every_writer_of_f_or_the_cell_data_clears_the_flag():
-    src = _read("navier_stokes_solver_amd", "csrc", "nsk_capi.cpp")
+    src = _csrc("nsk_capi.cpp", "nsk_capi_assembly.cpp")
 
     def body(name):
         m = re.search(rf"^int {name}\(.*?^}}", src, re.M | re.S)
