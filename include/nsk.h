@@ -29,6 +29,7 @@
  *   -30..-32 triangular-solve analysis (missing diagonal, row too long)
  *   -40..-47 missing blocks, bad preconditioner / solver type, call order
  *   -48 NSK_OPT_INNER_MATRIX_PRECISION = 32: a value of F, S or M_p is finite in fp64 but outside the range of fp32
+ *       (NSK_OPT_AMG_PRECISION = 32: the same for a value of A, P or R on a level of the velocity AMG, when it is built)
  *   -50..-59 bad arguments of the hand-off calls           -60..-66 device assembly / Newton state
  *   -69, -71..-73 forces / output patches from the resident state (-69: no cells, or no faces / edges handed over; -71:
  *        faces or a record list on a P2/P1 handle, edges or patches on the other kind; -72: a cell index out of range;
@@ -134,7 +135,8 @@ enum {
                                  arithmetic (values are widened as they are loaded).  Applies to the velocity factor (2x2
                                  node blocks) and the S / Mp factors; factors that take the natural-order ring, the level
                                  walker, the single-workgroup path for tiny factors or the velocity AMG keep double —
-                                 nsk_tri_get_value_bytes reports what each holds.  A LABELLED DEVIATION from the reference,
+                                 nsk_tri_get_value_bytes reports what each holds (the AMG's own switch:
+                                 NSK_OPT_AMG_PRECISION).  A LABELLED DEVIATION from the reference,
                                  whose Ifpack factors are double: the outer FGMRES stays double and checks the true residual,
                                  the preconditioner alone is perturbed.  Other values: -61.  NSK_FACTOR_PRECISION=32 / 64 in
                                  the environment overrides the option for every handle (A/B runs; other values ignored) */
@@ -155,7 +157,8 @@ enum {
                                  stops at a loose tolerance and the outer FGMRES stays double and checks the true residual,
                                  so only the preconditioner is perturbed.  Other values: -61.  NSK_INNER_MATRIX_PRECISION=32
                                  / 64 in the environment overrides the option for every handle (A/B runs; other values
-                                 ignored).  Independent of NSK_OPT_FACTOR_PRECISION; the velocity AMG keeps double */
+                                 ignored).  Independent of NSK_OPT_FACTOR_PRECISION; the velocity AMG keeps double unless
+                                 NSK_OPT_AMG_PRECISION says otherwise */
   NSK_OPT_INNER_BASIS_PRECISION = 18, /* storage precision of the Krylov basis V of the INNER FGMRES on F, which the two fused
                                  Gram-Schmidt sweeps read once each per inner iteration.  64 (default): double, as today and
                                  the same bits.  32: basis vector j IS the rounded vector, v_j = fl32(w / |w|) (owned entries
@@ -173,7 +176,7 @@ enum {
                                  checks the true residual, so only the preconditioner is perturbed.  Other values: -61.
                                  NSK_INNER_BASIS_PRECISION=32 / 64 in the environment overrides the option for every handle
                                  (A/B runs; other values ignored).  Independent of the two options above */
-  NSK_OPT_INNER_MATRIX_FREE_F = 19 /* how the INNER FGMRES on F multiplies by F on handles that assemble it themselves
+  NSK_OPT_INNER_MATRIX_FREE_F = 19, /* how the INNER FGMRES on F multiplies by F on handles that assemble it themselves
                                  (nsk_assembly_set_cells + nsk_assemble: congruent Q3/Q2 cells).  0 (default): the stored
                                  block, as today and the same bits.  1: matrix-free — the same operator in double, applied
                                  from what the last nsk_assemble left on the device (u and grad u at the quadrature points,
@@ -193,6 +196,28 @@ enum {
                                  NSK_OPT_INNER_MATRIX_PRECISION = 32 no fp32 copy of F is made while the product is
                                  matrix-free.  Other values: -61.  NSK_INNER_MATRIX_FREE_F=0 / 1 in the environment
                                  overrides the option for every handle (A/B runs; other values count as unset) */
+  NSK_OPT_AMG_PRECISION = 20 /* storage precision of the operators the velocity AMG's V-cycle multiplies by (stationary
+                                 blockTriangular, NSK_OPT_VELOCITY_AMG = 1).  64 (default): double, as today and the same
+                                 bits.  32: the values of every level's A, P and R, on every shard, are stored rounded to
+                                 float (nearest even) once the level is finished, and the cycle's products read those:
+                                 level 0 that is F itself through F's 2x2 node-block copy (the one the inner solves read
+                                 under NSK_OPT_INNER_MATRIX_PRECISION = 32; it exists while either option wants it) with a
+                                 y = z - A x node-block kernel, every other operator — coarse levels, P, R, the shards'
+                                 diagonal blocks under NSK_OPT_SUBDOMAINS > 1 or several ranks, F without node structure or
+                                 under NSK_OPT_BSR_VELOCITY = 0 — through the scalar stream kernels on fp32 values.  What
+                                 stays double: the whole set-up (strength, aggregation, the lambda power iterations,
+                                 prolongator smoothing, the Galerkin products), every vector, dinv, the coarsest level's
+                                 dense inverse and its product, the Chebyshev coefficients, every product, sum and LDS
+                                 partial (values are widened as they land), and F itself, which the outer J x, ILU(0), the
+                                 Schur SpGEMM and nsk_spmv read.  Takes effect at the next nsk_setup_preconditioner (the
+                                 hierarchy is still built on first apply); a value finite in fp64 but outside fp32's range
+                                 returns -48 from the call that builds it, naming the level and the operator.
+                                 nsk_amg_value_bytes reports what the hierarchy holds.  A LABELLED DEVIATION from the
+                                 reference, whose ML hierarchy is double: the V-cycle sits inside the inner FGMRES on F,
+                                 which is flexible and stops at a loose tolerance, and the outer FGMRES stays double and
+                                 checks the true residual, so only the preconditioner is perturbed.  Other values: -61.
+                                 NSK_AMG_PRECISION=32 / 64 in the environment overrides the option for every handle (A/B
+                                 runs; other values ignored).  Independent of the three precision options above */
 };
 
 typedef struct {
@@ -288,6 +313,9 @@ int nsk_tri_apply(nsk_handle h, int which, const double *b, double *x);
  * NSSolverStationary.hpp:225): returns the number of levels of sub-domain `shard` (0 when the setup has no AMG)
  * and, for a valid `level`, its size, non-zeros and the lambda_max(D^-1 A) estimate the smoother uses. */
 int nsk_amg_info(nsk_handle h, int shard, int level, int64_t *rows, int64_t *nnz, double *lambda_max);
+/* bytes per stored value of the operators the V-cycle of the current set-up multiplies by: 4 (NSK_OPT_AMG_PRECISION = 32),
+ * 8 (double), 0 when the set-up has no AMG.  Builds a pending hierarchy first, as nsk_amg_info does. */
+int nsk_amg_value_bytes(nsk_handle h, int32_t *bytes);
 /* ordering used by that triangular preconditioner: perm[new] = old (identity when natural) */
 int nsk_tri_get_perm(nsk_handle h, int which, int32_t *perm);
 /* bytes per stored off-diagonal value of that triangular preconditioner as its applies read them in the current set-up:
@@ -448,10 +476,13 @@ int nsk_reset_stats(nsk_handle h);
  * library's stream: op 0..5 = SpMV of block op; 10 = jacobian vmult; 20/21 = velocity /
  * pressure triangular apply; 30 = dot; 31 = axpy; 32 = fused add_and_dot; 50 + blk (50, 53, 55) = the inner
  * solves' SpMV of F, M_p, S (nsk_inner_spmv; needs a set-up); 56 = the matrix-free product with F (nsk_matfree_f:
- * needs a valid assembly, not the option).
+ * needs a valid assembly, not the option); 57 = one V-cycle of the current set-up's velocity AMG (as op 20 under
+ * that set-up).
  * Returns average milliseconds per repetition and the algorithmic bytes of one repetition — for ops 50 + blk the bytes
  * the stored format really moves (fp32 values: 4 bytes each), for op 56 (and op 50 while matrix-free is in effect) the
- * bytes the two kernels move: cell data, the cells' shares written and read, node lists, x and y. */
+ * bytes the two kernels move: cell data, the cells' shares written and read, node lists, x and y; for op 57 the bytes the
+ * stored formats hold for one cycle (fp32 values, node blocks: NSK_OPT_AMG_PRECISION), where op 20 reports the algorithmic
+ * CSR count. */
 int nsk_time_op(nsk_handle h, int op, int reps, double *avg_ms, double *bytes);
 
 /* HIP-event sampling of operation classes INSIDE the following solves: every launch of a sampled op

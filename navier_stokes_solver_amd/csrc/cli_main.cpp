@@ -164,7 +164,7 @@ struct NewtonDriver {
   int solve_system() {
     check(h, nsk_setup_preconditioner(h, preconditioner, NSK_UNSTEADY ? NSK_VARIANT_UNSTEADY : NSK_VARIANT_STATIONARY, 0.5),
           "nsk_setup_preconditioner");
-    // NSK_FACTOR_PRECISION=32 / NSK_INNER_MATRIX_PRECISION=32 / NSK_INNER_BASIS_PRECISION=32 (read by the library):
+    // NSK_FACTOR_PRECISION=32 / NSK_INNER_MATRIX_PRECISION=32 / NSK_INNER_BASIS_PRECISION=32 / NSK_AMG_PRECISION=32 (read by the library):
     // LABELLED DEVIATIONS from the reference.  (On lines of their own: the Newton line in front of this call is still open.)
     if (!precision_reported) {
       precision_reported = true;
@@ -184,6 +184,13 @@ struct NewtonDriver {
       }
       if (bv == 4) {
         std::printf("%s[nsk] NSK_INNER_BASIS_PRECISION=32: inner FGMRES basis on F stored in fp32 (deviation from the reference)\n", nl);
+        nl = "";
+      }
+      // (the question builds a pending hierarchy: the one the solve below would build at its first application)
+      int32_t ba = 0;
+      check(h, nsk_amg_value_bytes(h, &ba), "nsk_amg_value_bytes");
+      if (ba == 4) {
+        std::printf("%s[nsk] NSK_AMG_PRECISION=32: velocity AMG operators stored in fp32 (deviation from the reference)\n", nl);
         nl = "";
       }
       // NSK_INNER_MATRIX_FREE_F=1 (read by the library): the same operator in double, no deviation in storage

@@ -9,6 +9,7 @@
 #include <chrono>
 #include <cmath>
 
+#include <cstdint>
 #include <cstring>
 
 #include "nsk_amg_kernels.h"
@@ -721,15 +722,55 @@ void Amg::build(AmgHierarchy &H, Csr *A0, std::unique_ptr<Csr> own0) {
     L->has_coarse = true;
     ctx->sync();
     S.end_level();
+    if (value_bits == 32) to_f32(*L, l);
     H.lev.push_back(std::move(L));
   }
+  // (the last level: its operator is multiplied only where it is too large for a dense inverse)
+  if (value_bits == 32 && !H.lev.back()->inv.p) to_f32(*H.lev.back(), (int)H.lev.size() - 1);
+}
+
+void Amg::check_overflow(Csr &M, int level, const char *which) {
+  unsigned over = 0;
+  NSK_HIP(hipMemcpyAsync(&over, M.f32_overflow.p, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
+  ctx->sync();
+  if (over)
+    throw Error(-48, "NSK_OPT_AMG_PRECISION = 32: " + std::to_string(over) + " value(s) of level " + std::to_string(level) +
+                         "'s " + which + " are finite in fp64 but outside the range of fp32");
+}
+
+// The set-up is done with the level: nothing reads the double values of its operators any more (they are kept: the test
+// hook downloads them).  An operator without a stream plan keeps the CSR-vector kernel on its double values.
+void Amg::to_f32(AmgLevel &L, int level) {
+  struct Item { Csr *M; const char *which; };
+  const Item items[3] = {{L.A == &L.own_A ? &L.own_A : nullptr, "A"}, {L.has_coarse ? &L.P : nullptr, "P"}, {L.has_coarse ? &L.R : nullptr, "R"}};
+  for (const Item &it : items)
+    if (it.M && it.M->stream_ok) { it.M->amg32 = 2; it.M->refresh_f32(ctx->stream, true); }
+  for (const Item &it : items)
+    if (it.M && it.M->amg32) check_overflow(*it.M, level, it.which);
 }
 
 void Amg::setup(Ctx *c, Csr &F, const std::vector<int> &shard_off) {
   ctx = c;
   const double t0 = now_ms();
-  shards.clear();
+  clear();
+  built_bits = value_bits;
+  F.amg32 = 0;   // (the set-up multiplies by the double values; a copy left by the last hierarchy stays allocated meanwhile)
   if (F.n_rows <= 0) return;
+  try {
+    build_all(F, shard_off);
+  } catch (...) {   // (-48 from any level's conversion among them: no copy of F stays behind that nobody names)
+    F.amg32 = 0;
+    F.drop_unused_f32();
+    throw;
+  }
+  F.drop_unused_f32();
+  ctx->sync();
+  for (long &c : form_launches) c = 0;   // (the set-up's own products are not the cycle's)
+  setup_host_ms = now_ms() - t0;
+  if (std::getenv("NSK_AMG_TIMING")) std::fprintf(stderr, "amg set-up: total %.1f ms\n", setup_host_ms);
+}
+
+void Amg::build_all(Csr &F, const std::vector<int> &shard_off) {
   std::vector<int> off = shard_off;
   if (off.size() < 2) off = {0, F.n_rows};
   const bool single_full = off.size() == 2 && F.n_cols == F.n_own_cols && F.n_cols == F.n_rows;
@@ -738,7 +779,11 @@ void Amg::setup(Ctx *c, Csr &F, const std::vector<int> &shard_off) {
   for (size_t sidx = 0; sidx + 1 < off.size(); ++sidx) {
     const int r0 = off[sidx], r1 = off[sidx + 1];
     shards[sidx].offset = r0;
-    if (single_full) { build(shards[sidx], &F, nullptr); continue; }
+    if (single_full) {
+      build(shards[sidx], &F, nullptr);
+      level0 = &F;
+      continue;
+    }
     // the shard's diagonal block as a matrix of its own (ghost columns and other shards' columns dropped)
     Scratch S(ctx, arena, arena_want);
     auto B = std::make_unique<Csr>();
@@ -754,13 +799,30 @@ void Amg::setup(Ctx *c, Csr &F, const std::vector<int> &shard_off) {
     S.end_level();
     build(shards[sidx], nullptr, std::move(B));
   }
-  ctx->sync();
-  setup_host_ms = now_ms() - t0;
-  if (std::getenv("NSK_AMG_TIMING")) std::fprintf(stderr, "amg set-up: total %.1f ms\n", setup_host_ms);
+  if (level0 && value_bits == 32) {
+    // Level 0 is the caller's block: the cycle reads its 2 x 2 fp32 copy, the one the inner solves read under
+    // NSK_OPT_INNER_MATRIX_PRECISION = 32 (whichever of the two wants it first converts it), or its scalar fp32 values
+    // where it has no such copy.  Named only now: the set-up above multiplied by the double values.
+    const bool blk22 = use_bsr && F.blk_ok && F.blk_R == 2 && F.blk_C == 2;
+    F.amg32 = blk22 ? 1 : F.stream_ok ? 2 : 0;
+    if (F.amg32 && !F.f32_current()) {
+      F.refresh_f32(ctx->stream, true);
+      check_overflow(F, 0, "A");
+    }
+  }
 }
 
 void Amg::mv(Csr &A, const double *x, double *y, int mode, const double *z) {
-  A.spmv_launch(ctx->stream, A.spmv_form(true, false, mode), x, nullptr, y, mode, z);   // (no ghost tail, no 16-bit offsets)
+  // (no ghost tail, no 16-bit offsets; the rule: amg_spmv_form, nsk_core.hpp)
+  const bool aligned16 = (((uintptr_t)x | (uintptr_t)y | (uintptr_t)z) & 15) == 0;
+  const SpmvForm f = form_of(A, mode, aligned16);
+  if (is_f32(f)) {
+    // the caller's block: values written since the conversion, or vectors off the pair alignment for the first time
+    if (f == SpmvForm::stream_f32 && !(A.amg32 & 2)) { A.amg32 |= 2; A.val32_version = -1; }
+    if (A.val32_version != A.values_version) A.refresh_f32(ctx->stream, false);   // (stream-ordered: no host sync)
+  }
+  A.spmv_launch(ctx->stream, f, x, nullptr, y, mode, z);
+  ++form_launches[(int)f];
   ++ctx->st.spmv_calls;
   ctx->st.spmv_bytes += (double)A.spmv_bytes() + (mode ? 8.0 * A.n_rows : 0.0);
 }
@@ -813,6 +875,43 @@ size_t Amg::apply_bytes() const {
       else by += 3 * (L->A->spmv_bytes() + 8 * (size_t)L->n) + (size_t)L->n * 8 * 5 * 4;
     }
   return by;
+}
+
+double Amg::format_bytes(int shard, int level) const {
+  double by = 0;
+  for (size_t sh = 0; sh < shards.size(); ++sh) {
+    if (shard >= 0 && (int)sh != shard) continue;
+    const AmgHierarchy &H = shards[sh];
+    for (size_t l = 0; l < H.lev.size(); ++l) {
+      if (level >= 0 && (int)l != level) continue;
+      const AmgLevel &L = *H.lev[l];
+      const double n8 = 8.0 * L.n;
+      // (the forms of aligned vectors: what the cycle takes on the library's own)
+      const double a = L.A->format_bytes(form_of(*L.A, 2, true)) + n8;
+      if (L.has_coarse) by += 4 * a + L.P.format_bytes(form_of(L.P, 1, true)) + n8 + L.R.format_bytes(form_of(L.R, 0, true)) + n8 * 5 * 4;
+      else if (L.inv.p) by += (double)L.n * L.n * 8;
+      else by += 3 * a + n8 * 5 * 4;
+    }
+  }
+  return by;
+}
+
+int64_t Amg::debug_level(int shard, int level, int which, int32_t *rowptr, int32_t *col, double *val, double *dio) {
+  if (shard < 0 || shard >= (int)shards.size() || level < 0 || level >= n_levels(shard)) throw Error(-61, "nsk_debug_amg_level: shard or level");
+  AmgLevel &L = *shards[shard].lev[level];
+  if (which == 3) return L.inv.p ? 1 : 0;
+  if (which < 0 || which > 3 || (which != 0 && !L.has_coarse)) throw Error(-61, "nsk_debug_amg_level: the level has no such operator");
+  const Csr &M = which == 0 ? *L.A : which == 1 ? L.P : L.R;
+  hipStream_t s = ctx->stream;
+  if (rowptr) NSK_HIP(hipMemcpyAsync(rowptr, M.rowptr.p, sizeof(int) * ((size_t)M.n_rows + 1), hipMemcpyDeviceToHost, s));
+  if (col && M.nnz) NSK_HIP(hipMemcpyAsync(col, M.col.p, sizeof(int) * (size_t)M.nnz, hipMemcpyDeviceToHost, s));
+  if (val && M.nnz) NSK_HIP(hipMemcpyAsync(val, M.val.p, sizeof(double) * (size_t)M.nnz, hipMemcpyDeviceToHost, s));
+  if (dio && which == 0) {
+    if (L.inv.p) NSK_HIP(hipMemcpyAsync(dio, L.inv.p, sizeof(double) * (size_t)L.n * L.n, hipMemcpyDeviceToHost, s));
+    else NSK_HIP(hipMemcpyAsync(dio, L.dinv.p, sizeof(double) * (size_t)L.n, hipMemcpyDeviceToHost, s));
+  }
+  ctx->sync();
+  return M.nnz;
 }
 
 }  // namespace nsk

@@ -16,6 +16,11 @@
 // Set-up and cycle both run on the device: the set-up with the row-parallel kernels of nsk_amg_kernels.hip from the
 // block's device copy (only row pointers for the SpMV plans and the coarsest operator, for its dense inverse, visit
 // the host), the cycle with the library's CSR-stream SpMV kernels.
+//
+// NSK_OPT_AMG_PRECISION = 32: the set-up is the same, in double; when a level is finished the values of the
+// operators the cycle multiplies by — A, P, R — are rounded to float (Csr::val32; level 0 that is the caller's F: its 2x2
+// node-block copy blk_val32) and the cycle's products read those, widened as they land.  Vectors, dinv, the coarsest
+// level's dense inverse, the Chebyshev coefficients and all arithmetic stay double.
 #pragma once
 #include <memory>
 #include <vector>
@@ -45,12 +50,22 @@ struct Amg {
   Ctx *ctx = nullptr;
   std::vector<AmgHierarchy> shards;
   double setup_host_ms = 0;
+  // Set by the handle before setup(): bits the operators' values are stored in (64, or 32: NSK_OPT_AMG_PRECISION), and
+  // whether level 0 may use F's 2x2 node blocks (NSK_OPT_BSR_VELOCITY)
+  int value_bits = 64;
+  bool use_bsr = true;
+  long form_launches[5] = {0, 0, 0, 0, 0};   // products of the cycles since the set-up, by SpmvForm (test hook)
+  int value_bytes() const { return shards.empty() ? 0 : built_bits / 8; }   // of the hierarchy that stands
   // F: device block with host pattern; shard_off: empty = one shard
   void setup(Ctx *ctx, Csr &F, const std::vector<int> &shard_off);
   void apply(const double *b, double *x);
-  void clear() { shards.clear(); }   // (the set-up's scratch arena stays for the next set-up)
-  void release() {                   // the preconditioner is no longer in use
+  void clear() {
     shards.clear();
+    level0 = nullptr;
+    for (long &c : form_launches) c = 0;
+  }   // (the set-up's scratch arena stays for the next set-up)
+  void release() {                   // the preconditioner is no longer in use
+    clear();
     arena.release();
   }
   int n_levels(int shard = 0) const { return shards.empty() ? 0 : (int)shards[shard].lev.size(); }
@@ -58,8 +73,14 @@ struct Amg {
   int64_t level_nnz(int shard, int l) const { return shards[shard].lev[l]->A->nnz; }
   double level_lambda(int shard, int l) const { return shards[shard].lev[l]->lam; }
   size_t apply_bytes() const;  // algorithmic bytes of one V-cycle (SURVEY 8d formulas)
+  // the same count on what the stored formats hold (fp32 values, node blocks), vectors as in apply_bytes; level >= 0: that
+  // level of that shard alone
+  double format_bytes(int shard = -1, int level = -1) const;
+  // Test hook behind nsk_debug_amg_level (nsk_internal.h)
+  int64_t debug_level(int shard, int level, int which, int32_t *rowptr, int32_t *col, double *val, double *dinv_or_inverse);
 
  private:
+  void build_all(Csr &F, const std::vector<int> &shard_off);   // every shard's hierarchy, then level 0's fp32 copy
   void build(AmgHierarchy &H, Csr *A0, std::unique_ptr<Csr> own0);
   DBuf<char> arena;        // work arrays of the set-up, kept across set-ups (nsk_amg.cpp: Scratch)
   size_t arena_want = 0;   // bytes the largest level took so far
@@ -67,6 +88,13 @@ struct Amg {
   void cheby(AmgLevel &L, const double *b, double *x, bool zero_init);
   void vcycle(AmgHierarchy &H, int l, const double *b, double *x);
   void mv(Csr &A, const double *x, double *y, int mode = 0, const double *z = nullptr);
+  SpmvForm form_of(const Csr &A, int mode, bool aligned16) const {
+    return amg_spmv_form(A.blk_ok && A.blk_R == 2 && A.blk_C == 2, A.stream_ok, A.amg32 != 0, use_bsr, mode, aligned16);
+  }
+  void to_f32(AmgLevel &L, int level);   // round the finished level's A (its own), P and R; Error -48 on overflow
+  void check_overflow(Csr &M, int level, const char *which);
+  int built_bits = 64;
+  Csr *level0 = nullptr;   // the caller's block when it is level 0 itself
 };
 
 // Structural pattern of C = A B on the device, rows sorted by column (the row-product kernels of the AMG set-up: hash sets

@@ -257,6 +257,10 @@ int nsk_set_option(nsk_handle h, int opt, double v) {
       if (v != 64.0 && v != 32.0) throw Error(-61, "NSK_OPT_INNER_BASIS_PRECISION: 64 or 32");
       h->inner_basis_precision = (int)v;
       break;
+    case NSK_OPT_AMG_PRECISION:
+      if (v != 64.0 && v != 32.0) throw Error(-61, "NSK_OPT_AMG_PRECISION: 64 or 32");
+      h->amg_precision = (int)v;
+      break;
     case NSK_OPT_INNER_MATRIX_FREE_F:
       if (v != 0.0 && v != 1.0) throw Error(-61, "NSK_OPT_INNER_MATRIX_FREE_F: 0 or 1");
       h->matrix_free_f = (int)v;
@@ -434,6 +438,15 @@ int nsk_amg_info(nsk_handle h, int shard, int level, int64_t *rows, int64_t *nnz
     if (lambda_max) *lambda_max = h->amgF.level_lambda(shard, level);
   }
   return nl;
+  NSK_CATCH(h)
+}
+
+int nsk_amg_value_bytes(nsk_handle h, int32_t *bytes) {
+  NSK_TRY_DEV(h)
+  if (h->prec_type < 0) throw Error(-46, "call nsk_setup_preconditioner first");
+  if (h->amg_active) h->amg_ready();
+  *bytes = h->amg_active ? h->amgF.value_bytes() : 0;
+  return 0;
   NSK_CATCH(h)
 }
 
@@ -712,6 +725,13 @@ int nsk_time_op(nsk_handle h, int op, int reps, double *avg_ms, double *bytes) {
     const DVec xv = h->pool_u.view(xs);
     by = h->matfree_bytes();
     f = [=]() { h->matfree_apply(xv, yb); };
+  } else if (op == 57) {
+    // one V-cycle of the current set-up; bytes: what the stored formats hold for it (op 20: the algorithmic count)
+    if (h->prec_type < 0) throw Error(-46, "call nsk_setup_preconditioner first");
+    if (!h->amg_active) throw Error(-62, "nsk_time_op: the current set-up has no velocity AMG");
+    h->amg_ready();
+    by = h->amgF.format_bytes();
+    f = [=]() { h->amgF.apply(xb, yb); };
   } else if (op == 10) {
     Csr &F = h->blk[NSK_BLK_F], &Bt = h->blk[NSK_BLK_BT], &B = h->blk[NSK_BLK_B];
     by = (double)F.spmv_bytes() + (double)Bt.spmv_bytes() + (double)B.spmv_bytes();

@@ -614,9 +614,15 @@ int Csr::spmv_launch(hipStream_t s, SpmvForm f, const double *xo, const double *
   if (c1 <= c0) return 0;
   const int *cb = off16.p ? colbase.p + c0 : nullptr;   // (one base per run: it moves with the run range)
   switch (f) {
-    case SpmvForm::blk_f32: nsk::spmv_blk_stream(s, blk_view32(), blk_rowblk.p + c0, c1 - c0, xo, xg, y); return 0;
+    case SpmvForm::blk_f32:   // (y = A x, or the AMG's y = z - A x)
+      nsk::spmv_blk_stream(s, blk_view32(), blk_rowblk.p + c0, c1 - c0, xo, xg, y, mode == 2 ? z : nullptr);
+      return 0;
     case SpmvForm::blk: nsk::spmv_blk_stream(s, blk_view(), blk_R, blk_C, blk_rowblk.p + c0, c1 - c0, xo, xg, y); return 0;
-    case SpmvForm::stream_f32: return nsk::spmv_stream(s, view32(), rowblk.p + c0, c1 - c0, even_rows, xo, xg, y, off16.p, cb);
+    case SpmvForm::stream_f32: {
+      const int vec = nsk::spmv_stream(s, view32(), rowblk.p + c0, c1 - c0, even_rows, xo, xg, y, off16.p, cb, mode, z);
+      if (vec < 0) throw Error(-1, "fp32 stream SpMV: modes 1 and 2 have no kernel on 16-bit column offsets");
+      return vec;
+    }
     default: return nsk::spmv_stream(s, view(), rowblk.p + c0, c1 - c0, even_rows, xo, xg, y, mode, z, off16.p, cb);
   }
 }
@@ -802,18 +808,21 @@ void Csr::refresh_blocked(hipStream_t s) {
 }
 
 void Csr::refresh_f32(hipStream_t s, bool count_overflow) {
-  if (!inner32) return;
+  const bool want_blk = inner32 == 1 || (amg32 & 1), want_val = inner32 == 2 || (amg32 & 2);
+  drop_unused_f32();
+  if (!want_blk && !want_val) return;
   if (count_overflow) {
     if (!f32_overflow.p) f32_overflow.alloc(1);
     NSK_HIP(hipMemsetAsync(f32_overflow.p, 0, sizeof(unsigned), s));
   }
   unsigned *ovf = count_overflow ? f32_overflow.p : nullptr;
-  if (inner32 == 1) {   // F: gathered straight from val into the 2x2 layout (every entry of val has one place there)
+  if (want_blk) {   // F: gathered straight from val into the 2x2 layout (every entry of val has one place there)
     const size_t n = (size_t)blk_count * blk_R * blk_C;
     if (blk_val32.n != n) blk_val32.alloc(n);
     vec_gather(s, (int)n, blk_src.p, val.p, blk_val32.p);
-    if (ovf) vec_to_float(s, (int)nnz, val.p, nullptr, ovf);
-  } else {
+    if (ovf && !want_val) vec_to_float(s, (int)nnz, val.p, nullptr, ovf);
+  }
+  if (want_val) {
     if (val32.n != (size_t)nnz) val32.alloc((size_t)nnz);
     vec_to_float(s, (int)nnz, val.p, val32.p, ovf);
   }

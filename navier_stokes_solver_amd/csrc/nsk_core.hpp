@@ -135,6 +135,18 @@ constexpr SpmvForm spmv_form(bool blk_ok, bool stream_ok, int inner32, bool use_
   if (stream_ok && use_stream) return SpmvForm::stream;
   return SpmvForm::csr_vector;
 }
+// The same for an operator of the velocity AMG's V-cycle (Amg::mv).  The handle's stream option does not reach
+// the cycle; amg32 == false (NSK_OPT_AMG_PRECISION = 64) is today's choice, spmv_form(blk_ok, stream_ok, 0, true, false,
+// mode, false), whatever the other flags say.  amg32: the operator's values are stored in fp32 — 2 x 2 node blocks where
+// the operator has them and the handle uses them (level 0 when it is F itself; use_bsr = NSK_OPT_BSR_VELOCITY), for
+// y = A x and y = z - A x where x, y and z are 16-byte aligned (aligned16: the kernel moves them as pairs); the scalar
+// fp32 stream form otherwise.  An operator without a stream plan keeps its double values and the CSR-vector kernel.
+constexpr SpmvForm amg_spmv_form(bool blk_ok, bool stream_ok, bool amg32, bool use_bsr, int mode, bool aligned16) {
+  if (!amg32) return spmv_form(blk_ok, stream_ok, 0, true, false, mode, false);
+  if (blk_ok && use_bsr && aligned16 && (mode == 0 || mode == 2)) return SpmvForm::blk_f32;
+  if (stream_ok) return SpmvForm::stream_f32;
+  return SpmvForm::csr_vector;
+}
 
 struct Csr {  // device CSR block with host copy of the pattern
   int n_rows = 0, n_cols = 0, n_own_cols = 0;
@@ -176,12 +188,24 @@ struct Csr {  // device CSR block with host copy of the pattern
   // fp32 copies of the values for the preconditioner's inner solves (NSK_OPT_INNER_MATRIX_PRECISION = 32): inner32 = 1
   // F's 2x2 copy in blk_val32, 2 the scalar values in val32, 0 none (the inner solves read val / blk_val).  Every write of
   // val bumps values_version; a copy converted from an older version is converted again before its next use.
-  int inner32 = 0;
+  // amg32: the copies the velocity AMG's V-cycle reads (NSK_OPT_AMG_PRECISION = 32) — bit 0 blk_val32, bit 1 val32 — on F
+  // when it is level 0 itself, on the hierarchy's own operators (2).  A copy exists while either reader names it and is
+  // converted once per values_version for both.
+  int inner32 = 0, amg32 = 0;
   DBuf<float> blk_val32, val32;
   long values_version = 0, val32_version = -1;
   DBuf<unsigned> f32_overflow;   // values finite in fp64 and infinite in fp32, counted by the set-up's conversion
-  void release_f32() { inner32 = 0; blk_val32.release(); val32.release(); f32_overflow.release(); val32_version = -1; }
-  void refresh_f32(hipStream_t s, bool count_overflow);   // (re)convert the copy inner32 names from val, stream-ordered
+  void release_f32() { inner32 = amg32 = 0; blk_val32.release(); val32.release(); f32_overflow.release(); val32_version = -1; }
+  // (re)convert the copies inner32 and amg32 name from val, stream-ordered; a copy neither names is released
+  void refresh_f32(hipStream_t s, bool count_overflow);
+  void drop_unused_f32() {
+    if (!(inner32 == 1 || (amg32 & 1))) blk_val32.release();
+    if (!(inner32 == 2 || (amg32 & 2))) val32.release();
+  }
+  bool f32_current() const {
+    const bool b = inner32 == 1 || (amg32 & 1), v = inner32 == 2 || (amg32 & 2);
+    return val32_version == values_version && (!b || blk_val32.p) && (!v || val32.p);
+  }
   BlkView32 blk_view32() const { return BlkView32{blk_rows, n_own_cols / blk_C, blk_rowptr.p, blk_col.p, blk_val32.p}; }
   CsrView32 view32() const { return CsrView32{n_rows, n_own_cols, rowptr.p, col.p, val32.p}; }
   static constexpr int kToPlanEnd = -1;

@@ -350,16 +350,18 @@ int nsk_debug_spmv(nsk_handle h, int form, int lpr, int mode, int misalign, int 
   hipStream_t st = h->s();
   for (int k = 0; k < 16; ++k) info[k] = 0;
   info[0] = -1;
-  if (form < NSK_DBG_SPMV_CSRV || form > NSK_DBG_SPMV_STREAM_I16_F32) throw Error(-65, "nsk_debug_spmv: unknown form");
+  if (form < NSK_DBG_SPMV_CSRV || form > NSK_DBG_SPMV_BLK22_RES_F32) throw Error(-65, "nsk_debug_spmv: unknown form");
   const bool two = form == NSK_DBG_SPMV_STREAM2 || form == NSK_DBG_SPMV_BLK_FUSED;
-  const bool modes = form == NSK_DBG_SPMV_CSRV || form == NSK_DBG_SPMV_STREAM || form == NSK_DBG_SPMV_STREAM_I16;
+  const bool res = form == NSK_DBG_SPMV_BLK22_RES || form == NSK_DBG_SPMV_BLK22_RES_F32;   // y = z - A x and nothing else
+  const bool modes = form == NSK_DBG_SPMV_CSRV || form == NSK_DBG_SPMV_STREAM || form == NSK_DBG_SPMV_STREAM_I16 ||
+                     form == NSK_DBG_SPMV_STREAM_F32 || res;
   const bool epi = form == NSK_DBG_SPMV_BLK21_EPI;
   if (!Am || !y || two != (Bm != nullptr)) throw Error(-61, "nsk_debug_spmv: matrices");
-  if (mode < 0 || mode > 2 || (mode != 0 && !modes) || (mode == 2 && !z)) throw Error(-61, "nsk_debug_spmv: mode");
+  if (mode < 0 || mode > 2 || (mode != 0 && !modes) || (mode == 2 && !z) || (res && mode != 2)) throw Error(-61, "nsk_debug_spmv: mode");
   if (epi && !(d && dinv)) throw Error(-61, "nsk_debug_spmv: the epilogue needs d and dinv");
   if ((two || form == NSK_DBG_SPMV_CSRV) && c0 >= 0) throw Error(-61, "nsk_debug_spmv: this form runs whole plans only");
   int R = 1, C = 1;
-  if (form == NSK_DBG_SPMV_BLK22 || form == NSK_DBG_SPMV_BLK22_F32 || form == NSK_DBG_SPMV_BLK_FUSED) R = C = 2;
+  if (form == NSK_DBG_SPMV_BLK22 || form == NSK_DBG_SPMV_BLK22_F32 || form == NSK_DBG_SPMV_BLK_FUSED || res) R = C = 2;
   if (form == NSK_DBG_SPMV_BLK21 || epi) R = 2;
   if (form == NSK_DBG_SPMV_BLK12) C = 2;
   const bool blocked = form >= NSK_DBG_SPMV_BLK22 && form != NSK_DBG_SPMV_STREAM2 && form != NSK_DBG_SPMV_STREAM_I16 && form != NSK_DBG_SPMV_STREAM_I16_F32;
@@ -453,7 +455,7 @@ int nsk_debug_spmv(nsk_handle h, int form, int lpr, int mode, int misalign, int 
     case NSK_DBG_SPMV_STREAM_F32: case NSK_DBG_SPMV_STREAM_I16_F32:
       A.inner32 = 2;
       A.refresh_f32(st, false);
-      info[1] = A.spmv_launch(st, SpmvForm::stream_f32, xa.p, xag.p, yv.p, 0, nullptr, c0, c1);
+      info[1] = A.spmv_launch(st, SpmvForm::stream_f32, xa.p, xag.p, yv.p, mode, zv.p, c0, c1);
       break;
     case NSK_DBG_SPMV_BLK22: case NSK_DBG_SPMV_BLK21: case NSK_DBG_SPMV_BLK12: case NSK_DBG_SPMV_BLK11:
       A.spmv_launch(st, SpmvForm::blk, xa.p, xag.p, yv.p, 0, nullptr, c0, c1);
@@ -462,6 +464,14 @@ int nsk_debug_spmv(nsk_handle h, int form, int lpr, int mode, int misalign, int 
       A.inner32 = 1;
       A.refresh_f32(st, false);
       A.spmv_launch(st, SpmvForm::blk_f32, xa.p, xag.p, yv.p, 0, nullptr, c0, c1);
+      break;
+    case NSK_DBG_SPMV_BLK22_RES:
+      nsk::spmv_blk22_residual(st, A.blk_view(), d_rb + c0, n_run, xa.p, xag.p, yv.p, zv.p);
+      break;
+    case NSK_DBG_SPMV_BLK22_RES_F32:
+      A.amg32 = 1;
+      A.refresh_f32(st, false);
+      A.spmv_launch(st, SpmvForm::blk_f32, xa.p, xag.p, yv.p, 2, zv.p, c0, c1);
       break;
     case NSK_DBG_SPMV_BLK21_EPI:
       nsk::spmv_blk_stream(st, A.blk_view(), 2, 1, d_rb + c0, n_run, xa.p, xag.p, yv.p, dv.p, div.p);
@@ -662,6 +672,25 @@ int nsk_debug_index_width(nsk_handle h, int b, int32_t *out3) {
 
 int nsk_debug_spmv_form(int blk_ok, int stream_ok, int inner32, int use_stream, int use_bsr, int mode, int inner) {   // nsk_internal.h
   return (int)spmv_form(blk_ok != 0, stream_ok != 0, inner32, use_stream != 0, use_bsr != 0, mode, inner != 0);
+}
+
+int nsk_debug_amg_spmv_form(int blk_ok, int stream_ok, int amg32, int use_bsr, int mode, int aligned16) {   // nsk_internal.h
+  return (int)amg_spmv_form(blk_ok != 0, stream_ok != 0, amg32 != 0, use_bsr != 0, mode, aligned16 != 0);
+}
+
+int64_t nsk_debug_amg_level(nsk_handle h, int shard, int level, int which, int32_t *rowptr, int32_t *col, double *val,
+                            double *dinv_or_inverse) {   // nsk_internal.h
+  NSK_TRY_DEV(h)
+  if (h->prec_type < 0) throw Error(-46, "call nsk_setup_preconditioner first");
+  if (!h->amg_active) throw Error(-62, "nsk_debug_amg_level: the current set-up has no velocity AMG");
+  h->amg_ready();
+  return h->amgF.debug_level(shard, level, which, rowptr, col, val, dinv_or_inverse);
+  NSK_CATCH(h)
+}
+
+int nsk_debug_amg_forms(nsk_handle h, int64_t *out5) {   // nsk_internal.h
+  for (int k = 0; k < 5; ++k) out5[k] = h->amg_active ? h->amgF.form_launches[k] : 0;
+  return 0;
 }
 
 int nsk_debug_pool_counts(nsk_handle h, int32_t *out6) {   // nsk_internal.h

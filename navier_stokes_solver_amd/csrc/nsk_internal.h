@@ -151,12 +151,15 @@ int nsk_debug_krylov(struct nsk_handle_s *h, int op, int n, int m, int offset, c
  * above the cap, 5 (NSK_DBG_SPMV_STREAM_I16) a run spans 65 536 columns or more.  Device and stream of the handle; 0, 1 or
  * a negative error code.
  * NSK_DBG_SPMV_STREAM_I16: the stream kernel on 16-bit column offsets (Csr::build_index16), modes as
- * NSK_DBG_SPMV_STREAM; NSK_DBG_SPMV_STREAM_I16_F32: the same on the fp32 copy of the values (y = A x only). */
+ * NSK_DBG_SPMV_STREAM; NSK_DBG_SPMV_STREAM_I16_F32: the same on the fp32 copy of the values (y = A x only).
+ * NSK_DBG_SPMV_STREAM_F32 takes modes 1 and 2 as well (the velocity AMG's operators under NSK_OPT_AMG_PRECISION = 32).
+ * NSK_DBG_SPMV_BLK22_RES / _RES_F32: y = z - A x on 2 x 2 node blocks, double / fp32 values (mode 2 only) — the
+ * double form exists for this hook alone, no product of the library launches it. */
 enum {
   NSK_DBG_SPMV_CSRV = 0, NSK_DBG_SPMV_STREAM = 1, NSK_DBG_SPMV_STREAM_F32 = 2, NSK_DBG_SPMV_BLK22 = 3,
   NSK_DBG_SPMV_BLK21 = 4, NSK_DBG_SPMV_BLK12 = 5, NSK_DBG_SPMV_BLK11 = 6, NSK_DBG_SPMV_BLK22_F32 = 7,
   NSK_DBG_SPMV_BLK21_EPI = 8, NSK_DBG_SPMV_STREAM2 = 9, NSK_DBG_SPMV_BLK_FUSED = 10, NSK_DBG_SPMV_STREAM_I16 = 11,
-  NSK_DBG_SPMV_STREAM_I16_F32 = 12
+  NSK_DBG_SPMV_STREAM_I16_F32 = 12, NSK_DBG_SPMV_BLK22_RES = 13, NSK_DBG_SPMV_BLK22_RES_F32 = 14
 };
 struct nsk_dbg_spmv_mat {
   int32_t n_rows, n_cols, n_own_cols, pad_;
@@ -290,6 +293,23 @@ int nsk_debug_index_width(struct nsk_handle_s *h, int b, int32_t *out3);
  * 0 CSR-vector, 1 stream, 2 stream on the fp32 values, 3 blocked, 4 blocked on the fp32 values.  (Declared in
  * include/nsk.h as well: solver.EXPORTS lists it, and that list is the public header's.) */
 int nsk_debug_spmv_form(int blk_ok, int stream_ok, int inner32, int use_stream, int use_bsr, int mode, int inner);
+/* The rule that chooses the kernel of a product inside the velocity AMG's V-cycle (nsk::amg_spmv_form) on bare
+ * flags: no handle, no device.  Same return values.  amg32 = 0 gives nsk_debug_spmv_form(blk_ok, stream_ok, 0, 1, 0, mode, 0)
+ * whatever use_bsr and aligned16 are. */
+int nsk_debug_amg_spmv_form(int blk_ok, int stream_ok, int amg32, int use_bsr, int mode, int aligned16);
+/* One operator of the velocity AMG of the current set-up (built first when it is pending, as nsk_amg_info does), in double as
+ * the set-up left it — also under NSK_OPT_AMG_PRECISION = 32, whose fp32 copies are these values rounded.  which: 0 the
+ * level's A (n x n; n, nnz from nsk_amg_info), 1 P (n x n of the next level), 2 R (its transpose); 3 is a query: returns 1
+ * when the level holds a dense inverse (the coarsest level up to 2 048 rows), else 0, and copies nothing.  rowptr (rows + 1),
+ * col, val (nnz each) may each be null; all null is the size query.  dinv_or_inverse (which 0, may be null): the level's
+ * dinv, n doubles, or where the level holds a dense inverse that, n x n row-major.  Returns the operator's number of
+ * entries, or a negative error code (-61: no such shard, level or operator — the last level has no P and R; -62: the
+ * set-up has no AMG). */
+int64_t nsk_debug_amg_level(struct nsk_handle_s *h, int shard, int level, int which, int32_t *rowptr, int32_t *col, double *val,
+                            double *dinv_or_inverse);
+/* Products the V-cycles of the current hierarchy have launched since it was built, by kernel form: out5[f], f as
+ * nsk_debug_spmv_form returns it (0 CSR-vector .. 4 blocked on fp32 values); all 0 without an AMG. */
+int nsk_debug_amg_forms(struct nsk_handle_s *h, int64_t *out5);
 /* Work vectors of the handle's three pools: out6 = {allocated, free} of the velocity, the pressure and the block pool. */
 int nsk_debug_pool_counts(struct nsk_handle_s *h, int32_t *out6);
 /* Read-only view of what the last nsk_assemble left on a Q3/Q2 handle (tests/test_gpu_asm_kernels.py): copies

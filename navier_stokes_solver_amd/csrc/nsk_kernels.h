@@ -59,10 +59,13 @@ constexpr int kStreamRows = 64;  // rows per run = workgroup size / lanes per ro
 int spmv_stream(hipStream_t s, const CsrView &A, const int *rowblk, int nblk, int even_rows, const double *x_own,
                 const double *x_ghost, double *y, int mode, const double *z, const unsigned short *off16 = nullptr,
                 const int *colbase = nullptr);
-// fp32 values (y = A x only): the same plan, lane decomposition and summation order as the double launch, so the result
-// has the bits of the double kernel run on the values rounded to float beforehand
+// fp32 values: the same plan, lane decomposition and summation order as the double launch, so the result has the bits of
+// the double kernel run on the values rounded to float beforehand.  Modes 1 and 2 (the velocity AMG's operators,
+// NSK_OPT_AMG_PRECISION = 32) exist on int32 columns only: with off16 the launcher refuses — nothing is launched and it
+// returns -1, where every launch returns its VEC (2 or 3) and an empty range 0; Csr::spmv_launch makes an Error of it
 int spmv_stream(hipStream_t s, const CsrView32 &A, const int *rowblk, int nblk, int even_rows, const double *x_own,
-                const double *x_ghost, double *y, const unsigned short *off16 = nullptr, const int *colbase = nullptr);
+                const double *x_ghost, double *y, const unsigned short *off16 = nullptr, const int *colbase = nullptr,
+                int mode = 0, const double *z = nullptr);
 int spmv2_stream(hipStream_t s, const CsrView &A, const double *xa_own, const double *xa_ghost, const CsrView &B,
                  const double *xb_own, const double *xb_ghost, const int *rowblk, int nblk, double *y);
 
@@ -85,9 +88,14 @@ constexpr int kBlkMax = 1024;  // blocks per workgroup (both matrices together i
 // epi_d != null (R x C = 2 x 1 only): y = ((y .* epi_d) - A x) .* epi_dinv instead (aSIMPLE's velocity correction)
 void spmv_blk_stream(hipStream_t s, const BlkView &A, int R, int C, const int *rowblk, int nblk, const double *x_own,
                      const double *x_ghost, double *y, const double *epi_d = nullptr, const double *epi_dinv = nullptr);
-// fp32 2x2 blocks (F's copy for the inner solves), y = A x: same bits as the double launch on the rounded values
+// fp32 2x2 blocks (F's copy for the inner solves and the velocity AMG), y = A x, or y = z - A x where z is given (z and y
+// 16-byte aligned: one pair per node row, one rounding per component): same bits as the double launch on the rounded values
 void spmv_blk_stream(hipStream_t s, const BlkView32 &A, const int *rowblk, int nblk, const double *x_own,
-                     const double *x_ghost, double *y);
+                     const double *x_ghost, double *y, const double *z = nullptr);
+// y = z - A x on double 2x2 blocks: the kernel above with V = double.  For the test hook nsk_debug_spmv alone — no product
+// of the library launches it (the fp64 V-cycle keeps the scalar stream form and its bits)
+void spmv_blk22_residual(hipStream_t s, const BlkView &A, const int *rowblk, int nblk, const double *x_own,
+                         const double *x_ghost, double *y, const double *z);
 // y = A xa + B xb with A 2x2-blocked and B 2x1-blocked over the same block rows (velocity block row of J)
 void spmv_blk_fused22_21(hipStream_t s, const BlkView &A, const double *xa_own, const double *xa_ghost,
                          const BlkView &B, const double *xb_own, const double *xb_ghost, const int *rowblk, int nblk,

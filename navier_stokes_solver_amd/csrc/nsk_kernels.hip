@@ -344,6 +344,8 @@ __device__ __forceinline__ void blk_products(const BlkViewT<V> &A, int k0, int k
 
 // EPI = 1 (aSIMPLE's velocity correction, NSSolver.hpp:343-349, in the kernel's epilogue instead of two more passes
 // over the vector): y = ((y .* d) - A x) .* dinv, with the products rounded one by one like the separate vector calls.
+// EPI = 2 (2 x 2 only; the velocity AMG's residual products on F's node blocks, NSK_OPT_AMG_PRECISION = 32): y = d - A x,
+// d read as one pair per node row, the subtraction rounded once per component whatever V is.
 template <class V, int R, int C, int EPI>
 __global__ __launch_bounds__(BLK) void spmv_blk_kernel(BlkViewT<V> A, const int *__restrict__ rowblk,
                                                        const double *__restrict__ xo, const double *__restrict__ xg,
@@ -370,6 +372,11 @@ __global__ __launch_bounds__(BLK) void spmv_blk_kernel(BlkViewT<V> A, const int 
       const double2 di = *reinterpret_cast<const double2 *>(dinv + 2 * (size_t)r);
       s0 = __dmul_rn(__dsub_rn(__dmul_rn(yo.x, dd.x), s0), di.x);
       s1 = __dmul_rn(__dsub_rn(__dmul_rn(yo.y, dd.y), s1), di.y);
+    }
+    if (EPI == 2 && R == 2) {
+      const double2 zz = *reinterpret_cast<const double2 *>(d + 2 * (size_t)r);
+      s0 = __dsub_rn(zz.x, s0);
+      s1 = __dsub_rn(zz.y, s1);
     }
     if (R == 2) *reinterpret_cast<double2 *>(y + 2 * (size_t)r) = make_double2(s0, s1);
     else y[r] = s0;
@@ -1705,18 +1712,25 @@ int spmv_stream(hipStream_t s, const CsrView &A, const int *rowblk, int nblk, in
 }
 
 int spmv_stream(hipStream_t s, const CsrView32 &A, const int *rowblk, int nblk, int even_rows, const double *xo,
-                const double *xg, double *y, const unsigned short *off16, const int *colbase) {
+                const double *xg, double *y, const unsigned short *off16, const int *colbase, int mode, const double *z) {
   if (nblk <= 0) return 0;
   // the double launcher's choice of pair loads: the same lanes sum the same entries
-  const double *z = nullptr;
-#define NSK_SS(V)                                                                                                                      \
+#define NSK_SS(V, M)                                                                                                                   \
   do {                                                                                                                                 \
-    if (off16) hipLaunchKernelGGL((spmv_stream_kernel<float, V, 0, unsigned short>), dim3(nblk), dim3(BLK), 0, s, A, rowblk, xo, xg, y, z, off16, colbase); \
-    else hipLaunchKernelGGL((spmv_stream_kernel<float, V, 0, int>), dim3(nblk), dim3(BLK), 0, s, A, rowblk, xo, xg, y, z, off16, colbase); \
+    if (off16) hipLaunchKernelGGL((spmv_stream_kernel<float, V, M, unsigned short>), dim3(nblk), dim3(BLK), 0, s, A, rowblk, xo, xg, y, z, off16, colbase); \
+    else hipLaunchKernelGGL((spmv_stream_kernel<float, V, M, int>), dim3(nblk), dim3(BLK), 0, s, A, rowblk, xo, xg, y, z, off16, colbase); \
   } while (0)
-  if (even_rows) { NSK_SS(2); return 2; }
-  NSK_SS(3);
+  // modes 1 and 2 (the velocity AMG's coarse operators and prolongators, NSK_OPT_AMG_PRECISION = 32) on int32 columns only:
+  // the AMG builds no 16-bit offsets.  Asked for one, nothing is launched and the caller is told (-1)
+#define NSK_SM(V, M) hipLaunchKernelGGL((spmv_stream_kernel<float, V, M, int>), dim3(nblk), dim3(BLK), 0, s, A, rowblk, xo, xg, y, z, nullptr, nullptr)
+  if (mode != 0 && off16) return -1;
+  if (even_rows) {
+    if (mode == 0) NSK_SS(2, 0); else if (mode == 1) NSK_SM(2, 1); else NSK_SM(2, 2);
+    return 2;
+  }
+  if (mode == 0) NSK_SS(3, 0); else if (mode == 1) NSK_SM(3, 1); else NSK_SM(3, 2);
   return 3;
+#undef NSK_SM
 #undef NSK_SS
 }
 
@@ -1763,9 +1777,16 @@ void spmv_blk_stream(hipStream_t s, const BlkView &A, int R, int C, const int *r
 }
 
 void spmv_blk_stream(hipStream_t s, const BlkView32 &A, const int *rowblk, int nblk, const double *xo, const double *xg,
-                     double *y) {
+                     double *y, const double *z) {
+  if (nblk <= 0) return;
+  if (z) hipLaunchKernelGGL((spmv_blk_kernel<float, 2, 2, 2>), dim3(nblk), dim3(BLK), 0, s, A, rowblk, xo, xg, y, z, nullptr);
+  else hipLaunchKernelGGL((spmv_blk_kernel<float, 2, 2, 0>), dim3(nblk), dim3(BLK), 0, s, A, rowblk, xo, xg, y, nullptr, nullptr);
+}
+
+void spmv_blk22_residual(hipStream_t s, const BlkView &A, const int *rowblk, int nblk, const double *xo, const double *xg,
+                         double *y, const double *z) {
   if (nblk > 0)
-    hipLaunchKernelGGL((spmv_blk_kernel<float, 2, 2, 0>), dim3(nblk), dim3(BLK), 0, s, A, rowblk, xo, xg, y, nullptr, nullptr);
+    hipLaunchKernelGGL((spmv_blk_kernel<double, 2, 2, 2>), dim3(nblk), dim3(BLK), 0, s, A, rowblk, xo, xg, y, z, nullptr);
 }
 
 void spmv_blk_fused22_21(hipStream_t s, const BlkView &A, const double *xao, const double *xag, const BlkView &B,

@@ -135,6 +135,15 @@ void H::setup(int type, int variant_, double alpha_) {
   // PreconditionBlockTriangular, stationary: preconditioner_velocity is an AMG (NSSolverStationary.hpp:225,231)
   amg_active = type == 1 && variant == 0 && velocity_amg != 0;
   amg_pending = false;
+  // fp32 storage of the V-cycle's operators; NSK_AMG_PRECISION=32 / 64 overrides the option (A/B measurements with
+  // unchanged callers), any other value is ignored.  The hierarchy converts when it is built (Amg::setup)
+  static const int env_amg = [] {
+    const char *e = std::getenv("NSK_AMG_PRECISION");
+    const int v = e ? std::atoi(e) : 0;
+    return v == 32 || v == 64 ? v : 0;
+  }();
+  amgF.value_bits = amg_active && (env_amg ? env_amg : amg_precision) == 32 ? 32 : 64;
+  amgF.use_bsr = use_bsr != 0;
   if (amg_active) {
     amgF.clear();
     amg_pending = true;
@@ -255,8 +264,12 @@ void H::setup(int type, int variant_, double alpha_) {
     // the copy this block would hold: F's 2 x 2 blocks (the only shape build_blocked gives F, and the only one of the
     // blocked fp32 kernel), else the scalar values — kept where the rule gives the inner product an _f32 form for it
     A.inner32 = !wanted ? 0 : b == NSK_BLK_F ? 1 : 2;
-    if (!is_f32(form_of(A, 0, true))) { A.release_f32(); continue; }   // (release_f32 puts inner32 back to 0)
-    A.refresh_f32(s(), true);
+    if (!is_f32(form_of(A, 0, true))) A.inner32 = 0;
+    // (F's copies may also serve the V-cycle, level 0 being F itself: Amg::setup names them in amg32 when the hierarchy is
+    // built and this loop leaves them alone meanwhile; without an fp32 AMG in this set-up nothing of it remains)
+    if (!(b == NSK_BLK_F && amgF.value_bits == 32)) A.amg32 = 0;
+    if (!A.inner32 && !A.amg32) { A.release_f32(); continue; }
+    if (A.inner32) A.refresh_f32(s(), true);
   }
   ctx.sync();
   for (int b : {(int)NSK_BLK_F, (int)NSK_BLK_MP, (int)NSK_BLK_S}) {
@@ -266,6 +279,8 @@ void H::setup(int type, int variant_, double alpha_) {
     NSK_HIP(hipMemcpy(&over, A.f32_overflow.p, sizeof(unsigned), hipMemcpyDeviceToHost));
     if (over) {
       for (Csr *c : {&blk[NSK_BLK_F], &blk[NSK_BLK_MP], &blk[NSK_BLK_S]}) c->release_f32();
+      amgF.clear();
+      amg_pending = false;
       prec_type = -1;   // no preconditioner: call nsk_setup_preconditioner again (e.g. with the option at 64)
       static const char *names[6] = {"F (block 0,0)", "Bt", "B", "M_p (pressure mass)", "Bt ghost rows", "S (Schur approximation)"};
       throw Error(-48, std::string("NSK_OPT_INNER_MATRIX_PRECISION = 32: ") + std::to_string(over) + " value(s) of " +

@@ -35,6 +35,9 @@ def report_factor_precision(ls):
         print("[nsk] NSK_INNER_MATRIX_PRECISION=32: inner-solve matrices stored in fp32 (deviation from the reference)")
     if ls.rank == 0 and ls.inner_basis_bytes() == 4:
         print("[nsk] NSK_INNER_BASIS_PRECISION=32: inner FGMRES basis on F stored in fp32 (deviation from the reference)")
+    # (the question builds a pending hierarchy: the one the next solve would build at its first application)
+    if ls.amg_value_bytes() == 4 and ls.rank == 0:
+        print("[nsk] NSK_AMG_PRECISION=32: velocity AMG operators stored in fp32 (deviation from the reference)")
     if ls.rank == 0 and ls.inner_matrix_free() == 1:
         print("[nsk] NSK_INNER_MATRIX_FREE_F=1: inner FGMRES multiplies by the matrix-free F of the last assembly")
 

@@ -37,6 +37,7 @@ OPT_SCHUR_SIGN = 14   # +1 the reference's S (default); -1: labelled deviation, 
 OPT_FACTOR_PRECISION = 16  # 64 (default) / 32: off-diagonal factor values stored in fp32 — labelled deviation, see include/nsk.h
 OPT_INNER_MATRIX_PRECISION = 17  # 64 (default) / 32: inner solves multiply by fp32 copies of F, S, M_p — labelled deviation, see include/nsk.h
 OPT_INNER_BASIS_PRECISION = 18  # 64 (default) / 32: the inner FGMRES on F keeps its Krylov basis in fp32 — labelled deviation, see include/nsk.h
+OPT_AMG_PRECISION = 20  # 64 (default) / 32: the velocity AMG's V-cycle multiplies by fp32 copies of A, P, R — labelled deviation, see include/nsk.h
 OPT_INNER_MATRIX_FREE_F = 19  # 0 (default) / 1: the inner FGMRES on F multiplies by the matrix-free F of the last nsk_assemble, see include/nsk.h
 TIMEOP_MATFREE_F = 56      # time_op(TIMEOP_MATFREE_F): the matrix-free product with F (needs a valid assembly, not the option)
 TIMEOP_INNER_SPMV = 50     # time_op(TIMEOP_INNER_SPMV + blk): the inner solves' SpMV of F, M_p or S
@@ -53,7 +54,7 @@ EXPORTS = [
     "nsk_set_support_points",
     "nsk_set_block_csr", "nsk_update_values", "nsk_set_option", "nsk_setup_preconditioner", "nsk_solve",
     "nsk_upload_system", "nsk_solve_resident", "nsk_download_solution", "nsk_spmv", "nsk_jacobian_vmult", "nsk_dot", "nsk_vec_op",
-    "nsk_tri_apply", "nsk_amg_info", "nsk_tri_get_perm", "nsk_tri_get_value_bytes", "nsk_inner_value_bytes", "nsk_inner_basis_bytes", "nsk_inner_matrix_free", "nsk_matfree_f", "nsk_inner_spmv", "nsk_precond_vmult", "nsk_block_nnz", "nsk_get_block", "nsk_get_stats",
+    "nsk_tri_apply", "nsk_amg_info", "nsk_amg_value_bytes", "nsk_tri_get_perm", "nsk_tri_get_value_bytes", "nsk_inner_value_bytes", "nsk_inner_basis_bytes", "nsk_inner_matrix_free", "nsk_matfree_f", "nsk_inner_spmv", "nsk_precond_vmult", "nsk_block_nnz", "nsk_get_block", "nsk_get_stats",
     "nsk_reset_stats", "nsk_get_history", "nsk_cancel", "nsk_abort_group", "nsk_assembly_set_cells", "nsk_assembly_set_simplex", "nsk_assembly_set_dirichlet", "nsk_state_set", "nsk_state_get",
     "nsk_state_save", "nsk_state_save_old", "nsk_state_update", "nsk_assemble", "nsk_scale_values", "nsk_download_rhs", "nsk_time_assemble", "nsk_time_op", "nsk_profile_begin", "nsk_profile_read", "nsk_profile_end",
     "nsk_debug_spmv_form",
@@ -149,6 +150,7 @@ def lib() -> C.CDLL:
         L.nsk_tri_get_perm.argtypes = [vp, C.c_int, i32p]
         L.nsk_tri_get_value_bytes.argtypes = [vp, C.c_int, C.POINTER(C.c_int32)]
         L.nsk_inner_value_bytes.argtypes = [vp, C.c_int, C.POINTER(C.c_int32)]
+        L.nsk_amg_value_bytes.argtypes = [vp, C.POINTER(C.c_int32)]
         L.nsk_inner_basis_bytes.argtypes = [vp, C.POINTER(C.c_int32)]
         L.nsk_inner_matrix_free.argtypes = [vp, C.POINTER(C.c_int32)]
         L.nsk_matfree_f.argtypes = [vp, f64p, f64p]
@@ -430,6 +432,13 @@ class LinearSolver:
         inner FGMRES on F."""
         b = C.c_int32(0)
         self._ck(self.L.nsk_inner_basis_bytes(self.h, C.byref(b)))
+        return b.value
+
+    def amg_value_bytes(self):
+        """Bytes per stored value of the operators the velocity AMG's V-cycle multiplies by: 4 (fp32,
+        OPT_AMG_PRECISION = 32), 8 (fp64), 0 when the set-up has no AMG.  Builds a pending hierarchy first."""
+        b = C.c_int32(0)
+        self._ck(self.L.nsk_amg_value_bytes(self.h, C.byref(b)))
         return b.value
 
     def inner_matrix_free(self):
