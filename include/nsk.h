@@ -35,7 +35,8 @@
  *        faces or a record list on a P2/P1 handle, edges or patches on the other kind; -72: a cell index out of range;
  *        -73: no state); the record calls also -69 without a record list and -60 for subdivisions outside 1..4
  *   -70 single-launch triangular solve gave up waiting AND the per-colour retry failed too (see NSK_OPT_TRI_SYNC_FREE)
- *   -80..-84 AMG set-up (operator too large for 32-bit indices, rows too wide, rounds / estimates that do not end)
+ *   -80..-85 AMG set-up (operator too large for 32-bit indices, rows too wide, rounds / estimates that do not end; -85:
+ *        NSK_OPT_SCHUR_AMG, a level's diagonal with both signs or a zero — the set-up falls back to ILU(S), see there)
  *   -1 any other exception
  */
 #ifndef NSK_H
@@ -196,7 +197,7 @@ enum {
                                  NSK_OPT_INNER_MATRIX_PRECISION = 32 no fp32 copy of F is made while the product is
                                  matrix-free.  Other values: -61.  NSK_INNER_MATRIX_FREE_F=0 / 1 in the environment
                                  overrides the option for every handle (A/B runs; other values count as unset) */
-  NSK_OPT_AMG_PRECISION = 20 /* storage precision of the operators the velocity AMG's V-cycle multiplies by (stationary
+  NSK_OPT_AMG_PRECISION = 20, /* storage precision of the operators the velocity AMG's V-cycle multiplies by (stationary
                                  blockTriangular, NSK_OPT_VELOCITY_AMG = 1).  64 (default): double, as today and the same
                                  bits.  32: the values of every level's A, P and R, on every shard, are stored rounded to
                                  float (nearest even) once the level is finished, and the cycle's products read those:
@@ -217,7 +218,30 @@ enum {
                                  which is flexible and stops at a loose tolerance, and the outer FGMRES stays double and
                                  checks the true residual, so only the preconditioner is perturbed.  Other values: -61.
                                  NSK_AMG_PRECISION=32 / 64 in the environment overrides the option for every handle (A/B
-                                 runs; other values ignored).  Independent of the three precision options above */
+                                 runs; other values ignored).  Independent of the three precision options above.  Under
+                                 NSK_OPT_SCHUR_AMG it governs the hierarchy of S too: one knob for the operators a V-cycle
+                                 multiplies by (S itself, level 0 of one shard, through scalar fp32 values on its 16-bit
+                                 column offsets) */
+  NSK_OPT_SCHUR_AMG = 21      /* preconditioner of the inner CG on S in the STATIONARY aSIMPLE set-up (type 2, variant 0).
+                                 0 (default): ILU(0) of S, as the reference (Ifpack ILU, NSSolverStationary.hpp:325-326),
+                                 as today and the same bits.  1: one V-cycle of a smoothed-aggregation hierarchy of S — the
+                                 method, parameters and device set-up of the velocity AMG (nsk_amg_info), built from S at
+                                 every nsk_setup_preconditioner right after its values are formed (S changes with every
+                                 set-up); sub-domains as NSK_OPT_SUBDOMAINS cuts the pressure space, ghost columns dropped.
+                                 ILU(S) is then neither analysed nor factorised: the pressure slot of nsk_tri_apply applies
+                                 the cycle, nsk_tri_get_perm gives the identity and nsk_tri_get_value_bytes 0, as the
+                                 velocity slot does under the velocity AMG; profile class 21 samples the cycle.  The CG, its
+                                 tolerance, its start from the last delta_p and alpha are untouched.  S is symmetric and its
+                                 diagonal of one sign, and so is the cycle: CG takes it as it takes ILU(S).  Where the
+                                 hierarchy cannot be built — a row of a set-up product over 512 distinct columns (-81), a
+                                 diagonal on some level with both signs or a zero (-85), -80..-85 in general — the set-up
+                                 factorises ILU(S) as under 0 and ONE line `[nsk] warning: ...` per handle says so on
+                                 stderr; nsk_schur_amg_info reports which of the two stands.  Types 0 and 1 and the
+                                 unsteady variant ignore the option.  A LABELLED DEVIATION from the reference: the inner
+                                 solve stops at 1e-1 and the outer FGMRES checks the true residual, so only the
+                                 preconditioner is changed.  Takes effect at the next nsk_setup_preconditioner.  Other
+                                 values: -61.  NSK_SCHUR_AMG=0 / 1 in the environment overrides the option for every handle
+                                 (A/B runs; other values count as unset) */
 };
 
 typedef struct {
@@ -307,7 +331,8 @@ int nsk_dot(nsk_handle h, int n, const double *x, const double *y, double *dot_o
 int nsk_vec_op(nsk_handle h, int op, int n, double a, double c, const double *x, double *y, const double *z,
                const double *d, double *scalar_out);
 /* x = M^-1 b with the velocity / pressure preconditioner of the current setup (triangular solves, or one AMG
- * V-cycle for the velocity block of the stationary blockTriangular setup) */
+ * V-cycle for the velocity block of the stationary blockTriangular setup, and for the pressure block of the stationary
+ * aSIMPLE set-up under NSK_OPT_SCHUR_AMG) */
 int nsk_tri_apply(nsk_handle h, int which, const double *b, double *x);
 /* Hierarchy of the velocity AMG of the current setup (replaces TrilinosWrappers::PreconditionAMG,
  * NSSolverStationary.hpp:225): returns the number of levels of sub-domain `shard` (0 when the setup has no AMG)
@@ -316,11 +341,19 @@ int nsk_amg_info(nsk_handle h, int shard, int level, int64_t *rows, int64_t *nnz
 /* bytes per stored value of the operators the V-cycle of the current set-up multiplies by: 4 (NSK_OPT_AMG_PRECISION = 32),
  * 8 (double), 0 when the set-up has no AMG.  Builds a pending hierarchy first, as nsk_amg_info does. */
 int nsk_amg_value_bytes(nsk_handle h, int32_t *bytes);
+/* Hierarchy of S under NSK_OPT_SCHUR_AMG, with the conventions of nsk_amg_info: the number of levels of sub-domain
+ * `shard` — 0 when the current set-up preconditions S otherwise (option off, another type or variant, or the fallback
+ * to ILU(S)) — and, for a valid `level`, its size, non-zeros and lambda_max estimate. */
+int nsk_schur_amg_info(nsk_handle h, int shard, int level, int64_t *rows, int64_t *nnz, double *lambda_max);
+/* x = one V-cycle of that hierarchy on b (owned pressure entries; x is set, not read).  -62 when none stands, -46 before
+ * the first set-up. */
+int nsk_schur_amg_apply(nsk_handle h, const double *b, double *x);
 /* ordering used by that triangular preconditioner: perm[new] = old (identity when natural) */
 int nsk_tri_get_perm(nsk_handle h, int which, int32_t *perm);
 /* bytes per stored off-diagonal value of that triangular preconditioner as its applies read them in the current set-up:
  * 4 (NSK_OPT_FACTOR_PRECISION = 32 and the factor runs through the split-half kernels), 8 (double), 0 when the slot is no
- * triangular factor (the velocity AMG of the stationary blockTriangular preconditioner) */
+ * triangular factor (the velocity AMG of the stationary blockTriangular preconditioner; the pressure slot under
+ * NSK_OPT_SCHUR_AMG) */
 int nsk_tri_get_value_bytes(nsk_handle h, int which, int32_t *bytes);
 /* bytes per matrix value the inner solves of the current set-up read for blk (NSK_BLK_F, NSK_BLK_S or NSK_BLK_MP): 4
  * (NSK_OPT_INNER_MATRIX_PRECISION = 32 and the block's SpMV takes a stream kernel), 8 (double), 0 when this set-up runs

@@ -196,8 +196,13 @@ struct NewtonDriver {
       // NSK_INNER_MATRIX_FREE_F=1 (read by the library): the same operator in double, no deviation in storage
       int32_t mf = 0;
       check(h, nsk_inner_matrix_free(h, &mf), "nsk_inner_matrix_free");
-      if (mf == 1)
+      if (mf == 1) {
         std::printf("%s[nsk] NSK_INNER_MATRIX_FREE_F=1: inner FGMRES multiplies by the matrix-free F of the last assembly\n", nl);
+        nl = "";
+      }
+      // NSK_SCHUR_AMG=1 (read by the library): a hierarchy of S stands, so the inner CG on S is preconditioned by its V-cycle
+      if (nsk_schur_amg_info(h, 0, -1, nullptr, nullptr, nullptr) > 0)
+        std::printf("%s[nsk] NSK_SCHUR_AMG=1: inner CG on S preconditioned by an AMG V-cycle on S, not ILU(S) (deviation from the reference)\n", nl);
     }
     int iters = 0;
     double res = 0.0;

@@ -108,12 +108,12 @@ struct Scratch {
   size_t top = 0, level_total = 0;
   std::vector<DBuf<char>> spill;
   DBuf<long long> total;
-  DBuf<int> counters;   // [0] undecided rows, [1] error word of the row products
+  DBuf<int> counters;   // [0] undecided rows, [1] error word of the row products, [2] signs met on a level's diagonal
   int rounds = 0;       // independent-set rounds so far (NSK_AMG_TIMING)
   Guarded *exact = nullptr;   // test hook: every take() is an allocation of its own at its exact size between guard words
   Scratch(Ctx *c, DBuf<char> &arena_, size_t &want_) : ctx(c), arena(arena_), want(want_) {
     total.alloc(1);
-    counters.alloc(2);
+    counters.alloc(3);
   }
   template <class T>
   T *take(size_t count) {
@@ -679,7 +679,14 @@ void Amg::build(AmgHierarchy &H, Csr *A0, std::unique_ptr<Csr> own0) {
     L->n = n;
     double *ad = S.take<double>((size_t)n);
     L->dinv.alloc((size_t)n);
-    amgk::diag(s, mat(A), ad, L->dinv.p);
+    if (one_sign_diag) S.zero_counter(2);
+    amgk::diag(s, mat(A), ad, L->dinv.p, one_sign_diag ? reinterpret_cast<unsigned *>(S.counters.p + 2) : nullptr);
+    if (one_sign_diag) {
+      const int signs = S.read_counter(2);   // 1: all positive, 2: all negative
+      if (signs != 1 && signs != 2)
+        throw Error(-85, "AMG set-up: the diagonal of level " + std::to_string(l) + " holds " +
+                             ((signs & 4) ? "a zero (or a row lists none)" : "both signs"));
+    }
     L->r.alloc((size_t)n);
     L->w.alloc((size_t)n);
     lap(l, "diagonal");
@@ -813,7 +820,8 @@ void Amg::build_all(Csr &F, const std::vector<int> &shard_off) {
 }
 
 void Amg::mv(Csr &A, const double *x, double *y, int mode, const double *z) {
-  // (no ghost tail, no 16-bit offsets; the rule: amg_spmv_form, nsk_core.hpp)
+  // (no ghost tail; 16-bit offsets only where level 0 is the caller's S, which carries them: y = A x and y = z - A x, both
+  // with a kernel in either precision; the rule: amg_spmv_form, nsk_core.hpp)
   const bool aligned16 = (((uintptr_t)x | (uintptr_t)y | (uintptr_t)z) & 15) == 0;
   const SpmvForm f = form_of(A, mode, aligned16);
   if (is_f32(f)) {

@@ -13,6 +13,9 @@
 // Rank-local like every preconditioner of the reference's stack under additive Schwarz with overlap 0:
 // ghost columns are dropped (block Jacobi across ranks / sub-domains).
 //
+// The same hierarchy and cycle, built from aSIMPLE's S, precondition the inner CG on S under NSK_OPT_SCHUR_AMG (a second
+// Amg of the handle): the code below is generic over Csr, "F" names the caller's block.
+//
 // Set-up and cycle both run on the device: the set-up with the row-parallel kernels of nsk_amg_kernels.hip from the
 // block's device copy (only row pointers for the SpMV plans and the coarsest operator, for its dense inverse, visit
 // the host), the cycle with the library's CSR-stream SpMV kernels.
@@ -54,6 +57,9 @@ struct Amg {
   // whether level 0 may use F's 2x2 node blocks (NSK_OPT_BSR_VELOCITY)
   int value_bits = 64;
   bool use_bsr = true;
+  // The hierarchy preconditions a CG (the Schur AMG, NSK_OPT_SCHUR_AMG): the cycle must be definite, so every level's
+  // diagonal has to carry one sign and no zero — Error -85 from the set-up otherwise (checked where dinv is formed)
+  bool one_sign_diag = false;
   long form_launches[5] = {0, 0, 0, 0, 0};   // products of the cycles since the set-up, by SpmvForm (test hook)
   int value_bytes() const { return shards.empty() ? 0 : built_bits / 8; }   // of the hierarchy that stands
   // F: device block with host pattern; shard_off: empty = one shard

@@ -24,7 +24,8 @@ void block_count(hipStream_t s, const Mat &A, int r0, int r1, int *len);
 void block_fill(hipStream_t s, const Mat &A, int r0, int r1, const int *rp_out, int *col, double *val);
 
 // ---- aggregation ----
-void diag(hipStream_t s, const Mat &A, double *ad /* |a_ii| */, double *dinv /* 1 / a_ii, or 1 */);
+// signs (may be null; the caller zeroes it): |= 1 for a positive diagonal entry, 2 for a negative one, 4 for a zero or missing one
+void diag(hipStream_t s, const Mat &A, double *ad /* |a_ii| */, double *dinv /* 1 / a_ii, or 1 */, unsigned *signs = nullptr);
 // Strong connections: one bit per entry in 16-bit words, flag_words(nnz, n_rows) of them.  key[i] = undecided key or 0;
 // agg[i] = -1 / -2; *undecided += rows with a strong connection
 size_t flag_words(long nnz, int n_rows);

@@ -131,7 +131,10 @@ __global__ __launch_bounds__(WG) void block_fill_kernel(Mat A, int r0, int r1, c
 }
 
 // ---------------------------------------------------------------- aggregation
-__global__ __launch_bounds__(WG) void diag_kernel(Mat A, double *__restrict__ ad, double *__restrict__ dinv) {
+// signs (may be null): one word that collects, over all rows, bit 0 a positive diagonal, bit 1 a negative one, bit 2 a zero
+// or missing one (an integer OR: the order cannot matter)
+__global__ __launch_bounds__(WG) void diag_kernel(Mat A, double *__restrict__ ad, double *__restrict__ dinv,
+                                                  unsigned *__restrict__ signs) {
   const int g = threadIdx.x / LPR, l = threadIdx.x % LPR;
   const int i = (int)blockIdx.x * RPW + g;
   double d = 0.0;
@@ -147,6 +150,10 @@ __global__ __launch_bounds__(WG) void diag_kernel(Mat A, double *__restrict__ ad
   if (i < A.n_rows && l == 0) {
     ad[i] = fabs(d);
     dinv[i] = d != 0.0 ? 1.0 / d : 1.0;
+    if (signs) {
+      const unsigned bit = d > 0.0 ? 1u : d < 0.0 ? 2u : 4u;
+      if ((__hip_atomic_load(signs, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & bit) == 0) atomicOr(signs, bit);
+    }
   }
 }
 
@@ -653,8 +660,8 @@ void block_fill(hipStream_t s, const Mat &A, int r0, int r1, const int *rp_out, 
   if (r1 > r0) hipLaunchKernelGGL(block_fill_kernel, dim3(ew_grid(r1 - r0)), dim3(WG), 0, s, A, r0, r1, rp_out, col, val);
 }
 
-void diag(hipStream_t s, const Mat &A, double *ad, double *dinv) {
-  if (A.n_rows > 0) hipLaunchKernelGGL(diag_kernel, dim3(row_grid(A.n_rows, RPW)), dim3(WG), 0, s, A, ad, dinv);
+void diag(hipStream_t s, const Mat &A, double *ad, double *dinv, unsigned *signs) {
+  if (A.n_rows > 0) hipLaunchKernelGGL(diag_kernel, dim3(row_grid(A.n_rows, RPW)), dim3(WG), 0, s, A, ad, dinv, signs);
 }
 size_t flag_words(long nnz, int n_rows) { return (size_t)(nnz / LPR) + (size_t)n_rows + 2; }
 void strength(hipStream_t s, const Mat &A, const double *ad, double threshold, uint16_t *flag, uint64_t *key, int *agg,

@@ -265,6 +265,10 @@ int nsk_set_option(nsk_handle h, int opt, double v) {
       if (v != 0.0 && v != 1.0) throw Error(-61, "NSK_OPT_INNER_MATRIX_FREE_F: 0 or 1");
       h->matrix_free_f = (int)v;
       break;
+    case NSK_OPT_SCHUR_AMG:
+      if (v != 0.0 && v != 1.0) throw Error(-61, "NSK_OPT_SCHUR_AMG: 0 or 1");
+      h->schur_amg = (int)v;
+      break;
     case NSK_IOPT_TRI_X_LAYOUT:
       h->x_layout_mode = v == 0.0 ? 0 : 2;
       h->tF_ok = false;
@@ -419,6 +423,7 @@ int nsk_tri_apply(nsk_handle h, int which, const double *b, double *x) {
   const Lease bv(p, true), xv(p, true);
   NSK_HIP(hipMemcpyAsync(bv, b, sizeof(double) * (size_t)p.n, hipMemcpyHostToDevice, h->s()));
   if (which == NSK_TRI_VELOCITY && h->amg_active) { h->amg_ready(); h->amgF.apply(bv, xv); }  // the velocity preconditioner is the AMG
+  else if (which != NSK_TRI_VELOCITY && h->schur_amg_active) h->amgS.apply(bv, xv);           // NSK_OPT_SCHUR_AMG: so is S's
   else T->apply(bv, xv);
   NSK_HIP(hipMemcpyAsync(x, xv, sizeof(double) * (size_t)p.n, hipMemcpyDeviceToHost, h->s()));
   h->ctx.sync();
@@ -450,10 +455,36 @@ int nsk_amg_value_bytes(nsk_handle h, int32_t *bytes) {
   NSK_CATCH(h)
 }
 
+int nsk_schur_amg_info(nsk_handle h, int shard, int level, int64_t *rows, int64_t *nnz, double *lambda_max) {
+  NSK_TRY(h)
+  if (!h->schur_amg_active || shard < 0 || shard >= (int)h->amgS.shards.size()) return 0;
+  const int nl = h->amgS.n_levels(shard);
+  if (level >= 0 && level < nl) {
+    if (rows) *rows = h->amgS.level_rows(shard, level);
+    if (nnz) *nnz = h->amgS.level_nnz(shard, level);
+    if (lambda_max) *lambda_max = h->amgS.level_lambda(shard, level);
+  }
+  return nl;
+  NSK_CATCH(h)
+}
+
+int nsk_schur_amg_apply(nsk_handle h, const double *b, double *x) {
+  NSK_TRY_DEV(h)
+  if (h->prec_type < 0) throw Error(-46, "call nsk_setup_preconditioner first");
+  if (!h->schur_amg_active) throw Error(-62, "nsk_schur_amg_apply: the current set-up has no AMG on S");
+  const Lease bv(h->pool_p, true), xv(h->pool_p, true);
+  NSK_HIP(hipMemcpyAsync(bv, b, sizeof(double) * (size_t)h->n_p(), hipMemcpyHostToDevice, h->s()));
+  h->amgS.apply(bv, xv);
+  NSK_HIP(hipMemcpyAsync(x, xv, sizeof(double) * (size_t)h->n_p(), hipMemcpyDeviceToHost, h->s()));
+  h->ctx.sync();
+  return 0;
+  NSK_CATCH(h)
+}
+
 int nsk_tri_get_value_bytes(nsk_handle h, int which, int32_t *bytes) {
   NSK_TRY(h)
   if (h->prec_type < 0) throw Error(-46, "call nsk_setup_preconditioner first");
-  if (which == NSK_TRI_VELOCITY && h->amg_active) *bytes = 0;   // no triangular factor in this setup
+  if ((which == NSK_TRI_VELOCITY && h->amg_active) || (which != NSK_TRI_VELOCITY && h->schur_amg_active)) *bytes = 0;   // no triangular factor in this setup
   else *bytes = (which == NSK_TRI_VELOCITY ? &h->tF : h->tP)->value_bytes();
   return 0;
   NSK_CATCH(h)
@@ -517,6 +548,10 @@ int nsk_tri_get_perm(nsk_handle h, int which, int32_t *perm) {
   TriSolve *T = which == NSK_TRI_VELOCITY ? &h->tF : h->tP;
   if (which == NSK_TRI_VELOCITY && h->amg_active) {  // no triangular factor in this setup
     for (int i = 0; i < h->n_u(); ++i) perm[i] = i;
+    return 0;
+  }
+  if (which != NSK_TRI_VELOCITY && h->schur_amg_active) {  // nor here: the V-cycle on S (NSK_OPT_SCHUR_AMG)
+    for (int i = 0; i < h->n_p(); ++i) perm[i] = i;
     return 0;
   }
   for (int i = 0; i < T->n; ++i) perm[i] = T->perm.empty() ? i : T->perm[i];
@@ -652,6 +687,7 @@ int nsk_profile_read(nsk_handle h, int op, double *avg_ms, int *n_samples, doubl
   if (bytes) {
     if (op >= 0 && op <= NSK_BLK_S) *bytes = (double)h->blk[op].spmv_bytes();
     else if (op == 20) *bytes = (double)h->tF.apply_bytes();
+    else if (op == 21 && h->schur_amg_active) *bytes = (double)h->amgS.apply_bytes();   // class 21 is the V-cycle on S then
     else if (op == 21 && h->tP) *bytes = (double)h->tP->apply_bytes();
     else *bytes = 0.0;
   }
@@ -660,6 +696,7 @@ int nsk_profile_read(nsk_handle h, int op, double *avg_ms, int *n_samples, doubl
     if (op == NSK_BLK_F && h->matfree_in_effect()) *bytes_format = h->matfree_bytes();
     else if (op >= 0 && op <= NSK_BLK_S) *bytes_format = h->blk[op].format_bytes(h->form_of(h->blk[op], 0, true));
     else if (op == 20) *bytes_format = h->tF.format_bytes();
+    else if (op == 21 && h->schur_amg_active) *bytes_format = h->amgS.format_bytes();
     else if (op == 21 && h->tP) *bytes_format = h->tP->format_bytes();
     else *bytes_format = 0.0;
   }
@@ -743,6 +780,9 @@ int nsk_time_op(nsk_handle h, int op, int reps, double *avg_ms, double *bytes) {
       h->amg_ready();
       by = (double)h->amgF.apply_bytes();
       f = [=]() { h->amgF.apply(xb, yb); };
+    } else if (op == 21 && h->schur_amg_active) {  // and the pressure one the V-cycle on S (NSK_OPT_SCHUR_AMG)
+      by = (double)h->amgS.apply_bytes();
+      f = [=]() { h->amgS.apply(xb, yb); };
     } else {
       by = (double)T->apply_bytes();
       f = [=]() { T->apply(xb, yb); };

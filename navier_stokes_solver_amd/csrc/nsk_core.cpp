@@ -620,7 +620,7 @@ int Csr::spmv_launch(hipStream_t s, SpmvForm f, const double *xo, const double *
     case SpmvForm::blk: nsk::spmv_blk_stream(s, blk_view(), blk_R, blk_C, blk_rowblk.p + c0, c1 - c0, xo, xg, y); return 0;
     case SpmvForm::stream_f32: {
       const int vec = nsk::spmv_stream(s, view32(), rowblk.p + c0, c1 - c0, even_rows, xo, xg, y, off16.p, cb, mode, z);
-      if (vec < 0) throw Error(-1, "fp32 stream SpMV: modes 1 and 2 have no kernel on 16-bit column offsets");
+      if (vec < 0) throw Error(-1, "fp32 stream SpMV: mode 1 (y += A x) has no kernel on 16-bit column offsets");
       return vec;
     }
     default: return nsk::spmv_stream(s, view(), rowblk.p + c0, c1 - c0, even_rows, xo, xg, y, mode, z, off16.p, cb);

@@ -94,6 +94,7 @@ int nsk_debug_tri_trace(nsk_handle h, int which, int64_t *out16, int max_runs, i
   NSK_TRY_DEV(h)
   if (h->prec_type < 0) throw Error(-46, "call nsk_setup_preconditioner first");
   TriSolve *T = which == NSK_TRI_VELOCITY ? &h->tF : h->tP;
+  if (!T) return 0;                                   // (the pressure slot under NSK_OPT_SCHUR_AMG: no triangular factor)
   if (!(T->stream_ready && T->sync_free)) return 0;   // only the scalar single-launch kernels carry the stamps
   const int n_wg = T->n_Lsf + T->n_Usf;
   VecPool &p = which == NSK_TRI_VELOCITY ? h->pool_u : h->pool_p;
@@ -354,7 +355,7 @@ int nsk_debug_spmv(nsk_handle h, int form, int lpr, int mode, int misalign, int 
   const bool two = form == NSK_DBG_SPMV_STREAM2 || form == NSK_DBG_SPMV_BLK_FUSED;
   const bool res = form == NSK_DBG_SPMV_BLK22_RES || form == NSK_DBG_SPMV_BLK22_RES_F32;   // y = z - A x and nothing else
   const bool modes = form == NSK_DBG_SPMV_CSRV || form == NSK_DBG_SPMV_STREAM || form == NSK_DBG_SPMV_STREAM_I16 ||
-                     form == NSK_DBG_SPMV_STREAM_F32 || res;
+                     form == NSK_DBG_SPMV_STREAM_F32 || form == NSK_DBG_SPMV_STREAM_I16_F32 || res;
   const bool epi = form == NSK_DBG_SPMV_BLK21_EPI;
   if (!Am || !y || two != (Bm != nullptr)) throw Error(-61, "nsk_debug_spmv: matrices");
   if (mode < 0 || mode > 2 || (mode != 0 && !modes) || (mode == 2 && !z) || (res && mode != 2)) throw Error(-61, "nsk_debug_spmv: mode");
@@ -663,7 +664,8 @@ int nsk_debug_index_width(nsk_handle h, int b, int32_t *out3) {
   const Csr &A = h->blk[b];
   const TriSolve &T = b == NSK_BLK_S ? h->tS : h->tMp;
   out3[0] = !A.present || h->form_of(A) != SpmvForm::stream ? 0 : A.off16.p ? 16 : 32;
-  const bool halves = T.stream_ready && T.halves_in_use();
+  // (S under NSK_OPT_SCHUR_AMG: no factor in this set-up, whatever an earlier one left in tS)
+  const bool halves = T.stream_ready && T.halves_in_use() && !(b == NSK_BLK_S && h->schur_amg_active);
   out3[1] = !halves ? 0 : T.Loff16.p ? 16 : 32;
   out3[2] = !halves ? 0 : T.Uoff16.p ? 16 : 32;
   return 0;
@@ -690,6 +692,11 @@ int64_t nsk_debug_amg_level(nsk_handle h, int shard, int level, int which, int32
 
 int nsk_debug_amg_forms(nsk_handle h, int64_t *out5) {   // nsk_internal.h
   for (int k = 0; k < 5; ++k) out5[k] = h->amg_active ? h->amgF.form_launches[k] : 0;
+  return 0;
+}
+
+int nsk_debug_schur_amg_forms(nsk_handle h, int64_t *out5) {   // nsk_internal.h
+  for (int k = 0; k < 5; ++k) out5[k] = h->schur_amg_active ? h->amgS.form_launches[k] : 0;
   return 0;
 }
 

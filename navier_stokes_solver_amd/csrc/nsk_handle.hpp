@@ -155,6 +155,17 @@ struct nsk_handle_s {
   TriSolve tF, tMp, tS;
   Amg amgF;                 // velocity AMG of the stationary block-triangular preconditioner
   int velocity_amg = 1;     // NSK_OPT_VELOCITY_AMG
+  // NSK_OPT_SCHUR_AMG: in the stationary aSIMPLE set-up one V-cycle of amgS, built from S at every set-up,
+  // preconditions the inner CG on S instead of ILU(S).  schur_amg_active: the current set-up runs it — tS is then neither
+  // analysed nor factorised and tP is null; every reader of tP asks schur_amg_active first
+  Amg amgS;
+  int schur_amg = 0;
+  bool schur_amg_active = false, schur_amg_warned = false;
+  void pressure_apply_sampled(const double *b, double *x) {   // profile class 21: ILU(S) / ILU(M_p) / SGS, or the cycle on S
+    if (!schur_amg_active) return tri_apply_sampled(*tP, 21, b, x);
+    Sampled smp(sampler, 21, s());
+    amgS.apply(b, x);
+  }
   int schur_sign = 1;       // NSK_OPT_SCHUR_SIGN: +1 the reference's S = B D^-1 Bt, -1 the negated (SIMPLE's) one
   int blas1_pairs = -1;     // NSK_OPT_BLAS1_PAIRS: -1 by variant (stationary on, unsteady off), 0, 1
   int factor_precision = 64;   // NSK_OPT_FACTOR_PRECISION: 64, or 32 (single-precision off-diagonal values of the split halves)

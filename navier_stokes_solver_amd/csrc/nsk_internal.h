@@ -151,7 +151,8 @@ int nsk_debug_krylov(struct nsk_handle_s *h, int op, int n, int m, int offset, c
  * above the cap, 5 (NSK_DBG_SPMV_STREAM_I16) a run spans 65 536 columns or more.  Device and stream of the handle; 0, 1 or
  * a negative error code.
  * NSK_DBG_SPMV_STREAM_I16: the stream kernel on 16-bit column offsets (Csr::build_index16), modes as
- * NSK_DBG_SPMV_STREAM; NSK_DBG_SPMV_STREAM_I16_F32: the same on the fp32 copy of the values (y = A x only).
+ * NSK_DBG_SPMV_STREAM; NSK_DBG_SPMV_STREAM_I16_F32: the same on the fp32 copy of the values (y = A x, and
+ * y = z - A x for the Schur AMG's level 0 under NSK_OPT_AMG_PRECISION = 32; mode 1 has no kernel there: -1).
  * NSK_DBG_SPMV_STREAM_F32 takes modes 1 and 2 as well (the velocity AMG's operators under NSK_OPT_AMG_PRECISION = 32).
  * NSK_DBG_SPMV_BLK22_RES / _RES_F32: y = z - A x on 2 x 2 node blocks, double / fp32 values (mode 2 only) — the
  * double form exists for this hook alone, no product of the library launches it. */
@@ -310,6 +311,8 @@ int64_t nsk_debug_amg_level(struct nsk_handle_s *h, int shard, int level, int wh
 /* Products the V-cycles of the current hierarchy have launched since it was built, by kernel form: out5[f], f as
  * nsk_debug_spmv_form returns it (0 CSR-vector .. 4 blocked on fp32 values); all 0 without an AMG. */
 int nsk_debug_amg_forms(struct nsk_handle_s *h, int64_t *out5);
+/* The same for the hierarchy of S (NSK_OPT_SCHUR_AMG); all 0 while the set-up preconditions S with ILU(S). */
+int nsk_debug_schur_amg_forms(struct nsk_handle_s *h, int64_t *out5);
 /* Work vectors of the handle's three pools: out6 = {allocated, free} of the velocity, the pressure and the block pool. */
 int nsk_debug_pool_counts(struct nsk_handle_s *h, int32_t *out6);
 /* Read-only view of what the last nsk_assemble left on a Q3/Q2 handle (tests/test_gpu_asm_kernels.py): copies

@@ -1720,15 +1720,17 @@ int spmv_stream(hipStream_t s, const CsrView32 &A, const int *rowblk, int nblk, 
     if (off16) hipLaunchKernelGGL((spmv_stream_kernel<float, V, M, unsigned short>), dim3(nblk), dim3(BLK), 0, s, A, rowblk, xo, xg, y, z, off16, colbase); \
     else hipLaunchKernelGGL((spmv_stream_kernel<float, V, M, int>), dim3(nblk), dim3(BLK), 0, s, A, rowblk, xo, xg, y, z, off16, colbase); \
   } while (0)
-  // modes 1 and 2 (the velocity AMG's coarse operators and prolongators, NSK_OPT_AMG_PRECISION = 32) on int32 columns only:
-  // the AMG builds no 16-bit offsets.  Asked for one, nothing is launched and the caller is told (-1)
+  // mode 2 (y = z - A x: four of a V-cycle's five products with a level's operator, NSK_OPT_AMG_PRECISION = 32) also on
+  // 16-bit offsets: S carries them when it is level 0 of the Schur AMG (NSK_OPT_SCHUR_AMG).  Mode 1 (y += A x) on int32
+  // columns only: the cycle takes it on prolongators alone, which the AMG builds without 16-bit offsets.  Asked for
+  // that one, nothing is launched and the caller is told (-1)
 #define NSK_SM(V, M) hipLaunchKernelGGL((spmv_stream_kernel<float, V, M, int>), dim3(nblk), dim3(BLK), 0, s, A, rowblk, xo, xg, y, z, nullptr, nullptr)
-  if (mode != 0 && off16) return -1;
+  if (mode == 1 && off16) return -1;
   if (even_rows) {
-    if (mode == 0) NSK_SS(2, 0); else if (mode == 1) NSK_SM(2, 1); else NSK_SM(2, 2);
+    if (mode == 0) NSK_SS(2, 0); else if (mode == 1) NSK_SM(2, 1); else NSK_SS(2, 2);
     return 2;
   }
-  if (mode == 0) NSK_SS(3, 0); else if (mode == 1) NSK_SM(3, 1); else NSK_SM(3, 2);
+  if (mode == 0) NSK_SS(3, 0); else if (mode == 1) NSK_SM(3, 1); else NSK_SS(3, 2);
   return 3;
 #undef NSK_SM
 #undef NSK_SS

@@ -144,6 +144,21 @@ void H::setup(int type, int variant_, double alpha_) {
   }();
   amgF.value_bits = amg_active && (env_amg ? env_amg : amg_precision) == 32 ? 32 : 64;
   amgF.use_bsr = use_bsr != 0;
+  // the V-cycle on S in place of ILU(S); NSK_SCHUR_AMG=0 / 1 overrides the option (A/B runs with unchanged
+  // callers), any other value counts as unset.  Stationary aSIMPLE only: every other set-up ignores it
+  static const int env_schur_amg = [] {
+    const char *e = std::getenv("NSK_SCHUR_AMG");
+    if (e && e[0] == '0' && !e[1]) return 0;
+    if (e && e[0] == '1' && !e[1]) return 1;
+    return -1;
+  }();
+  const bool want_amgS = type == 2 && variant == 0 && (env_schur_amg >= 0 ? env_schur_amg : schur_amg) == 1;
+  schur_amg_active = false;
+  // (one knob for "operators a V-cycle multiplies by": NSK_OPT_AMG_PRECISION governs this hierarchy too)
+  amgS.value_bits = want_amgS && (env_amg ? env_amg : amg_precision) == 32 ? 32 : 64;
+  amgS.use_bsr = false;
+  amgS.one_sign_diag = true;
+  if (!want_amgS) amgS.release();
   if (amg_active) {
     amgF.clear();
     amg_pending = true;
@@ -155,7 +170,8 @@ void H::setup(int type, int variant_, double alpha_) {
     std::thread side;
     std::exception_ptr side_err;
     bool side_done_s = false;
-    if (type == 2 && (!tF_ok || tF_key != key) && (!tS_ok || tS_key != key)) {
+    // (not under NSK_OPT_SCHUR_AMG: S's factor is not analysed then, and the pattern is formed below)
+    if (type == 2 && !want_amgS && (!tF_ok || tF_key != key) && (!tS_ok || tS_key != key)) {
       side = std::thread([&] {
         try {
           (void)hipSetDevice(ctx.device);
@@ -209,15 +225,37 @@ void H::setup(int type, int variant_, double alpha_) {
                         S.col.p, S.val.p, S.n_rows, std::max(1, s_max_row));
     if (schur_sign < 0) vec_scale(s(), (int)S.nnz, sref(-1.0), S.val.p);   // opt-in deviation (nsk.h: NSK_OPT_SCHUR_SIGN)
     ++S.values_version;
-    if (!tS_ok || tS_key != key) {
-      Phase ph("analyse S factor (host)");
-      tS.analyze(&ctx, S, 0, tri_ordering, sub_offsets(1), false, xy(1), group_p);
-      tS_ok = true;
-      tS_key = key;
+    tP = nullptr;
+    if (want_amgS) {
+      // S changes with every set-up: the hierarchy is rebuilt every time, here and not on first use (the CG on S runs in
+      // every application).  A set-up the device kernels cannot finish — a row of a product over their 512 columns, a
+      // diagonal of S that is not of one sign — leaves ILU(S) in charge, said once per handle
+      Phase ph("AMG hierarchy of S (device)");
+      try {
+        amgS.setup(&ctx, S, sub_offsets(1));
+        schur_amg_active = true;
+      } catch (const Error &e) {
+        amgS.release();
+        S.amg32 = 0;
+        if (e.code > -80 || e.code < -85) throw;
+        if (!schur_amg_warned) {
+          schur_amg_warned = true;
+          fprintf(stderr, "[nsk] warning: NSK_OPT_SCHUR_AMG = 1, but the hierarchy of S cannot be built (%s): ILU(S) preconditions the inner CG on S\n",
+                  e.what());
+        }
+      }
     }
-    tS.kind = 0;
-    tS.numeric(S.val.p);
-    tP = &tS;
+    if (!schur_amg_active) {
+      if (!tS_ok || tS_key != key) {
+        Phase ph("analyse S factor (host)");
+        tS.analyze(&ctx, S, 0, tri_ordering, sub_offsets(1), false, xy(1), group_p);
+        tS_ok = true;
+        tS_key = key;
+      }
+      tS.kind = 0;
+      tS.numeric(S.val.p);
+      tP = &tS;
+    }
     // delta_p.reinit(...) in initialize(): zero
     vec_set(s(), n_p(), delta_p, 0.0);
   } else {
@@ -267,7 +305,8 @@ void H::setup(int type, int variant_, double alpha_) {
     if (!is_f32(form_of(A, 0, true))) A.inner32 = 0;
     // (F's copies may also serve the V-cycle, level 0 being F itself: Amg::setup names them in amg32 when the hierarchy is
     // built and this loop leaves them alone meanwhile; without an fp32 AMG in this set-up nothing of it remains)
-    if (!(b == NSK_BLK_F && amgF.value_bits == 32)) A.amg32 = 0;
+    // (S the same way under NSK_OPT_SCHUR_AMG, where amgS.setup above has named its copy already)
+    if (!(b == NSK_BLK_F && amgF.value_bits == 32) && !(b == NSK_BLK_S && schur_amg_active && amgS.value_bits == 32)) A.amg32 = 0;
     if (!A.inner32 && !A.amg32) { A.release_f32(); continue; }
     if (A.inner32) A.refresh_f32(s(), true);
   }
@@ -280,8 +319,10 @@ void H::setup(int type, int variant_, double alpha_) {
     if (over) {
       for (Csr *c : {&blk[NSK_BLK_F], &blk[NSK_BLK_MP], &blk[NSK_BLK_S]}) c->release_f32();
       amgF.clear();
+      amgS.clear();
+      schur_amg_active = false;
       amg_pending = false;
-      prec_type = -1;   // no preconditioner: call nsk_setup_preconditioner again (e.g. with the option at 64)
+      prec_type = -1;  // no preconditioner: call nsk_setup_preconditioner again (e.g. with the option at 64)
       static const char *names[6] = {"F (block 0,0)", "Bt", "B", "M_p (pressure mass)", "Bt ghost rows", "S (Schur approximation)"};
       throw Error(-48, std::string("NSK_OPT_INNER_MATRIX_PRECISION = 32: ") + std::to_string(over) + " value(s) of " +
                            names[b] + " are finite in fp64 but outside the range of fp32");
@@ -318,7 +359,7 @@ void H::prec_vmult(DVec &dst, const DVec &src) {
     if (amg_active) { amg_ready(); amgF.apply(r.own, d.own); }
     else tri_apply_sampled(tF, 20, r.own, d.own);
   };
-  PrecVmult P_P = [&](DVec &d, const DVec &r) { tri_apply_sampled(*tP, 21, r.own, d.own); };
+  PrecVmult P_P = [&](DVec &d, const DVec &r) { pressure_apply_sampled(r.own, d.own); };
   const SlotLease sl(ctx, 4);
   auto norm_of = [&](const double *v, int n) { ctx.norm2(n, v, sl); return ctx.read_slots(sl + 1, 1)[0]; };
 

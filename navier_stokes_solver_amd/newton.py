@@ -40,6 +40,9 @@ def report_factor_precision(ls):
         print("[nsk] NSK_AMG_PRECISION=32: velocity AMG operators stored in fp32 (deviation from the reference)")
     if ls.rank == 0 and ls.inner_matrix_free() == 1:
         print("[nsk] NSK_INNER_MATRIX_FREE_F=1: inner FGMRES multiplies by the matrix-free F of the last assembly")
+    if ls.rank == 0 and ls.schur_amg_info():
+        print("[nsk] NSK_SCHUR_AMG=1: inner CG on S preconditioned by an AMG V-cycle on S, not ILU(S) "
+              "(deviation from the reference)")
 
 
 class InletVelocity:

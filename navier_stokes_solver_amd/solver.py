@@ -39,7 +39,8 @@ OPT_INNER_MATRIX_PRECISION = 17  # 64 (default) / 32: inner solves multiply by f
 OPT_INNER_BASIS_PRECISION = 18  # 64 (default) / 32: the inner FGMRES on F keeps its Krylov basis in fp32 — labelled deviation, see include/nsk.h
 OPT_AMG_PRECISION = 20  # 64 (default) / 32: the velocity AMG's V-cycle multiplies by fp32 copies of A, P, R — labelled deviation, see include/nsk.h
 OPT_INNER_MATRIX_FREE_F = 19  # 0 (default) / 1: the inner FGMRES on F multiplies by the matrix-free F of the last nsk_assemble, see include/nsk.h
-TIMEOP_MATFREE_F = 56      # time_op(TIMEOP_MATFREE_F): the matrix-free product with F (needs a valid assembly, not the option)
+OPT_SCHUR_AMG = 21  # 0 (default) / 1: stationary aSIMPLE preconditions its inner CG on S with an AMG V-cycle on S, not ILU(S) — labelled deviation, see include/nsk.h
+TIMEOP_MATFREE_F = 56     # time_op(TIMEOP_MATFREE_F): the matrix-free product with F (needs a valid assembly, not the option)
 TIMEOP_INNER_SPMV = 50     # time_op(TIMEOP_INNER_SPMV + blk): the inner solves' SpMV of F, M_p or S
 IOPT_FUSED_MGS, IOPT_OVERLAP_HALO = 106, 107
 IOPT_TIMEOP_BETWEEN = 109  # time_op: SpMV of this block between two repetitions, outside the timed brackets (-1: back to back)
@@ -54,7 +55,7 @@ EXPORTS = [
     "nsk_set_support_points",
     "nsk_set_block_csr", "nsk_update_values", "nsk_set_option", "nsk_setup_preconditioner", "nsk_solve",
     "nsk_upload_system", "nsk_solve_resident", "nsk_download_solution", "nsk_spmv", "nsk_jacobian_vmult", "nsk_dot", "nsk_vec_op",
-    "nsk_tri_apply", "nsk_amg_info", "nsk_amg_value_bytes", "nsk_tri_get_perm", "nsk_tri_get_value_bytes", "nsk_inner_value_bytes", "nsk_inner_basis_bytes", "nsk_inner_matrix_free", "nsk_matfree_f", "nsk_inner_spmv", "nsk_precond_vmult", "nsk_block_nnz", "nsk_get_block", "nsk_get_stats",
+    "nsk_tri_apply", "nsk_amg_info", "nsk_amg_value_bytes", "nsk_schur_amg_info", "nsk_schur_amg_apply","nsk_tri_get_perm", "nsk_tri_get_value_bytes", "nsk_inner_value_bytes", "nsk_inner_basis_bytes", "nsk_inner_matrix_free", "nsk_matfree_f", "nsk_inner_spmv", "nsk_precond_vmult", "nsk_block_nnz", "nsk_get_block", "nsk_get_stats",
     "nsk_reset_stats", "nsk_get_history", "nsk_cancel", "nsk_abort_group", "nsk_assembly_set_cells", "nsk_assembly_set_simplex", "nsk_assembly_set_dirichlet", "nsk_state_set", "nsk_state_get",
     "nsk_state_save", "nsk_state_save_old", "nsk_state_update", "nsk_assemble", "nsk_scale_values", "nsk_download_rhs", "nsk_time_assemble", "nsk_time_op", "nsk_profile_begin", "nsk_profile_read", "nsk_profile_end",
     "nsk_debug_spmv_form",
@@ -146,6 +147,9 @@ def lib() -> C.CDLL:
         L.nsk_time_assemble.argtypes = [vp, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_double)]
         L.nsk_amg_info.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                    C.POINTER(C.c_double)]
+        L.nsk_schur_amg_info.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                         C.POINTER(C.c_double)]
+        L.nsk_schur_amg_apply.argtypes = [vp, f64p, f64p]
         L.nsk_tri_apply.argtypes = [vp, C.c_int, f64p, f64p]
         L.nsk_tri_get_perm.argtypes = [vp, C.c_int, i32p]
         L.nsk_tri_get_value_bytes.argtypes = [vp, C.c_int, C.POINTER(C.c_int32)]
@@ -624,6 +628,26 @@ class LinearSolver:
             self.L.nsk_amg_info(self.h, shard, l, C.byref(rows), C.byref(nnz), C.byref(lam))
             out.append((rows.value, nnz.value, lam.value))
         return out
+
+    def schur_amg_info(self, shard=0):
+        """[(rows, nnz, lambda_max)] of the hierarchy of S the current set-up preconditions its inner CG with
+        (OPT_SCHUR_AMG = 1, stationary aSIMPLE); [] when it holds none."""
+        out = []
+        rows, nnz, lam = C.c_int64(), C.c_int64(), C.c_double()
+        nl = self.L.nsk_schur_amg_info(self.h, shard, -1, None, None, None)
+        if nl < 0:
+            self._ck(nl)
+        for l in range(nl):
+            self.L.nsk_schur_amg_info(self.h, shard, l, C.byref(rows), C.byref(nnz), C.byref(lam))
+            out.append((rows.value, nnz.value, lam.value))
+        return out
+
+    def schur_amg_apply(self, b):
+        """x = one V-cycle of that hierarchy on b (owned pressure entries); raises when the set-up holds none."""
+        b = _f64(b)
+        x = np.empty(self.n_p)
+        self._ck(self.L.nsk_schur_amg_apply(self.h, b.ctypes.data, x.ctypes.data))
+        return x
 
     def stats(self) -> dict:
         st = Stats()
