@@ -36,7 +36,8 @@
  *        -73: no state); the record calls also -69 without a record list and -60 for subdivisions outside 1..4
  *   -70 single-launch triangular solve gave up waiting AND the per-colour retry failed too (see NSK_OPT_TRI_SYNC_FREE)
  *   -80..-85 AMG set-up (operator too large for 32-bit indices, rows too wide, rounds / estimates that do not end; -85:
- *        NSK_OPT_SCHUR_AMG, a level's diagonal with both signs or a zero — the set-up falls back to ILU(S), see there)
+ *        NSK_OPT_SCHUR_AMG, a level's diagonal with both signs or a zero — the set-up falls back to ILU(S), see there;
+ *        under NSK_OPT_ASIMPLE_VELOCITY_AMG these codes do not reach the caller either: the set-up falls back to ILU(F))
  *   -1 any other exception
  */
 #ifndef NSK_H
@@ -222,7 +223,7 @@ enum {
                                  NSK_OPT_SCHUR_AMG it governs the hierarchy of S too: one knob for the operators a V-cycle
                                  multiplies by (S itself, level 0 of one shard, through scalar fp32 values on its 16-bit
                                  column offsets) */
-  NSK_OPT_SCHUR_AMG = 21      /* preconditioner of the inner CG on S in the STATIONARY aSIMPLE set-up (type 2, variant 0).
+  NSK_OPT_SCHUR_AMG = 21,     /* preconditioner of the inner CG on S in the STATIONARY aSIMPLE set-up (type 2, variant 0).
                                  0 (default): ILU(0) of S, as the reference (Ifpack ILU, NSSolverStationary.hpp:325-326),
                                  as today and the same bits.  1: one V-cycle of a smoothed-aggregation hierarchy of S — the
                                  method, parameters and device set-up of the velocity AMG (nsk_amg_info), built from S at
@@ -242,6 +243,32 @@ enum {
                                  preconditioner is changed.  Takes effect at the next nsk_setup_preconditioner.  Other
                                  values: -61.  NSK_SCHUR_AMG=0 / 1 in the environment overrides the option for every handle
                                  (A/B runs; other values count as unset) */
+  NSK_OPT_ASIMPLE_VELOCITY_AMG = 22
+                              /* preconditioner of the inner FGMRES on F in the STATIONARY aSIMPLE set-up (type 2, variant
+                                 0).  0 (default): ILU(0) of F, as the reference (Ifpack ILU, NSSolverStationary.hpp:325-326),
+                                 as today and the same bits.  1: one V-cycle of the velocity hierarchy — the smoothed-
+                                 aggregation AMG of F that blockTriangular uses (nsk_amg_info reports it) — built inside
+                                 every nsk_setup_preconditioner; sub-domains as NSK_OPT_SUBDOMAINS cuts the velocity space,
+                                 ghost columns dropped.  ILU(F) is then neither analysed nor factorised and its storage is
+                                 released: the velocity slot of nsk_tri_apply applies the cycle, nsk_tri_get_perm gives the
+                                 identity, nsk_tri_get_value_bytes 0 and nsk_amg_value_bytes the hierarchy's, exactly as
+                                 under blockTriangular; profile class 20 samples the cycle.  diag(F), S, the FGMRES, its
+                                 tolerance and alpha are untouched.  With one sub-domain level 0 is F itself, read through
+                                 its 2 x 2 node blocks (NSK_OPT_BSR_VELOCITY = 1): the residual products take the blocked
+                                 kernel and the Chebyshev steps that follow them run in its epilogue — the same bits as the
+                                 scalar two-launch steps give, fewer bytes.  NSK_OPT_AMG_PRECISION, NSK_OPT_SCHUR_AMG,
+                                 NSK_OPT_INNER_MATRIX_PRECISION and NSK_OPT_INNER_MATRIX_FREE_F combine with it as with
+                                 blockTriangular.  Where the hierarchy cannot be built (-80..-85: a row of a set-up product
+                                 over 512 distinct columns and its kin) the set-up analyses and factorises ILU(F) as under
+                                 0 and ONE line `[nsk] warning: ...` per handle says so on stderr; -48 and HIP errors stay
+                                 errors.  (Only the set-up falls back: nsk_set_block_csr of F followed by a solve without a
+                                 new nsk_setup_preconditioner rebuilds the hierarchy at its first application, and these
+                                 codes then fail that solve.)  Types 0 and 1 and the unsteady variant ignore the option; NSK_OPT_VELOCITY_AMG
+                                 keeps meaning blockTriangular only.  A LABELLED DEVIATION from the reference: the inner
+                                 solve stops at 1e-1 and the outer FGMRES checks the true residual, so only the
+                                 preconditioner is changed.  Takes effect at the next nsk_setup_preconditioner.  Other
+                                 values: -61.  NSK_ASIMPLE_VELOCITY_AMG=0 / 1 in the environment overrides the option for
+                                 every handle (A/B runs; other values count as unset) */
 };
 
 typedef struct {

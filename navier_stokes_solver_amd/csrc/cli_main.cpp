@@ -201,8 +201,13 @@ struct NewtonDriver {
         nl = "";
       }
       // NSK_SCHUR_AMG=1 (read by the library): a hierarchy of S stands, so the inner CG on S is preconditioned by its V-cycle
-      if (nsk_schur_amg_info(h, 0, -1, nullptr, nullptr, nullptr) > 0)
+      if (nsk_schur_amg_info(h, 0, -1, nullptr, nullptr, nullptr) > 0) {
         std::printf("%s[nsk] NSK_SCHUR_AMG=1: inner CG on S preconditioned by an AMG V-cycle on S, not ILU(S) (deviation from the reference)\n", nl);
+        nl = "";
+      }
+      // NSK_ASIMPLE_VELOCITY_AMG=1 (read by the library): under aSIMPLE a velocity hierarchy stands only through that option
+      if (preconditioner == 2 && !NSK_UNSTEADY && nsk_amg_info(h, 0, -1, nullptr, nullptr, nullptr) > 0)
+        std::printf("%s[nsk] NSK_ASIMPLE_VELOCITY_AMG=1: inner FGMRES on F preconditioned by an AMG V-cycle on F, not ILU(F) (deviation from the reference)\n", nl);
     }
     int iters = 0;
     double res = 0.0;

@@ -689,6 +689,9 @@ void Amg::build(AmgHierarchy &H, Csr *A0, std::unique_ptr<Csr> own0) {
     }
     L->r.alloc((size_t)n);
     L->w.alloc((size_t)n);
+    // (level 0 on 2 x 2 node blocks under fused_cheby: the fused smoother steps need a second iterate)
+    if (l == 0 && fused_cheby && use_bsr && A.blk_ok && A.blk_R == 2 && A.blk_C == 2 && (blk_residual || value_bits == 32))
+      L->x2.alloc((size_t)n);
     lap(l, "diagonal");
     L->lam = estimate_lambda_device(*L);
     if (!(L->lam > 0.0) || !std::isfinite(L->lam))
@@ -822,8 +825,7 @@ void Amg::build_all(Csr &F, const std::vector<int> &shard_off) {
 void Amg::mv(Csr &A, const double *x, double *y, int mode, const double *z) {
   // (no ghost tail; 16-bit offsets only where level 0 is the caller's S, which carries them: y = A x and y = z - A x, both
   // with a kernel in either precision; the rule: amg_spmv_form, nsk_core.hpp)
-  const bool aligned16 = (((uintptr_t)x | (uintptr_t)y | (uintptr_t)z) & 15) == 0;
-  const SpmvForm f = form_of(A, mode, aligned16);
+  const SpmvForm f = form_of(A, mode, all_aligned16(x, y, z));
   if (is_f32(f)) {
     // the caller's block: values written since the conversion, or vectors off the pair alignment for the first time
     if (f == SpmvForm::stream_f32 && !(A.amg32 & 2)) { A.amg32 |= 2; A.val32_version = -1; }
@@ -851,6 +853,45 @@ void Amg::cheby(AmgLevel &L, const double *b, double *x, bool zero_init) {
   vec_cheby_step(s, L.n, rho_new * rho, 2.0 * rho_new / delta, L.dinv.p, L.r.p, L.w.p, x, 0);
 }
 
+// Level 0 on 2 x 2 node blocks under fused_cheby: whether this call's smoothers run their steps in the
+// epilogue of the residual products.  Coarse levels, shard copies (no node blocks), forms without node blocks and
+// vectors off the pair alignment keep the two-launch steps.
+bool Amg::fusable(const AmgLevel &L, const double *b, const double *x) const {
+  if (!fused_cheby || !L.x2.p || !L.has_coarse) return false;
+  return is_blk(fused_form(L, b, x));
+}
+
+// the form of a fused step on these vectors: every vector the kernel moves as pairs enters the rule's alignment argument
+SpmvForm Amg::fused_form(const AmgLevel &L, const double *b, const double *x) const {
+  return form_of(*L.A, 2, all_aligned16(b, x, L.x2.p, L.w.p, L.dinv.p));
+}
+
+void Amg::fused_step(AmgLevel &L, SpmvForm f, const double *x_in, double *x_out, const double *b, double c1, double c2) {
+  Csr &A = *L.A;
+  if (is_f32(f) && A.val32_version != A.values_version) A.refresh_f32(ctx->stream, false);   // (as Amg::mv)
+  if (A.cheby_launch(ctx->stream, f, x_in, nullptr, x_out, b, L.dinv.p, L.w.p, c1, c2) != 0)
+    throw Error(-1, "AMG: the fused Chebyshev step was refused (x_out == x_in, or a vector off the 16-byte alignment)");
+  ++form_launches[(int)f];
+  ++fused_launches;
+  ++ctx->st.spmv_calls;
+  // the product's bytes (its y is x_out, its gather x_in) + b + dinv + w read and written
+  ctx->st.spmv_bytes += (double)A.spmv_bytes() + 32.0 * A.n_rows;
+}
+
+// cheby() with every step that follows a residual fused into it: the same arithmetic in the same order (cheby_w is the
+// one update of both), so the same bits.  A fused step cannot run in place; the iterate alternates between x and L.x2 and
+// ends in x: zero guess -> x2 -> x, and x -> x2 -> x.
+void Amg::cheby_fused(AmgLevel &L, const double *b, double *x, bool zero_init) {
+  const double lmax = L.lam, lmin = lmax / kChebyAlpha;
+  const double theta = 0.5 * (lmax + lmin), delta = 0.5 * (lmax - lmin), sigma = theta / delta;
+  const double rho = 1.0 / sigma;
+  const SpmvForm f = fused_form(L, b, x);
+  if (zero_init) vec_cheby_step(ctx->stream, L.n, 0.0, 1.0 / theta, L.dinv.p, b, L.w.p, L.x2.p, 1);
+  else fused_step(L, f, x, L.x2.p, b, 0.0, 1.0 / theta);
+  const double rho_new = 1.0 / (2.0 * sigma - rho);
+  fused_step(L, f, L.x2.p, x, b, rho_new * rho, 2.0 * rho_new / delta);
+}
+
 void Amg::vcycle(AmgHierarchy &H, int l, const double *b, double *x) {
   AmgLevel &L = *H.lev[l];
   if (!L.has_coarse) {
@@ -859,16 +900,28 @@ void Amg::vcycle(AmgHierarchy &H, int l, const double *b, double *x) {
     return;
   }
   AmgLevel &C = *H.lev[l + 1];
-  cheby(L, b, x, true);
+  const bool fused = l == 0 && fusable(L, b, x);
+  if (fused) cheby_fused(L, b, x, true);
+  else cheby(L, b, x, true);
   mv(*L.A, x, L.r.p, 2, b);
   mv(L.R, L.r.p, C.b.p);
   vcycle(H, l + 1, C.b.p, C.x.p);
   mv(L.P, C.x.p, x, 1);  // x += P x_c
-  cheby(L, b, x, false);
+  if (fused) cheby_fused(L, b, x, false);
+  else cheby(L, b, x, false);
 }
 
 void Amg::apply(const double *b, double *x) {
   for (AmgHierarchy &H : shards) vcycle(H, 0, b + H.offset, x + H.offset);
+}
+
+double Amg::smoother_bytes(const AmgLevel &L, double a) const {
+  const double n8 = 8.0 * L.n;
+  // two launches per step: four residuals (+ z) and four Chebyshev updates of 5 vector streams each
+  if (!(fused_cheby && L.x2.p && is_blk(form_of(*L.A, 2, true)))) return 4 * (a + n8) + n8 * 5 * 4;
+  // fused steps: the zero-guess update, the restricted residual, and three products that also stream b, dinv
+  // and w read and written (r is never stored; the c1 = 0 step does not read w and is counted as if it did)
+  return n8 * 5 + (a + n8) + 3 * (a + 4 * n8);
 }
 
 size_t Amg::apply_bytes() const {
@@ -876,9 +929,9 @@ size_t Amg::apply_bytes() const {
   for (const AmgHierarchy &H : shards)
     for (const auto &L : H.lev) {
       // pre-smoother 1 SpMV (zero guess), residual 1, post-smoother 2; restriction, prolongation (+ 8 n for the add);
-      // four Chebyshev updates of 5 vector streams each
-      if (L->has_coarse) by += 4 * (L->A->spmv_bytes() + 8 * (size_t)L->n) + L->P.spmv_bytes() + 8 * (size_t)L->n +
-                               L->R.spmv_bytes() + (size_t)L->n * 8 * 5 * 4;
+      // four Chebyshev updates of 5 vector streams each (fewer streams where the steps are fused: smoother_bytes)
+      if (L->has_coarse) by += (size_t)smoother_bytes(*L, (double)L->A->spmv_bytes()) + L->P.spmv_bytes() + 8 * (size_t)L->n +
+                               L->R.spmv_bytes();
       else if (L->inv.p) by += (size_t)L->n * L->n * 8;
       else by += 3 * (L->A->spmv_bytes() + 8 * (size_t)L->n) + (size_t)L->n * 8 * 5 * 4;
     }
@@ -896,7 +949,7 @@ double Amg::format_bytes(int shard, int level) const {
       const double n8 = 8.0 * L.n;
       // (the forms of aligned vectors: what the cycle takes on the library's own)
       const double a = L.A->format_bytes(form_of(*L.A, 2, true)) + n8;
-      if (L.has_coarse) by += 4 * a + L.P.format_bytes(form_of(L.P, 1, true)) + n8 + L.R.format_bytes(form_of(L.R, 0, true)) + n8 * 5 * 4;
+      if (L.has_coarse) by += smoother_bytes(L, a - n8) + L.P.format_bytes(form_of(L.P, 1, true)) + n8 + L.R.format_bytes(form_of(L.R, 0, true));
       else if (L.inv.p) by += (double)L.n * L.n * 8;
       else by += 3 * a + n8 * 5 * 4;
     }

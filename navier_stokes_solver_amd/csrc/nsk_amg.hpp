@@ -42,6 +42,7 @@ struct AmgLevel {
   bool has_coarse = false;
   double lam = 1.0;
   DBuf<double> dinv, inv, x, b, r, w;
+  DBuf<double> x2;    // level 0 under Amg::fused_cheby alone: the second iterate of the fused smoother steps (x_out != x_in)
 };
 
 struct AmgHierarchy {
@@ -60,6 +61,14 @@ struct Amg {
   // The hierarchy preconditions a CG (the Schur AMG, NSK_OPT_SCHUR_AMG): the cycle must be definite, so every level's
   // diagonal has to carry one sign and no zero — Error -85 from the set-up otherwise (checked where dinv is formed)
   bool one_sign_diag = false;
+  // The velocity hierarchy stationary aSIMPLE builds under NSK_OPT_ASIMPLE_VELOCITY_AMG; both false for every
+  // other hierarchy (the velocity AMG of blockTriangular, the one of S), which keep their kernel forms and bits.
+  // blk_residual: in double, r = b - A x on a level with 2 x 2 node blocks (level 0 when it is F itself) takes
+  // spmv_blk22_residual instead of the scalar stream kernel (the rule: amg_spmv_form's last argument).
+  // fused_cheby: on such a level — double or fp32 blocks — the smoother steps that follow a residual run in that
+  // product's epilogue (nsk::spmv_blk22_cheby), alternating between x and the level's x2; NSK_IOPT_AMG_FUSED_CHEBY
+  bool blk_residual = false, fused_cheby = false;
+  long fused_launches = 0;                   // fused smoother steps of the cycles since the set-up (test hook)
   long form_launches[5] = {0, 0, 0, 0, 0};   // products of the cycles since the set-up, by SpmvForm (test hook)
   int value_bytes() const { return shards.empty() ? 0 : built_bits / 8; }   // of the hierarchy that stands
   // F: device block with host pattern; shard_off: empty = one shard
@@ -69,6 +78,7 @@ struct Amg {
     shards.clear();
     level0 = nullptr;
     for (long &c : form_launches) c = 0;
+    fused_launches = 0;
   }   // (the set-up's scratch arena stays for the next set-up)
   void release() {                   // the preconditioner is no longer in use
     clear();
@@ -92,10 +102,20 @@ struct Amg {
   size_t arena_want = 0;   // bytes the largest level took so far
   double estimate_lambda_device(AmgLevel &L);
   void cheby(AmgLevel &L, const double *b, double *x, bool zero_init);
+  // The same smoothers with every step after a residual fused into it (level 0 under fused_cheby): pre leaves the iterate
+  // in x having passed through L.x2, post takes x -> x2 -> x.  fusable: the conditions, on this call's vectors
+  bool fusable(const AmgLevel &L, const double *b, const double *x) const;
+  SpmvForm fused_form(const AmgLevel &L, const double *b, const double *x) const;
+  void cheby_fused(AmgLevel &L, const double *b, double *x, bool zero_init);
+  void fused_step(AmgLevel &L, SpmvForm f, const double *x_in, double *x_out, const double *b, double c1, double c2);
+  // what the cycle streams on a level with a coarser one besides P and R — four products with A (a bytes each, x and y
+  // included) and four smoother steps — by the launches it takes on aligned vectors
+  double smoother_bytes(const AmgLevel &L, double a) const;
   void vcycle(AmgHierarchy &H, int l, const double *b, double *x);
   void mv(Csr &A, const double *x, double *y, int mode = 0, const double *z = nullptr);
   SpmvForm form_of(const Csr &A, int mode, bool aligned16) const {
-    return amg_spmv_form(A.blk_ok && A.blk_R == 2 && A.blk_C == 2, A.stream_ok, A.amg32 != 0, use_bsr, mode, aligned16);
+    return amg_spmv_form(A.blk_ok && A.blk_R == 2 && A.blk_C == 2, A.stream_ok, A.amg32 != 0, use_bsr, mode, aligned16,
+                         blk_residual);
   }
   void to_f32(AmgLevel &L, int level);   // round the finished level's A (its own), P and R; Error -48 on overflow
   void check_overflow(Csr &M, int level, const char *which);

@@ -269,6 +269,14 @@ int nsk_set_option(nsk_handle h, int opt, double v) {
       if (v != 0.0 && v != 1.0) throw Error(-61, "NSK_OPT_SCHUR_AMG: 0 or 1");
       h->schur_amg = (int)v;
       break;
+    case NSK_OPT_ASIMPLE_VELOCITY_AMG:
+      if (v != 0.0 && v != 1.0) throw Error(-61, "NSK_OPT_ASIMPLE_VELOCITY_AMG: 0 or 1");
+      h->asimple_velocity_amg = (int)v;
+      break;
+    case NSK_IOPT_AMG_FUSED_CHEBY:
+      if (v != -1.0 && v != 0.0 && v != 1.0) throw Error(-61, "NSK_IOPT_AMG_FUSED_CHEBY: -1, 0 or 1");
+      h->amg_fused_cheby = (int)v;
+      break;
     case NSK_IOPT_TRI_X_LAYOUT:
       h->x_layout_mode = v == 0.0 ? 0 : 2;
       h->tF_ok = false;
@@ -686,6 +694,7 @@ int nsk_profile_read(nsk_handle h, int op, double *avg_ms, int *n_samples, doubl
   if (n_calls) *n_calls = S->seen;
   if (bytes) {
     if (op >= 0 && op <= NSK_BLK_S) *bytes = (double)h->blk[op].spmv_bytes();
+    else if (op == 20 && h->asimple_amg_active) *bytes = (double)h->amgF.apply_bytes();   // class 20 is the V-cycle on F then
     else if (op == 20) *bytes = (double)h->tF.apply_bytes();
     else if (op == 21 && h->schur_amg_active) *bytes = (double)h->amgS.apply_bytes();   // class 21 is the V-cycle on S then
     else if (op == 21 && h->tP) *bytes = (double)h->tP->apply_bytes();
@@ -695,6 +704,7 @@ int nsk_profile_read(nsk_handle h, int op, double *avg_ms, int *n_samples, doubl
     // (F, S, M_p with fp32 copies for the inner solves: the fp32 format — see nsk.h, NSK_OPT_INNER_MATRIX_PRECISION)
     if (op == NSK_BLK_F && h->matfree_in_effect()) *bytes_format = h->matfree_bytes();
     else if (op >= 0 && op <= NSK_BLK_S) *bytes_format = h->blk[op].format_bytes(h->form_of(h->blk[op], 0, true));
+    else if (op == 20 && h->asimple_amg_active) *bytes_format = h->amgF.format_bytes();
     else if (op == 20) *bytes_format = h->tF.format_bytes();
     else if (op == 21 && h->schur_amg_active) *bytes_format = h->amgS.format_bytes();
     else if (op == 21 && h->tP) *bytes_format = h->tP->format_bytes();

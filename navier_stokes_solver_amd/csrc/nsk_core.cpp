@@ -617,7 +617,11 @@ int Csr::spmv_launch(hipStream_t s, SpmvForm f, const double *xo, const double *
     case SpmvForm::blk_f32:   // (y = A x, or the AMG's y = z - A x)
       nsk::spmv_blk_stream(s, blk_view32(), blk_rowblk.p + c0, c1 - c0, xo, xg, y, mode == 2 ? z : nullptr);
       return 0;
-    case SpmvForm::blk: nsk::spmv_blk_stream(s, blk_view(), blk_R, blk_C, blk_rowblk.p + c0, c1 - c0, xo, xg, y); return 0;
+    case SpmvForm::blk:
+      // (mode 2: only amg_spmv_form gives it to this form, on 2 x 2 blocks — the double residual kernel)
+      if (mode == 2) nsk::spmv_blk22_residual(s, blk_view(), blk_rowblk.p + c0, c1 - c0, xo, xg, y, z);
+      else nsk::spmv_blk_stream(s, blk_view(), blk_R, blk_C, blk_rowblk.p + c0, c1 - c0, xo, xg, y);
+      return 0;
     case SpmvForm::stream_f32: {
       const int vec = nsk::spmv_stream(s, view32(), rowblk.p + c0, c1 - c0, even_rows, xo, xg, y, off16.p, cb, mode, z);
       if (vec < 0) throw Error(-1, "fp32 stream SpMV: mode 1 (y += A x) has no kernel on 16-bit column offsets");
@@ -625,6 +629,14 @@ int Csr::spmv_launch(hipStream_t s, SpmvForm f, const double *xo, const double *
     }
     default: return nsk::spmv_stream(s, view(), rowblk.p + c0, c1 - c0, even_rows, xo, xg, y, mode, z, off16.p, cb);
   }
+}
+
+int Csr::cheby_launch(hipStream_t s, SpmvForm f, const double *x_in, const double *x_ghost, double *x_out, const double *b,
+                      const double *dinv, double *w, double c1, double c2) const {
+  if (!blk_ok || blk_R != 2 || blk_C != 2 || !is_blk(f)) return -1;
+  if (f == SpmvForm::blk_f32)
+    return nsk::spmv_blk22_cheby(s, blk_view32(), blk_rowblk.p, blk_nblk, x_in, x_ghost, x_out, b, dinv, w, c1, c2);
+  return nsk::spmv_blk22_cheby(s, blk_view(), blk_rowblk.p, blk_nblk, x_in, x_ghost, x_out, b, dinv, w, c1, c2);
 }
 
 // The handle's options do not reach this product (nor the AMG levels', Amg::mv): always the stream kernel where the plan

@@ -141,7 +141,13 @@ constexpr SpmvForm spmv_form(bool blk_ok, bool stream_ok, int inner32, bool use_
 // the operator has them and the handle uses them (level 0 when it is F itself; use_bsr = NSK_OPT_BSR_VELOCITY), for
 // y = A x and y = z - A x where x, y and z are 16-byte aligned (aligned16: the kernel moves them as pairs); the scalar
 // fp32 stream form otherwise.  An operator without a stream plan keeps its double values and the CSR-vector kernel.
-constexpr SpmvForm amg_spmv_form(bool blk_ok, bool stream_ok, bool amg32, bool use_bsr, int mode, bool aligned16) {
+// blk_residual (Amg::blk_residual: the velocity hierarchy under NSK_OPT_ASIMPLE_VELOCITY_AMG; false everywhere
+// else, and then the rule is the one above): in double, y = z - A x on an operator with 2 x 2 node blocks the handle uses
+// and 16-byte aligned x, y, z takes the blocked residual kernel (SpmvForm::blk with mode 2: spmv_blk22_residual) — F as
+// level 0 read as the rest of the library reads it, 9 B per entry instead of 12.
+constexpr SpmvForm amg_spmv_form(bool blk_ok, bool stream_ok, bool amg32, bool use_bsr, int mode, bool aligned16,
+                                 bool blk_residual = false) {
+  if (!amg32 && blk_residual && blk_ok && use_bsr && aligned16 && mode == 2) return SpmvForm::blk;
   if (!amg32) return spmv_form(blk_ok, stream_ok, 0, true, false, mode, false);
   if (blk_ok && use_bsr && aligned16 && (mode == 0 || mode == 2)) return SpmvForm::blk_f32;
   if (stream_ok) return SpmvForm::stream_f32;
@@ -217,6 +223,10 @@ struct Csr {  // device CSR block with host copy of the pattern
   // what the nsk:: launcher returned (the stream kernels' VEC, the CSR-vector kernel's lanes per row; 0 for the blocked forms)
   int spmv_launch(hipStream_t s, SpmvForm f, const double *x_own, const double *x_ghost, double *y, int mode = 0,
                   const double *z = nullptr, int c0 = 0, int c1 = kToPlanEnd) const;
+  // One Chebyshev step fused into the residual product on the 2 x 2 node blocks (nsk::spmv_blk22_cheby; f = blk or
+  // blk_f32), the whole plan: 0, or -1 and nothing launched (x_out == x_in among the reasons)
+  int cheby_launch(hipStream_t s, SpmvForm f, const double *x_in, const double *x_ghost, double *x_out, const double *b,
+                   const double *dinv, double *w, double c1, double c2) const;
   // bytes the storage format form f streams holds (values, indices, descriptors) + y + x once
   double format_bytes(SpmvForm f) const {
     const double vb = is_f32(f) ? 4.0 : 8.0;

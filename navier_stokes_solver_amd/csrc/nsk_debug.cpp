@@ -700,6 +700,60 @@ int nsk_debug_schur_amg_forms(nsk_handle h, int64_t *out5) {   // nsk_internal.h
   return 0;
 }
 
+int nsk_debug_amg_spmv_form2(int blk_ok, int stream_ok, int amg32, int use_bsr, int mode, int aligned16, int blk_residual) {   // nsk_internal.h
+  return (int)amg_spmv_form(blk_ok != 0, stream_ok != 0, amg32 != 0, use_bsr != 0, mode, aligned16 != 0, blk_residual != 0);
+}
+
+int nsk_debug_amg_fused(nsk_handle h, int64_t *out1) {   // nsk_internal.h
+  *out1 = h->amg_active ? h->amgF.fused_launches : 0;
+  return 0;
+}
+
+// test hook (nsk_internal.h): one fused Chebyshev step, and the two launches it replaces, on the same device data
+int nsk_debug_cheby_fused(nsk_handle h, const nsk_dbg_spmv_mat *Am, const double *b, const double *dinv, const double *w,
+                          double c1, double c2, int fp32, int in_place, double *w_out, double *x_out, double *r_ref,
+                          double *w_ref, double *x_ref, int32_t *info4) {
+  NSK_TRY_DEV(h)
+  Ctx &c = h->ctx;
+  hipStream_t st = h->s();
+  for (int k = 0; k < 4; ++k) info4[k] = 0;
+  if (!Am || !b || !dinv || !w) throw Error(-61, "nsk_debug_cheby_fused: arguments");
+  if (Am->n_rows % 2 || Am->n_own_cols < Am->n_rows) throw Error(-61, "nsk_debug_cheby_fused: an even number of rows, no more than owned columns");
+  Csr A;
+  dbg_fill_csr(A, *Am, st);
+  A.build_blocked(2, 2, st);
+  if (!A.blk_ok) { info4[2] = 2; return 1; }
+  const SpmvForm f = fp32 ? SpmvForm::blk_f32 : SpmvForm::blk;
+  if (fp32) { A.amg32 = 1; A.refresh_f32(st, false); }
+  const size_t n = (size_t)A.n_rows;
+  DbgVec<double> xi, xg, bv, dv, wf, xo, rr, wr, xr;
+  xi.put(Am->x_own, (size_t)A.n_own_cols, kDbgFront, kDbgBack, st);
+  xg.put(Am->x_ghost, (size_t)(A.n_cols - A.n_own_cols), kDbgFront, kDbgBack, st);
+  bv.put(b, n, kDbgFront, kDbgBack, st);
+  dv.put(dinv, n, kDbgFront, kDbgBack, st);
+  wf.put(w, n, kDbgFront, kDbgBack, st);
+  wr.put(w, n, kDbgFront, kDbgBack, st);
+  xo.put(b, n, kDbgFront, kDbgBack, st);          // (overwritten: the fused launch sets every entry of x_out)
+  rr.put(b, n, kDbgFront, kDbgBack, st);
+  xr.put(Am->x_own, n, kDbgFront, kDbgBack, st);   // the two-launch step updates x in place: a copy of x_in's rows
+  if (in_place) {
+    // the refusal, and nothing else: the launcher must not touch the device
+    const int rc = A.cheby_launch(st, f, xi.p, xg.p, xi.p, bv.p, dv.p, wf.p, c1, c2);
+    if (rc == 0) throw Error(-1, "nsk_debug_cheby_fused: an in-place fused step was launched");
+    throw Error(-61, "fused Chebyshev step: x_out must not be x_in (other workgroups are still gathering it)");
+  }
+  if (A.cheby_launch(st, f, xi.p, xg.p, xo.p, bv.p, dv.p, wf.p, c1, c2) != 0) throw Error(-1, "nsk_debug_cheby_fused: the launcher refused");
+  A.spmv_launch(st, f, xi.p, xg.p, rr.p, 2, bv.p);
+  vec_cheby_step(st, (int)n, c1, c2, dv.p, rr.p, wr.p, xr.p, 0);
+  NSK_HIP(hipGetLastError());
+  info4[1] = A.blk_nblk;
+  int bad = wf.fetch(w_out, c) + xo.fetch(x_out, c) + rr.fetch(r_ref, c) + wr.fetch(w_ref, c) + xr.fetch(x_ref, c);
+  for (DbgVec<double> *v : {&xi, &xg, &bv, &dv}) bad += v->fetch(nullptr, c);
+  info4[0] = bad;
+  return 0;
+  NSK_CATCH(h)
+}
+
 int nsk_debug_pool_counts(nsk_handle h, int32_t *out6) {   // nsk_internal.h
   int k = 0;
   for (const VecPool *p : {&h->pool_u, &h->pool_p, &h->pool_b}) {

@@ -166,6 +166,29 @@ struct nsk_handle_s {
     Sampled smp(sampler, 21, s());
     amgS.apply(b, x);
   }
+  // NSK_OPT_ASIMPLE_VELOCITY_AMG: in the stationary aSIMPLE set-up one V-cycle of amgF, built inside the set-up,
+  // preconditions the inner FGMRES on F instead of ILU(F).  asimple_amg_active: the current set-up runs it — amg_active is
+  // then true as well (every reader of the velocity slot behaves as under the velocity AMG of blockTriangular) and tF is
+  // neither analysed nor factorised nor held
+  int asimple_velocity_amg = 0;
+  int amg_fused_cheby = -1;   // NSK_IOPT_AMG_FUSED_CHEBY: -1 fused smoother steps where that hierarchy allows them, 0, 1
+  bool asimple_amg_active = false, asimple_amg_warned = false;
+  void velocity_apply_sampled(const double *b, double *x) {   // profile class 20 while asimple_amg_active: the cycle on F
+    Sampled smp(sampler, 20, s());
+    amgF.apply(b, x);
+  }
+  // No ILU(F) in this set-up: its storage goes, what the handle's options gave it stays
+  void drop_velocity_factor() {
+    TriSolve fresh;
+    fresh.tiny_bytes = tF.tiny_bytes;
+    fresh.host_analysis = tF.host_analysis;
+    fresh.x_layout = tF.x_layout;
+    fresh.want_f32 = tF.want_f32;
+    tF = std::move(fresh);
+    tF_ok = false;
+    tF_key = -1;
+    push_tri_options();
+  }
   int schur_sign = 1;       // NSK_OPT_SCHUR_SIGN: +1 the reference's S = B D^-1 Bt, -1 the negated (SIMPLE's) one
   int blas1_pairs = -1;     // NSK_OPT_BLAS1_PAIRS: -1 by variant (stationary on, unsteady off), 0, 1
   int factor_precision = 64;   // NSK_OPT_FACTOR_PRECISION: 64, or 32 (single-precision off-diagonal values of the split halves)
@@ -195,6 +218,9 @@ struct nsk_handle_s {
   // The hierarchy is built on first use: PreconditionAMG::initialize is called before every solve (NSSolverStationary.hpp:231),
   // also before the many solves of a Newton run that stop at step 0 without ever applying the preconditioner; building it
   // when the first vmult arrives (or before the block's values change) gives the same results without those set-ups.
+  // Under NSK_OPT_ASIMPLE_VELOCITY_AMG the set-up builds the hierarchy itself and nothing is pending after it; only
+  // nsk_set_block_csr(F) without a new set-up comes through here, and then WITHOUT the set-up's fallback to ILU(F) (whose
+  // storage is gone): errors -80..-85 fail that solve
   bool amg_pending = false;
   void amg_ready() {
     if (!amg_pending) return;

@@ -38,6 +38,11 @@ enum {
                                 // nsk_setup_preconditioner, solve — the application the first solve left over then runs
                                 // on the new values, where the reference order ran it on the old ones (either way a
                                 // stale preconditioner; nsk_setup_preconditioner between the solves drops it)
+  NSK_IOPT_AMG_FUSED_CHEBY = 113, // -1 (default) / 1: the velocity hierarchy of NSK_OPT_ASIMPLE_VELOCITY_AMG runs the smoother
+                                // steps of level 0 in the epilogue of the residual products on F's 2 x 2 node blocks
+                                // (Amg::fused_cheby) wherever that level allows it; 0: two launches per step
+                                // (A/B runs, tests).  Same bits.  No other hierarchy reads it.  NSK_AMG_FUSED_CHEBY=0 / 1
+                                // in the environment overrides it for every handle.  Takes effect at the next set-up
   NSK_IOPT_FUSED_MGS = 106      // 1 (default): the modified Gram-Schmidt chain of an Arnoldi step in ONE launch when the
                                 // vector fits the registers of the co-resident grid (single rank); 0: one launch per link
 };
@@ -313,6 +318,24 @@ int64_t nsk_debug_amg_level(struct nsk_handle_s *h, int shard, int level, int wh
 int nsk_debug_amg_forms(struct nsk_handle_s *h, int64_t *out5);
 /* The same for the hierarchy of S (NSK_OPT_SCHUR_AMG); all 0 while the set-up preconditions S with ILU(S). */
 int nsk_debug_schur_amg_forms(struct nsk_handle_s *h, int64_t *out5);
+/* nsk_debug_amg_spmv_form with the rule's last argument: blk_residual = 0 gives nsk_debug_amg_spmv_form's value
+ * for every combination of the others; 1 gives 3 (blocked) exactly where amg32 = 0, mode = 2, blk_ok, use_bsr and aligned16
+ * all hold, and that value everywhere else. */
+int nsk_debug_amg_spmv_form2(int blk_ok, int stream_ok, int amg32, int use_bsr, int mode, int aligned16, int blk_residual);
+/* Fused smoother steps the V-cycles of the velocity hierarchy have launched since it was built; 0 without one. */
+int nsk_debug_amg_fused(struct nsk_handle_s *h, int64_t *out1);
+/* ONE fused Chebyshev step alone (nsk::spmv_blk22_cheby) on the caller's CSR matrix A (as nsk_debug_spmv takes
+ * it: x_own is x_in, x_ghost the ghost tail; n_own_cols >= n_rows; built into 2 x 2 node blocks as nsk_set_block_csr
+ * builds F) and b, dinv, w of n_rows doubles, and the two launches it replaces on the same device data: r_ref = b - A x_in
+ * (spmv_blk22_residual, or the fp32 blocked form), then vec_cheby_step(c1, c2, dinv, r_ref, w, x) on copies of w and of
+ * x_in's first n_rows entries.  fp32 != 0: both on the fp32 copy of the blocks.  Out (n_rows doubles each, may be null):
+ * w_out, x_out of the fused launch; r_ref, w_ref, x_ref of the two.  Every device vector sits between guard words;
+ * info4 = {guard words that changed, runs launched, refusal, 0}.  in_place != 0 asks for x_out == x_in: the launcher's
+ * refusal comes back as -61 and nothing is launched.  Returns 0; 1 when nothing was launched because the pattern has no
+ * 2 x 2 node structure or a block row is above the run cap (info4[2] = 2, as nsk_debug_spmv); a negative error code. */
+int nsk_debug_cheby_fused(struct nsk_handle_s *h, const struct nsk_dbg_spmv_mat *A, const double *b, const double *dinv,
+                          const double *w, double c1, double c2, int fp32, int in_place, double *w_out, double *x_out,
+                          double *r_ref, double *w_ref, double *x_ref, int32_t *info4);
 /* Work vectors of the handle's three pools: out6 = {allocated, free} of the velocity, the pressure and the block pool. */
 int nsk_debug_pool_counts(struct nsk_handle_s *h, int32_t *out6);
 /* Read-only view of what the last nsk_assemble left on a Q3/Q2 handle (tests/test_gpu_asm_kernels.py): copies

@@ -84,6 +84,12 @@ struct BlkViewT {
 using BlkView = BlkViewT<double>;
 using BlkView32 = BlkViewT<float>;
 constexpr int kBlkMax = 1024;  // blocks per workgroup (both matrices together in the fused kernel)
+// Every pointer 16-byte aligned (null counts as aligned): what the kernels that move vectors as pairs ask of them.  The one
+// statement of that rule for the AMG's products (Amg::mv, Amg::fusable) and for the launcher of the fused Chebyshev step
+template <class... P>
+inline bool all_aligned16(const P *...p) {
+  return ((... | (uintptr_t)p) & 15) == 0;
+}
 // y = A x on an R x C blocked matrix (R, C in {1,2}); rowblk = runs of block rows.
 // epi_d != null (R x C = 2 x 1 only): y = ((y .* epi_d) - A x) .* epi_dinv instead (aSIMPLE's velocity correction)
 void spmv_blk_stream(hipStream_t s, const BlkView &A, int R, int C, const int *rowblk, int nblk, const double *x_own,
@@ -92,10 +98,21 @@ void spmv_blk_stream(hipStream_t s, const BlkView &A, int R, int C, const int *r
 // 16-byte aligned: one pair per node row, one rounding per component): same bits as the double launch on the rounded values
 void spmv_blk_stream(hipStream_t s, const BlkView32 &A, const int *rowblk, int nblk, const double *x_own,
                      const double *x_ghost, double *y, const double *z = nullptr);
-// y = z - A x on double 2x2 blocks: the kernel above with V = double.  For the test hook nsk_debug_spmv alone — no product
-// of the library launches it (the fp64 V-cycle keeps the scalar stream form and its bits)
+// y = z - A x on double 2x2 blocks: the kernel above with V = double.  Launched by the test hook nsk_debug_spmv and by the
+// level-0 residuals of the velocity hierarchy under NSK_OPT_ASIMPLE_VELOCITY_AMG (Amg::blk_residual) — every
+// other fp64 V-cycle keeps the scalar stream form and its bits
 void spmv_blk22_residual(hipStream_t s, const BlkView &A, const int *rowblk, int nblk, const double *x_own,
                          const double *x_ghost, double *y, const double *z);
+// One Chebyshev smoother step in the epilogue of that residual product (EPI = 3), A with at least as many owned
+// columns as rows: with r = b - A x_in kept in registers,  w = (c1 != 0 ? c1 w : 0) + c2 dinv .* r ;  x_out = x_in + w  — the bits of
+// spmv_blk22_residual followed by vec_cheby_step (one shared update, cheby_w), r never stored, w not read when c1 == 0.
+// x_out must be a buffer of its own: other workgroups are still gathering x_in while this one stores.  Returns 0, or -1
+// with NOTHING launched when x_out is x_in, b, dinv or w, when a vector is not 16-byte aligned, or when A has fewer owned
+// block columns than block rows.
+int spmv_blk22_cheby(hipStream_t s, const BlkView &A, const int *rowblk, int nblk, const double *x_in, const double *x_ghost, double *x_out,
+                     const double *b, const double *dinv, double *w, double c1, double c2);
+int spmv_blk22_cheby(hipStream_t s, const BlkView32 &A, const int *rowblk, int nblk, const double *x_in, const double *x_ghost, double *x_out,
+                     const double *b, const double *dinv, double *w, double c1, double c2);
 // y = A xa + B xb with A 2x2-blocked and B 2x1-blocked over the same block rows (velocity block row of J)
 void spmv_blk_fused22_21(hipStream_t s, const BlkView &A, const double *xa_own, const double *xa_ghost,
                          const BlkView &B, const double *xb_own, const double *xb_ghost, const int *rowblk, int nblk,

@@ -346,11 +346,30 @@ __device__ __forceinline__ void blk_products(const BlkViewT<V> &A, int k0, int k
 // over the vector): y = ((y .* d) - A x) .* dinv, with the products rounded one by one like the separate vector calls.
 // EPI = 2 (2 x 2 only; the velocity AMG's residual products on F's node blocks, NSK_OPT_AMG_PRECISION = 32): y = d - A x,
 // d read as one pair per node row, the subtraction rounded once per component whatever V is.
+// EPI = 3 (2 x 2 only, no fewer owned columns than rows; the velocity hierarchy under NSK_OPT_ASIMPLE_VELOCITY_AMG):
+// one Chebyshev smoother step on the residual r = d - A x the owning lane holds — w = cheby_w(c1, c2, dinv, r, w),
+// y = x(row) + w — the bits of EPI = 2 followed by vec_cheby_step.  y is NOT x: other workgroups still gather x (the
+// launcher refuses an in-place call).  Its three extra operands travel in BlkEpi<3>; every other EPI takes an empty one.
+template <int EPI>
+struct BlkEpi {};
+template <>
+struct BlkEpi<3> {
+  double *w;
+  double c1, c2;
+};
+// The Chebyshev update, shared by vec_cheby_step and the EPI = 3 epilogue: (c1 != 0 ? c1 w : 0) + c2 dinv r with the
+// contraction the compiler chose for vec_cheby_step spelled out (two rounded products, one fma), so that both places
+// give the same bits whatever surrounds them.  *w is not read when c1 == 0 (it may hold anything then, NaN included)
+__device__ __forceinline__ double cheby_w(double c1, double c2, double dinv, double r, const double *w) {
+  const double keep = c1 != 0.0 ? __dmul_rn(c1, *w) : 0.0;
+  return __fma_rn(__dmul_rn(c2, dinv), r, keep);
+}
+
 template <class V, int R, int C, int EPI>
 __global__ __launch_bounds__(BLK) void spmv_blk_kernel(BlkViewT<V> A, const int *__restrict__ rowblk,
                                                        const double *__restrict__ xo, const double *__restrict__ xg,
                                                        double *__restrict__ y, const double *__restrict__ d,
-                                                       const double *__restrict__ dinv) {
+                                                       const double *__restrict__ dinv, BlkEpi<EPI> epi) {
   __shared__ double p0[kBlkMax];
   __shared__ double p1[R == 2 ? kBlkMax : 1];
   const int r0 = rowblk[blockIdx.x], r1 = rowblk[blockIdx.x + 1];
@@ -377,6 +396,17 @@ __global__ __launch_bounds__(BLK) void spmv_blk_kernel(BlkViewT<V> A, const int 
       const double2 zz = *reinterpret_cast<const double2 *>(d + 2 * (size_t)r);
       s0 = __dsub_rn(zz.x, s0);
       s1 = __dsub_rn(zz.y, s1);
+    }
+    if constexpr (EPI == 3 && R == 2) {
+      const double2 zz = *reinterpret_cast<const double2 *>(d + 2 * (size_t)r);
+      const double2 di = *reinterpret_cast<const double2 *>(dinv + 2 * (size_t)r);
+      const double2 xi = *reinterpret_cast<const double2 *>(xo + 2 * (size_t)r);
+      double *wp = epi.w + 2 * (size_t)r;
+      const double w0 = cheby_w(epi.c1, epi.c2, di.x, __dsub_rn(zz.x, s0), wp);
+      const double w1 = cheby_w(epi.c1, epi.c2, di.y, __dsub_rn(zz.y, s1), wp + 1);
+      *reinterpret_cast<double2 *>(wp) = make_double2(w0, w1);
+      s0 = __dadd_rn(xi.x, w0);
+      s1 = __dadd_rn(xi.y, w1);
     }
     if (R == 2) *reinterpret_cast<double2 *>(y + 2 * (size_t)r) = make_double2(s0, s1);
     else y[r] = s0;
@@ -1767,10 +1797,10 @@ void spmv_blk_stream(hipStream_t s, const BlkView &A, int R, int C, const int *r
                      const double *xg, double *y, const double *epi_d, const double *epi_dinv) {
   if (nblk <= 0) return;
   if (epi_d) {   // only built for the (2 x 1) block shape of the (0,1) block
-    hipLaunchKernelGGL((spmv_blk_kernel<double, 2, 1, 1>), dim3(nblk), dim3(BLK), 0, s, A, rowblk, xo, xg, y, epi_d, epi_dinv);
+    hipLaunchKernelGGL((spmv_blk_kernel<double, 2, 1, 1>), dim3(nblk), dim3(BLK), 0, s, A, rowblk, xo, xg, y, epi_d, epi_dinv, BlkEpi<1>{});
     return;
   }
-#define NSK_BK(RR, CC) hipLaunchKernelGGL((spmv_blk_kernel<double, RR, CC, 0>), dim3(nblk), dim3(BLK), 0, s, A, rowblk, xo, xg, y, nullptr, nullptr)
+#define NSK_BK(RR, CC) hipLaunchKernelGGL((spmv_blk_kernel<double, RR, CC, 0>), dim3(nblk), dim3(BLK), 0, s, A, rowblk, xo, xg, y, nullptr, nullptr, BlkEpi<0>{})
   if (R == 2 && C == 2) NSK_BK(2, 2);
   else if (R == 2 && C == 1) NSK_BK(2, 1);
   else if (R == 1 && C == 2) NSK_BK(1, 2);
@@ -1781,14 +1811,35 @@ void spmv_blk_stream(hipStream_t s, const BlkView &A, int R, int C, const int *r
 void spmv_blk_stream(hipStream_t s, const BlkView32 &A, const int *rowblk, int nblk, const double *xo, const double *xg,
                      double *y, const double *z) {
   if (nblk <= 0) return;
-  if (z) hipLaunchKernelGGL((spmv_blk_kernel<float, 2, 2, 2>), dim3(nblk), dim3(BLK), 0, s, A, rowblk, xo, xg, y, z, nullptr);
-  else hipLaunchKernelGGL((spmv_blk_kernel<float, 2, 2, 0>), dim3(nblk), dim3(BLK), 0, s, A, rowblk, xo, xg, y, nullptr, nullptr);
+  if (z) hipLaunchKernelGGL((spmv_blk_kernel<float, 2, 2, 2>), dim3(nblk), dim3(BLK), 0, s, A, rowblk, xo, xg, y, z, nullptr, BlkEpi<2>{});
+  else hipLaunchKernelGGL((spmv_blk_kernel<float, 2, 2, 0>), dim3(nblk), dim3(BLK), 0, s, A, rowblk, xo, xg, y, nullptr, nullptr, BlkEpi<0>{});
 }
 
 void spmv_blk22_residual(hipStream_t s, const BlkView &A, const int *rowblk, int nblk, const double *xo, const double *xg,
                          double *y, const double *z) {
   if (nblk > 0)
-    hipLaunchKernelGGL((spmv_blk_kernel<double, 2, 2, 2>), dim3(nblk), dim3(BLK), 0, s, A, rowblk, xo, xg, y, z, nullptr);
+    hipLaunchKernelGGL((spmv_blk_kernel<double, 2, 2, 2>), dim3(nblk), dim3(BLK), 0, s, A, rowblk, xo, xg, y, z, nullptr, BlkEpi<2>{});
+}
+
+template <class V>
+static int spmv_blk22_cheby_t(hipStream_t s, const BlkViewT<V> &A, const int *rowblk, int nblk, const double *x_in, const double *x_ghost,
+                              double *x_out, const double *b, const double *dinv, double *w, double c1, double c2) {
+  // in place is a race (other workgroups gather x_in), and x_out over an operand the owning lanes still read is none better
+  if (x_out == x_in || x_out == b || x_out == dinv || x_out == w || !x_in || !x_out || !b || !dinv || !w) return -1;
+  if (!all_aligned16(x_in, x_out, b, dinv, w)) return -1;
+  if (A.n_own_bcols < A.n_brows) return -1;   // x_in(row) is read by the row's own index
+  if (nblk > 0)
+    hipLaunchKernelGGL((spmv_blk_kernel<V, 2, 2, 3>), dim3(nblk), dim3(BLK), 0, s, A, rowblk, x_in, x_ghost, x_out, b, dinv,
+                       BlkEpi<3>{w, c1, c2});
+  return 0;
+}
+int spmv_blk22_cheby(hipStream_t s, const BlkView &A, const int *rowblk, int nblk, const double *x_in, const double *x_ghost, double *x_out,
+                     const double *b, const double *dinv, double *w, double c1, double c2) {
+  return spmv_blk22_cheby_t(s, A, rowblk, nblk, x_in, x_ghost, x_out, b, dinv, w, c1, c2);
+}
+int spmv_blk22_cheby(hipStream_t s, const BlkView32 &A, const int *rowblk, int nblk, const double *x_in, const double *x_ghost, double *x_out,
+                     const double *b, const double *dinv, double *w, double c1, double c2) {
+  return spmv_blk22_cheby_t(s, A, rowblk, nblk, x_in, x_ghost, x_out, b, dinv, w, c1, c2);
 }
 
 void spmv_blk_fused22_21(hipStream_t s, const BlkView &A, const double *xao, const double *xag, const BlkView &B,
@@ -1862,7 +1913,7 @@ void vec_recip(hipStream_t s, int n, const double *x, double *y) {
 void vec_cheby_step(hipStream_t s, int n, double c1, double c2, const double *dinv, const double *r, double *w,
                     double *x, int set_x) {
   NSK_EW(n, [=] __device__(int i) {
-    const double wi = (c1 != 0.0 ? c1 * w[i] : 0.0) + c2 * dinv[i] * r[i];
+    const double wi = cheby_w(c1, c2, dinv[i], r[i], w + i);
     w[i] = wi;
     x[i] = set_x ? wi : x[i] + wi;
   });

@@ -142,8 +142,50 @@ void H::setup(int type, int variant_, double alpha_) {
     const int v = e ? std::atoi(e) : 0;
     return v == 32 || v == 64 ? v : 0;
   }();
-  amgF.value_bits = amg_active && (env_amg ? env_amg : amg_precision) == 32 ? 32 : 64;
+  // the V-cycle on F in place of ILU(F) in stationary aSIMPLE; NSK_ASIMPLE_VELOCITY_AMG=0 / 1 overrides the
+  // option (A/B runs with unchanged callers), any other value counts as unset.  Every other set-up ignores both
+  static const int env_asimple_amg = [] {
+    const char *e = std::getenv("NSK_ASIMPLE_VELOCITY_AMG");
+    if (e && e[0] == '0' && !e[1]) return 0;
+    if (e && e[0] == '1' && !e[1]) return 1;
+    return -1;
+  }();
+  // (NSK_AMG_FUSED_CHEBY=0 / 1: the same for NSK_IOPT_AMG_FUSED_CHEBY, so that the benchmark can run both)
+  static const int env_fused = [] {
+    const char *e = std::getenv("NSK_AMG_FUSED_CHEBY");
+    if (e && e[0] == '0' && !e[1]) return 0;
+    if (e && e[0] == '1' && !e[1]) return 1;
+    return -1;
+  }();
+  const bool want_amgF = type == 2 && variant == 0 && (env_asimple_amg >= 0 ? env_asimple_amg : asimple_velocity_amg) == 1;
+  asimple_amg_active = false;
+  amgF.value_bits = (amg_active || want_amgF) && (env_amg ? env_amg : amg_precision) == 32 ? 32 : 64;
   amgF.use_bsr = use_bsr != 0;
+  // level 0 on F's node blocks, and the smoother steps in those products' epilogues: this hierarchy alone
+  amgF.blk_residual = want_amgF;
+  amgF.fused_cheby = want_amgF && (env_fused >= 0 ? env_fused : amg_fused_cheby) != 0;
+  if (want_amgF) {
+    // Built here and not on first use: it can fail, and ILU(F) must then still be possible.  A set-up the device kernels
+    // cannot finish (-80..-85: a row of a product over their 512 columns and its kin) leaves ILU(F) in charge, said once
+    // per handle; -48 and HIP errors are errors
+    Phase ph("AMG hierarchy of F (device)");
+    try {
+      amgF.setup(&ctx, F, sub_offsets(0));
+      amg_active = asimple_amg_active = true;
+    } catch (const Error &e) {
+      amgF.release();
+      F.amg32 = 0;
+      amgF.blk_residual = amgF.fused_cheby = false;
+      amgF.value_bits = 64;
+      if (e.code > -80 || e.code < -85) { prec_type = -1; throw; }
+      if (!asimple_amg_warned) {
+        asimple_amg_warned = true;
+        fprintf(stderr, "[nsk] warning: NSK_OPT_ASIMPLE_VELOCITY_AMG = 1, but the hierarchy of F cannot be built (%s): ILU(F) preconditions the inner FGMRES on F\n",
+                e.what());
+      }
+    }
+    if (asimple_amg_active) drop_velocity_factor();
+  }
   // the V-cycle on S in place of ILU(S); NSK_SCHUR_AMG=0 / 1 overrides the option (A/B runs with unchanged
   // callers), any other value counts as unset.  Stationary aSIMPLE only: every other set-up ignores it
   static const int env_schur_amg = [] {
@@ -159,7 +201,10 @@ void H::setup(int type, int variant_, double alpha_) {
   amgS.use_bsr = false;
   amgS.one_sign_diag = true;
   if (!want_amgS) amgS.release();
-  if (amg_active) {
+  if (asimple_amg_active) {
+    // (the hierarchy stands; no factor of F.  S's pattern and factor, where ILU(S) is wanted, are formed below on this
+    // thread: the side thread exists to overlap F's analysis, of which there is none)
+  } else if (amg_active) {
     amgF.clear();
     amg_pending = true;
   } else {
@@ -321,6 +366,7 @@ void H::setup(int type, int variant_, double alpha_) {
       amgF.clear();
       amgS.clear();
       schur_amg_active = false;
+      if (asimple_amg_active) amg_active = asimple_amg_active = false;   // (the hierarchy of DESIGN 5v: cleared with the rest)
       amg_pending = false;
       prec_type = -1;  // no preconditioner: call nsk_setup_preconditioner again (e.g. with the option at 64)
       static const char *names[6] = {"F (block 0,0)", "Bt", "B", "M_p (pressure mass)", "Bt ghost rows", "S (Schur approximation)"};
@@ -356,7 +402,8 @@ void H::prec_vmult(DVec &dst, const DVec &src) {
   const int nu = n_u(), np = n_p();
   MatVec A_F = [&](const DVec &x, double *y) { spmv_halo(F, 0, x, y); };
   PrecVmult P_F = [&](DVec &d, const DVec &r) {
-    if (amg_active) { amg_ready(); amgF.apply(r.own, d.own); }
+    if (asimple_amg_active) { amg_ready(); velocity_apply_sampled(r.own, d.own); }   // (class 20 is the cycle on F then)
+    else if (amg_active) { amg_ready(); amgF.apply(r.own, d.own); }
     else tri_apply_sampled(tF, 20, r.own, d.own);
   };
   PrecVmult P_P = [&](DVec &d, const DVec &r) { pressure_apply_sampled(r.own, d.own); };

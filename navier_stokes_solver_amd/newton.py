@@ -43,6 +43,9 @@ def report_factor_precision(ls):
     if ls.rank == 0 and ls.schur_amg_info():
         print("[nsk] NSK_SCHUR_AMG=1: inner CG on S preconditioned by an AMG V-cycle on S, not ILU(S) "
               "(deviation from the reference)")
+    if ls.asimple_velocity_amg() and ls.rank == 0:
+        print("[nsk] NSK_ASIMPLE_VELOCITY_AMG=1: inner FGMRES on F preconditioned by an AMG V-cycle on F, not ILU(F) "
+              "(deviation from the reference)")
 
 
 class InletVelocity:

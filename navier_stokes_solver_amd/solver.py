@@ -40,6 +40,8 @@ OPT_INNER_BASIS_PRECISION = 18  # 64 (default) / 32: the inner FGMRES on F keeps
 OPT_AMG_PRECISION = 20  # 64 (default) / 32: the velocity AMG's V-cycle multiplies by fp32 copies of A, P, R — labelled deviation, see include/nsk.h
 OPT_INNER_MATRIX_FREE_F = 19  # 0 (default) / 1: the inner FGMRES on F multiplies by the matrix-free F of the last nsk_assemble, see include/nsk.h
 OPT_SCHUR_AMG = 21  # 0 (default) / 1: stationary aSIMPLE preconditions its inner CG on S with an AMG V-cycle on S, not ILU(S) — labelled deviation, see include/nsk.h
+OPT_ASIMPLE_VELOCITY_AMG = 22  # 0 (default) / 1: stationary aSIMPLE preconditions its inner FGMRES on F with an AMG V-cycle on F, not ILU(F) — labelled deviation, see include/nsk.h
+IOPT_AMG_FUSED_CHEBY = 113  # -1 (default) / 1: that hierarchy's level-0 smoother steps run in the residual products' epilogues (same bits); 0: two launches
 TIMEOP_MATFREE_F = 56     # time_op(TIMEOP_MATFREE_F): the matrix-free product with F (needs a valid assembly, not the option)
 TIMEOP_INNER_SPMV = 50     # time_op(TIMEOP_INNER_SPMV + blk): the inner solves' SpMV of F, M_p or S
 IOPT_FUSED_MGS, IOPT_OVERLAP_HALO = 106, 107
@@ -330,7 +332,14 @@ class LinearSolver:
 
     # ---- the path -------------------------------------------------------------------------
     def setup_preconditioner(self, type, variant=STATIONARY, alpha=0.5):
+        self._prec = None
         self._ck(self.L.nsk_setup_preconditioner(self.h, type, variant, alpha))
+        self._prec = (type, variant)
+
+    def asimple_velocity_amg(self):
+        """True when the current set-up is stationary aSIMPLE and preconditions its inner FGMRES on F with the V-cycle of
+        the velocity hierarchy (OPT_ASIMPLE_VELOCITY_AMG = 1; amg_levels() reports it), not ILU(F)."""
+        return getattr(self, "_prec", None) == (ASIMPLE, STATIONARY) and bool(self.amg_levels())
 
     def solve(self, solver, tol, max_iter, rhs_u, rhs_p, x_u, x_p):
         """Returns (x_u, x_p, iters, final_res, status); status as in ``nsk.h``."""
