@@ -432,24 +432,34 @@ int nsk_debug_spmv_form(int blk_ok, int stream_ok, int inner32, int use_stream, 
  *   inhomogeneous values (the inlet profile of the very first iteration).
  * nsk_state_*: `solution` on the device.  set/get move owned entries; save = `evaluation_point = solution`;
  *   update(alpha) = `solution = evaluation_point + alpha * delta_owned` with delta the resident result of the
- *   last solve (:718-721).  Ghost entries are refreshed by a halo exchange.
+ *   last solve (:718-721).  Ghost entries are refreshed by a halo exchange.  The result stays available to every
+ *   update of one line search, whatever nsk_assemble writes between them (P2/P1 handles copy it before the
+ *   assembly writes the next initial guess over it).
  * nsk_assemble: fills block (0,0) (+ Dirichlet clearing), the resident right-hand side and the Dirichlet entries
  *   of the resident initial guess, and returns residual_vector.l2_norm() (:701).  Collective.
  *   stokes != 0 is the reference's Stokes phase (`computing_stokes`, :383-406, :455-458): no convective part,
  *   no residual (right-hand side = outlet term + Dirichlet values).
+ *   The Dirichlet diagonal |entry (0,0)| is written by the rank owning global DoF 0 and summed over the ranks (one
+ *   word) before the Dirichlet rows and the right-hand side read it — Q3/Q2 and P2/P1 cells alike.
  *   Call nsk_setup_preconditioner afterwards, as solve_system() builds its preconditioner from the new matrix. */
 int nsk_assembly_set_cells(nsk_handle h, int64_t n_cells, const int32_t *cell_u_nodes, const int32_t *cell_p_dofs,
                            const uint8_t *cell_flags, const double *tables944, int32_t cell_of_dof0);
 int nsk_assembly_set_dirichlet(nsk_handle h, const uint8_t *dirichlet_u, const double *bc_u /* or NULL */);
 /* The same for general (non-congruent) P2/P1 triangles — the reference's `-M` path (FE_SimplexP, QGaussSimplex(3),
- * NSSolverStationary.cpp:144-206), one rank.  Instead of nsk_assembly_set_cells.  Per cell: 6 velocity NODE ids
+ * NSSolverStationary.cpp:144-206).  Instead of nsk_assembly_set_cells.  Per cell: 6 velocity NODE ids
  * (vertices, then the midpoints of edges (0,1), (1,2), (2,0)), 3 pressure DoF ids, the gradients of the three
  * barycentric coordinates and the area (what MappingFE / FEValues::reinit give per cell).  The transposed connectivity
  * the gather kernels need is computed by the caller's side once per mesh (navier_stokes_solver_amd/simplex.py:
  * device_handoff): per 2x2 node block of block (0,0) the cells holding both nodes (cell * 36 + local row node * 6 +
  * local column node) and the positions of the block's first entry in the node's two scalar CSR rows; per velocity node
  * and per pressure DoF the cells touching it (cell * 6 + local node, cell * 3 + local vertex); outlet_w[2 node + c] =
- * integral of phi_node n_c over the boundary-id-8 edges.  pos00: position of entry (0,0) of block (0,0). */
+ * integral of phi_node n_c over the boundary-id-8 edges.  pos00: position of entry (0,0) of block (0,0).
+ * Several ranks (simplex.py: device_rank_handoff): the cells are those touching an owned node or DoF plus the
+ * rank's own, in ascending global order; ids are local — owned first, then the ghosts in the order of the partition's
+ * ghost lists (velocity ghosts as whole nodes: an odd ghost count is -65), valid below n_u/2 + ng_u/2 and n_p + ng_p;
+ * the block, node and vertex lists cover the owned rows, nodes and DoFs; pos00 is the position of the diagonal entry of
+ * global DoF 0 on the rank that owns it and -1 on the others (-64 on one rank).  Every id a kernel dereferences is
+ * checked here on the host (-64) before anything is launched. */
 int nsk_assembly_set_simplex(nsk_handle h, int64_t n_cells, const int32_t *cell_u_nodes, const int32_t *cell_p_dofs,
                              const double *grad_lambda, const double *area, int64_t n_blocks, const int32_t *blk_ptr,
                              const int32_t *blk_ent, const int64_t *blk_pos0, const int64_t *blk_pos1,
@@ -477,7 +487,8 @@ int nsk_assemble(nsk_handle h, int stokes, double nu, double inv_dt, double p_ou
  *   dphi/dx[16], dphi/dy[16] and psi[9], then JxW[4][4] at 656.  n_faces may be 0 (a rank whose cells do not touch the
  *   obstacle).  nsk_forces_set_edges: the same for P2/P1 handles, after nsk_assembly_set_simplex — per id-10 edge its
  *   cell, the cell's local edge (0: vertices 0-1, 1: 1-2, 2: 2-0) and (n_x, n_y, length) with the fluid cell's outward
- *   normal; two Gauss points per edge.  Cell indices are checked on the host at hand-off (-72).
+ *   normal; two Gauss points per edge.  Cell indices are checked on the host at hand-off (-72).  On several ranks:
+ *   the id-10 edges of the rank's OWN cells, indices into that rank's cell list; n_edges may be 0.
  *   nsk_assembly_set_cells / nsk_assembly_set_simplex void the list.
  * nsk_forces: drag_lift[0..1] = -sum over those faces of (nu (grad u + grad u^T) - p I) n JxW from the resident state
  *   (owned entries and the ghost tail, as nsk_assemble reads them), summed over the ranks (Utilities::MPI::sum,
@@ -504,9 +515,16 @@ int nsk_state_get_patches(nsk_handle h, int64_t n, const int32_t *cells, double 
  *   vel3 = (u_x, u_y, +0.0) per point, prs one value per point.  n_points must be n_cells (s+1)^2 (-60).  s = 1 copies
  *   the bits of the state, owned or ghost, as nsk_state_get_patches does; s > 1: value = sum_n W[pt][n] state[n], n
  *   increasing, one accumulator, no atomics: two calls give the same bits.  P2/P1 handles (one rank) need no list: the
- *   record is the mesh's vertices, the first n_p velocity nodes and the pressure DoFs; n_points = n_p. */
+ *   record is the mesh's vertices, the first n_p velocity nodes and the pressure DoFs; n_points = n_p.
+ * nsk_record_set_points (P2/P1 handles, after nsk_assembly_set_simplex; -71 on Q3/Q2 handles): the record's points as
+ *   local ids — per point the velocity node and the pressure DoF of a vertex, owned or ghost (one rank's piece: the
+ *   vertices of its own cells).  Ids are checked on the host (-72); n_points may be 0.  nsk_assembly_set_cells /
+ *   nsk_assembly_set_simplex void the list.  With a list nsk_state_get_record returns (u_x, u_y, +0.0) and p of the
+ *   listed points, the bits of the state, n_points = the list's length; without one it behaves as above (-60 on
+ *   several ranks). */
 int nsk_record_set_cells(nsk_handle h, int64_t n_cells, const int32_t *cells, int subdivisions,
                          const double *w_u /* (s+1)^2 x 16 */, const double *w_p /* (s+1)^2 x 9 */);
+int nsk_record_set_points(nsk_handle h, int64_t n_points, const int32_t *u_node, const int32_t *p_dof);
 int nsk_state_get_record(nsk_handle h, int64_t n_points, double *vel3 /* 3 per point */, double *prs /* 1 per point */);
 /* values of a resident block times a factor: pressure_mass is assembled with 1/nu (:404, :450), block (1,0)
  * changes sign between the Stokes and the Newton phase (:397 against :444) */

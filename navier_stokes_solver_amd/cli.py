@@ -207,6 +207,12 @@ def run_gmsh(cfg, unsteady: bool) -> int:
     print("-----------------------------------------------")
     from . import postprocess as PP
     nranks = int(os.environ.get("NSK_RANKS", "1"))    # `mpirun -n N`: N rank threads (in-process transport), see below
+    if nranks > 1 and os.environ.get("NSK_DEVICE_ASSEMBLY") == "1":
+        # opt-in: every rank assembles, reports and records from its own resident state — both drivers
+        if os.environ.get("NSK_HOST_ASSEMBLY"):
+            sys.stderr.write("Error: NSK_DEVICE_ASSEMBLY=1 does not go with NSK_HOST_ASSEMBLY\n")
+            return 1
+        return run_gmsh_ranks(cfg, unsteady, nranks, space)
     ls = None
     if nranks <= 1 or unsteady:
         ls = S.LinearSolver()
@@ -472,6 +478,127 @@ def run_ranks(cfg, unsteady: bool, nranks: int) -> int:
     return 0
 
 
+def _gmsh_rank_main(cfg, unsteady, r, nranks, grp, make_handle, say, space, lay, first, out=None):
+    """One rank of `mpirun -n N StationaryNSSolver / NSSolver -M FILE` with the assembly on the device: its
+    rows of the first hand-off, its cells in local numbering (`simplex.device_rank_handoff`), its handle, device-resident
+    state with a halo-refreshed ghost tail and the reference's driver loop; forces and the VTU piece of its own cells from
+    that state.  `out` (tests): receives the rank's Newton history and its owned solution."""
+    import numpy as np
+
+    from . import newton as N
+    from . import partition as PT
+    from . import postprocess as PP
+    from . import simplex as SX
+    from . import solver as S
+    q = SX.local_problem(first, lay, r)
+    q.simplex = SX.device_rank_handoff(space, lay, r, q)      # (ValueError: an own cell outside the rank's ghost lists)
+    ghosts = grp.allgather(r, (q.ghost_u, q.ghost_p))
+    plan = {S.SPACE_U: PT.build_halo_plan(r, lay.u_ranges, [g[0] for g in ghosts]),
+            S.SPACE_P: PT.build_halo_plan(r, lay.p_ranges, [g[1] for g in ghosts])}
+    ls = make_handle()
+    try:
+        ls.set_option(S.OPT_TRI_ORDERING, S.ORDER_MULTICOLOR)
+        _env_options(ls, S)
+        backend = N.DeviceBackend(ls, q, cfg["solver"], cfg["prec"], cfg["tol"], max_iter=100000 if unsteady else 20000,
+                                  inv_dt=1.0 / cfg["dt"] if unsteady else 0.0, plan=plan)
+        host_report = _host_postprocess()
+        binary = cfg.get("vtu_format", "ascii") == "binary"
+        out_dir = os.environ.get("NSK_OUTPUT_DIR", "./")
+        if not host_report:
+            ls.set_force_edges_rank(space, lay, r, q.simplex)
+            xy, tris, u_node, p_dof = SX.record_points_rank(space, lay, r, q.simplex)
+            ls.set_record_points(u_node, p_dof)
+            # the piece: the vertices of the rank's own cells only; binary: the file image, filled in place (DESIGN 5s)
+            record = PP.VtuRecord.triangles(xy, tris) if binary else None
+            vel3, prs = (record.vel3, record.prs) if binary else (np.empty((len(xy), 3)), np.empty(len(xy)))
+
+        def report(nu, inlet_u, name):
+            stem = name[:-4]
+            pieces = [f"{stem}.{k}.vtu" for k in range(nranks)]
+            os.makedirs(out_dir, exist_ok=True)
+            if host_report:
+                # the A/B yardstick: the gathered solution through the host integrals and writer, as the host backend reports
+                parts = grp.allgather(r, backend.solution())
+                u, p = SX.gather_solution(lay, [x[0] for x in parts], [x[1] for x in parts])
+                SX.write_vtu(os.path.join(out_dir, pieces[r]), space, u, p, cells=np.nonzero(lay.cell_rank == r)[0])
+                shares = grp.allgather(r, SX.lift_drag_rank(space, lay, r, u, p, nu))          # (Utilities::MPI::sum)
+                drag, lift = sum(s[0] for s in shares), sum(s[1] for s in shares)
+            else:
+                ls.state_record(vel3=vel3, prs=prs)
+                if binary:
+                    record.write(os.path.join(out_dir, pieces[r]))
+                else:
+                    SX.write_vtu_points(os.path.join(out_dir, pieces[r]), xy, tris, vel3[:, 0], vel3[:, 1], prs)
+                drag, lift = ls.forces(nu)                     # this rank's edges; summed over the ranks inside the library
+            if r == 0:
+                SX.write_pvtu(os.path.join(out_dir, stem + ".pvtu"), pieces)
+            say("===============================================\nOutput written to output-stokes")
+            say("===============================================\n===============================================\nComputing lift and drag forces")
+            cd, cl = PP.coefficients(drag, lift, inlet_u)
+            say(f"===============================================\nLift coefficient: {cl:g}")
+            say(f"===============================================\nDrag coefficient: {cd:g}")
+
+        t0 = time.time()
+        try:
+            if unsteady:
+                nu_last = 1.0 / max(_levels(1.0, 10.0, cfg["Re"]))
+                hist = N.time_loop(backend, cfg["T"], cfg["dt"], cfg["Re"], log=say,
+                                   after_step=lambda step: report(nu_last, 0.3, f"output_{step:03d}.vtu"))
+            else:
+                hist = N.solve_newton(backend, cfg["Re"], log=say)
+                report(1.0 / max(_levels(10.0, 20.0, cfg["Re"])), 1.0, "output-stokes_0.vtu")
+            if out is not None:
+                out[r] = dict(history=hist, solution=backend.solution())
+        finally:
+            say(f"[nsk] {nranks} ranks, {backend.assemblies} assemblies (device, P2/P1), {backend.total_linear_iterations} outer "
+                f"iterations of solve_system() on the GPU, {time.time() - t0:.3f} s in "
+                f"{'the time loop' if unsteady else 'solve_newton'}")
+    finally:
+        ls.close()
+
+
+def run_gmsh_ranks(cfg, unsteady: bool, nranks: int, space) -> int:
+    """`-M FILE` on `NSK_RANKS=N` rank threads with `NSK_DEVICE_ASSEMBLY=1`: the layout and the first Stokes
+    hand-off once, then `_gmsh_rank_main` per rank over the in-process transport, as `run_ranks` runs `_rank_main`."""
+    import threading
+
+    import numpy as np
+    import torch
+
+    from . import simplex as SX
+    from . import solver as S
+    lay = SX.rank_layout(space, nranks)
+    U, nu0 = (0.3, 1.0) if unsteady else (0.1, 0.1)
+    first = SX.assemble(space, nu0, mode=0, inlet_bc=1, U=U)
+    print(f"  Number of ranks            = {nranks} (cells per rank: "
+          f"{' '.join(str(int(c)) for c in np.bincount(lay.cell_rank, minlength=nranks))})")
+    print(f"[nsk] NSK_DEVICE_ASSEMBLY=1: assembly, forces and VTU pieces on the device, P2/P1, {nranks} ranks")
+    ndev = max(1, torch.cuda.device_count())
+    uid = S.local_group_id(nranks, on_stream=(ndev == 1))
+    grp = _ThreadGroup(nranks)
+    errs = []
+
+    def rank_main(r):
+        try:
+            _gmsh_rank_main(cfg, unsteady, r, nranks, grp, lambda: S.LinearSolver(r, nranks, r % ndev, uid),
+                            print if r == 0 else (lambda *_a, **_k: None), space, lay, first)
+        except Exception as e:  # noqa: BLE001
+            errs.append((r, repr(e)))
+            grp.abort()                      # (as run_ranks: the Python rendezvous and the library's collectives)
+            S.abort_local_group(uid)
+
+    th = [threading.Thread(target=rank_main, args=(r,), daemon=True) for r in range(nranks)]
+    [t.start() for t in th]
+    while any(t.is_alive() for t in th) and not errs:
+        [t.join(0.2) for t in th]
+    if errs:
+        deadline = time.time() + float(os.environ.get("NSK_RANK_JOIN_TIMEOUT", "60"))
+        [t.join(max(0.0, deadline - time.time())) for t in th]
+        stuck = [r for r, t in enumerate(th) if t.is_alive()]
+        raise RuntimeError(f"rank failures: {sorted(errs)}" + (f"; ranks still blocked after the deadline: {stuck}" if stuck else ""))
+    return 0
+
+
 def run_processes(cfg, unsteady: bool) -> int:
     """The same drivers with ONE PROCESS PER RANK, as the reference runs under mpirun:
         python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 -m navier_stokes_solver_amd.cli StationaryNSSolver -m X,Y ...
@@ -507,8 +634,11 @@ def run(cfg, unsteady: bool) -> int:
     from . import solver as S
     if cfg.get("vtu_format", "ascii") == "binary":
         s = cfg.get("vtu_subdivisions", 1)
-        # (-M on several ranks or with NSK_HOST_ASSEMBLY: the values come from the host backend)
-        host = cfg["read_mesh"] and (int(os.environ.get("NSK_RANKS", "1")) > 1 or bool(os.environ.get("NSK_HOST_ASSEMBLY")))
+        # (-M on several ranks or with NSK_HOST_ASSEMBLY: the values come from the host backend — unless the ranks
+        #  assemble on the device, NSK_DEVICE_ASSEMBLY=1: then every rank packs its own piece)
+        several = int(os.environ.get("NSK_RANKS", "1")) > 1
+        host = cfg["read_mesh"] and ((several and os.environ.get("NSK_DEVICE_ASSEMBLY") != "1")
+                                     or bool(os.environ.get("NSK_HOST_ASSEMBLY")))
         print("[nsk] NSK_VTU_FORMAT=binary: the VTU record as raw appended data" + ("" if host else ", packed on the device")
               + (f", {s} x {s} patches per cell" if s > 1 else ""))
     if cfg["read_mesh"]:

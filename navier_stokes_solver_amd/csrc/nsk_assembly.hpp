@@ -60,7 +60,9 @@ void state_record(hipStream_t s, const AsmMesh &M, long n_cells, int subdivision
 struct SimplexMesh {  // device pointers
   long n_cells, n_blocks;
   int n_unodes, n_pdofs;
-  long pos00;               // position of entry (0,0) in the scalar CSR of block (0,0)
+  long pos00;               // position of entry (0,0) in the scalar CSR of block (0,0); -1: another rank owns global DoF 0
+  // several ranks: n_unodes / n_pdofs are the OWNED counts; the cells' ids run on into the ghost tail of the
+  // state vectors [owned | ghost], every list below is over owned nodes / DoFs / rows
   const int *cell_u;        // [n_cells][6] velocity node ids (vertices, then edge midpoints (0,1), (1,2), (2,0))
   const int *cell_p;        // [n_cells][3]
   const double *grad_lam;   // [n_cells][3][2] gradients of the barycentric coordinates
@@ -73,14 +75,23 @@ struct SimplexMesh {  // device pointers
   const double *outlet_w;   // [2 n_unodes] int phi_n n_c over the outlet (id 8) edges
   const unsigned char *dirichlet;    // per velocity DoF
 };
-void simplex_assemble(hipStream_t s, const SimplexMesh &M, const double *su, const double *sp, const double *so, double nu,
-                      double inv_dt, double p_out, int stokes, const int *rowptr, const int *col, double *val, double *d0,
-                      const double *bc, double *rhs_u, double *rhs_p, double *x0_u, double *x0_p);
+// One assembly in two halves, the sum of d0 over the ranks between them (the rank owning global DoF 0 writes
+// |val[pos00]|, the others 0).  simplex_assemble_blocks: the 2x2 node blocks of (0,0) and d0; simplex_assemble_rows: the
+// Dirichlet rows and the two right-hand sides, which read d0.
+void simplex_assemble_blocks(hipStream_t s, const SimplexMesh &M, const double *su, double nu, double inv_dt, int stokes,
+                             double *val, double *d0);
+void simplex_assemble_rows(hipStream_t s, const SimplexMesh &M, const double *su, const double *sp, const double *so, double nu,
+                           double inv_dt, double p_out, int stokes, const int *rowptr, const int *col, double *val,
+                           const double *d0, const double *bc, double *rhs_u, double *rhs_p, double *x0_u, double *x0_p);
 
 // forces over the id-10 edges: edge_cell, edge_local (the cell's local edge 0-2), edge_nl = (nx, ny, length) per edge
 void forces_edges(hipStream_t s, const SimplexMesh &M, long n_edges, const int *edge_cell, const unsigned char *edge_local,
                   const double *edge_nl, const double *su, const double *sp, double nu, double *slots, double *out2);
 // the record of the mesh's vertices: the first n_points velocity nodes and pressure DoFs, (u_x, u_y, +0.0) and p
 void simplex_record(hipStream_t s, long n_points, const double *su, const double *sp, double *vel3, double *prs);
+// the record of listed points (nsk_record_set_points): per point a velocity node and a pressure DoF of the state
+// [owned | ghost]; the bits of the state.  One launch, one thread per point
+void simplex_record_points(hipStream_t s, long n_points, const int *u_node, const int *p_dof, const double *su, const double *sp,
+                           double *vel3, double *prs);
 
 }  // namespace nsk

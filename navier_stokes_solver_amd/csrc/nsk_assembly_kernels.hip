@@ -587,7 +587,8 @@ __global__ __launch_bounds__(256) void simplex_dirichlet_rows_kernel(int n_u, co
   const double d = d0[0];
   for (int k = rowptr[r]; k < rowptr[r + 1]; ++k) val[k] = col[k] == r ? d : 0.0;
 }
-__global__ void simplex_d0_kernel(const double *val, long pos, double *out) { out[0] = fabs(val[pos]); }
+// (pos < 0: another rank owns global DoF 0 and this one adds 0 to the sum over the ranks)
+__global__ void simplex_d0_kernel(const double *val, long pos, double *out) { out[0] = pos >= 0 ? fabs(val[pos]) : 0.0; }
 
 __global__ __launch_bounds__(256) void simplex_rhs_u_kernel(SimplexMesh M, const double *__restrict__ su,
                                                            const double *__restrict__ spv, const double *__restrict__ so,
@@ -716,12 +717,35 @@ __global__ __launch_bounds__(256) void simplex_record_kernel(long n_points, cons
   prs[t] = spv[t];
 }
 
+// The same record for a list of points (one rank's piece): point t is velocity node u_node[t] and pressure DoF
+// p_dof[t] of the state [owned | ghost] — a gather, the bits of the state.  The ids were checked on the host.
+__global__ __launch_bounds__(256) void simplex_record_points_kernel(long n_points, const int *__restrict__ u_node,
+                                                                    const int *__restrict__ p_dof,
+                                                                    const double *__restrict__ su,
+                                                                    const double *__restrict__ spv, double *__restrict__ vel3,
+                                                                    double *__restrict__ prs) {
+  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n_points) return;
+  const size_t n = (size_t)u_node[t];
+  vel3[3 * t] = su[2 * n];
+  vel3[3 * t + 1] = su[2 * n + 1];
+  vel3[3 * t + 2] = 0.0;
+  prs[t] = spv[p_dof[t]];
+}
+
 }  // namespace
 
 void simplex_record(hipStream_t s, long n_points, const double *su, const double *sp, double *vel3, double *prs) {
   if (n_points > 0)
     hipLaunchKernelGGL(simplex_record_kernel, dim3((unsigned)((n_points + 255) / 256)), dim3(256), 0, s, n_points, su, sp, vel3,
                        prs);
+}
+
+void simplex_record_points(hipStream_t s, long n_points, const int *u_node, const int *p_dof, const double *su, const double *sp,
+                           double *vel3, double *prs) {
+  if (n_points > 0)
+    hipLaunchKernelGGL(simplex_record_points_kernel, dim3((unsigned)((n_points + 255) / 256)), dim3(256), 0, s, n_points, u_node,
+                       p_dof, su, sp, vel3, prs);
 }
 
 void forces_edges(hipStream_t s, const SimplexMesh &M, long n_edges, const int *edge_cell, const unsigned char *edge_local,
@@ -732,13 +756,18 @@ void forces_edges(hipStream_t s, const SimplexMesh &M, long n_edges, const int *
   forces_sum(s, n_edges * 2, slots, out2);
 }
 
-void simplex_assemble(hipStream_t s, const SimplexMesh &M, const double *su, const double *sp, const double *so, double nu,
-                      double inv_dt, double p_out, int stokes, const int *rowptr, const int *col, double *val, double *d0,
-                      const double *bc, double *rhs_u, double *rhs_p, double *x0_u, double *x0_p) {
+void simplex_assemble_blocks(hipStream_t s, const SimplexMesh &M, const double *su, double nu, double inv_dt, int stokes,
+                             double *val, double *d0) {
   const int T = 256;
   hipLaunchKernelGGL(simplex_F_blocks_kernel, dim3((unsigned)((M.n_blocks + T - 1) / T)), dim3(T), 0, s, M, su, nu, inv_dt,
                      stokes, val);
   hipLaunchKernelGGL(simplex_d0_kernel, dim3(1), dim3(1), 0, s, val, (long)M.pos00, d0);
+}
+
+void simplex_assemble_rows(hipStream_t s, const SimplexMesh &M, const double *su, const double *sp, const double *so, double nu,
+                           double inv_dt, double p_out, int stokes, const int *rowptr, const int *col, double *val,
+                           const double *d0, const double *bc, double *rhs_u, double *rhs_p, double *x0_u, double *x0_p) {
+  const int T = 256;
   hipLaunchKernelGGL(simplex_dirichlet_rows_kernel, dim3((2 * M.n_unodes + T - 1) / T), dim3(T), 0, s, 2 * M.n_unodes, rowptr,
                      col, M.dirichlet, d0, val);
   hipLaunchKernelGGL(simplex_rhs_u_kernel, dim3((M.n_unodes + T - 1) / T), dim3(T), 0, s, M, su, sp, so, nu, inv_dt, p_out,

@@ -310,13 +310,17 @@ int nsk_upload_system(nsk_handle h, const double *ru, const double *rp, const do
   NSK_HIP(hipMemcpyAsync(h->x_b, xu, bu, hipMemcpyHostToDevice, h->s()));
   NSK_HIP(hipMemcpyAsync(h->x_b + h->n_u(), xp, bp, hipMemcpyHostToDevice, h->s()));
   h->ctx.sync();
+  h->asmd.x_is_result = h->asmd.sx_delta_valid = false;   // (the caller's vector, no solve's result)
   return 0;
   NSK_CATCH(h)
 }
 
 int nsk_solve_resident(nsk_handle h, int solver, double tol, int max_iter, int *iters, double *final_res) {
   NSK_TRY_DEV(h)
-  return h->solve_resident(solver, tol, max_iter, iters, final_res);
+  const int rc = h->solve_resident(solver, tol, max_iter, iters, final_res);
+  h->asmd.x_is_result = true;   // x_b is delta_owned until an assembly writes the next initial guess (nsk_assemble, P2/P1)
+  h->asmd.sx_delta_valid = false;
+  return rc;
   NSK_CATCH_ABORT(h)
 }
 

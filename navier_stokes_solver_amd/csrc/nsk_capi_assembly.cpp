@@ -97,6 +97,7 @@ int nsk_assembly_set_cells(nsk_handle h, int64_t n_cells, const int32_t *cell_u_
   A.mf_valid = false;   // (cq of another mesh)
   A.forces_set = false;   // (faces index the cells of another mesh)
   A.record_set = false;   // (so does the record's list)
+  A.rec_points_set = false;
   if (!A.sol_u) {
     A.sol_u = h->pool_u.get(true); A.eval_u = h->pool_u.get(true); A.old_u = h->pool_u.get(true);
     A.sol_p = h->pool_p.get(true); A.eval_p = h->pool_p.get(true);
@@ -176,8 +177,10 @@ int nsk_state_update(nsk_handle h, double alpha) {
   // solution_owned = evaluation_point; solution_owned.add(alpha, delta_owned); solution = solution_owned
   vec_copy(h->s(), h->n_u(), A.eval_u, A.sol_u);
   vec_copy(h->s(), h->n_p(), A.eval_p, A.sol_p);
-  vec_axpy(h->s(), h->n_u(), sref(alpha), h->x_b, A.sol_u);
-  vec_axpy(h->s(), h->n_p(), sref(alpha), h->x_b + h->n_u(), A.sol_p);
+  // (P2/P1: an assembly since the solve has overwritten x_b; the result is in the copy made there)
+  const double *delta = (A.simplex && A.sx_delta_valid) ? A.sx_delta : h->x_b;
+  vec_axpy(h->s(), h->n_u(), sref(alpha), delta, A.sol_u);
+  vec_axpy(h->s(), h->n_p(), sref(alpha), delta + h->n_u(), A.sol_p);
   h->halo(0, h->pool_u.view(A.sol_u));
   h->halo(1, h->pool_p.view(A.sol_p));
   return 0;
@@ -190,17 +193,22 @@ int nsk_assembly_set_simplex(nsk_handle h, int64_t n_cells, const int32_t *cell_
                              const int32_t *node_ptr, const int32_t *node_ent, const int32_t *vert_ptr,
                              const int32_t *vert_ent, const double *outlet_w, int64_t pos00) {
   NSK_TRY_DEV(h)
-  if (h->ctx.comm.nranks > 1) throw Error(-65, "nsk_assembly_set_simplex: one rank only");
   Csr &F = h->blk[NSK_BLK_F];
   if (!F.present) throw Error(-63, "hand the blocks over before the assembly data");
+  const bool several = h->ctx.comm.nranks > 1;
+  // several ranks: the cells' ids run on into the ghost tail of the state vectors [owned | ghost] (VecPool), whole nodes
+  if (several && h->sp[0].ng % 2) throw Error(-65, "nsk_assembly_set_simplex: the ghost velocity DoFs must be whole nodes");
   h->ensure_pools();
   const int nun = h->n_u() / 2, np = h->n_p();
-  if (n_cells <= 0 || n_blocks <= 0 || pos00 < 0 || pos00 >= F.nnz) throw Error(-64, "nsk_assembly_set_simplex: bad sizes");
+  const int nun_all = several ? nun + h->sp[0].ng / 2 : nun, np_all = several ? np + h->sp[1].ng : np;
+  if (n_cells <= 0 || n_blocks <= 0 || pos00 >= F.nnz) throw Error(-64, "nsk_assembly_set_simplex: bad sizes");
+  // pos00 = -1: another rank owns global DoF 0 (its |entry (0,0)| reaches this one in nsk_assemble's sum over the ranks)
+  if (pos00 < (several ? -1 : 0)) throw Error(-64, "nsk_assembly_set_simplex: bad sizes (pos00 = -1 needs several ranks)");
   // shapes the kernels index with: checked on the host before anything is launched
   for (int64_t k = 0; k < 6 * n_cells; ++k)
-    if (cell_u_nodes[k] < 0 || cell_u_nodes[k] >= nun) throw Error(-64, "simplex assembly: velocity node id out of range");
+    if (cell_u_nodes[k] < 0 || cell_u_nodes[k] >= nun_all) throw Error(-64, "simplex assembly: velocity node id out of range");
   for (int64_t k = 0; k < 3 * n_cells; ++k)
-    if (cell_p_dofs[k] < 0 || cell_p_dofs[k] >= np) throw Error(-64, "simplex assembly: pressure DoF id out of range");
+    if (cell_p_dofs[k] < 0 || cell_p_dofs[k] >= np_all) throw Error(-64, "simplex assembly: pressure DoF id out of range");
   if (blk_ptr[0] != 0 || node_ptr[0] != 0 || vert_ptr[0] != 0) throw Error(-64, "simplex assembly: lists must start at 0");
   for (int64_t b = 0; b < n_blocks; ++b) {
     if (blk_ptr[b + 1] < blk_ptr[b]) throw Error(-64, "simplex assembly: block list not ascending");
@@ -244,6 +252,8 @@ int nsk_assembly_set_simplex(nsk_handle h, int64_t n_cells, const int32_t *cell_
   A.mf_valid = false;
   A.forces_set = false;   // (edges index the cells of another mesh)
   A.record_set = false;
+  A.rec_points_set = false;   // (the points name nodes of another numbering)
+  A.sx_delta_valid = false;
   A.rec_out.release();
   A.simplex = true;
   A.ready = true;
@@ -268,9 +278,18 @@ int nsk_assemble(nsk_handle h, int stokes, double nu, double inv_dt, double p_ou
     const SimplexMesh SM{A.n_cells, A.sx_blocks, h->n_u() / 2, h->n_p(), A.sx_pos00, A.cell_u.p, A.cell_p.p, A.sx_grad.p,
                          A.sx_area.p, A.sx_blk_ptr.p, A.sx_blk_ent.p, A.sx_pos0.p, A.sx_pos1.p, A.sx_node_ptr.p,
                          A.sx_node_ent.p, A.sx_vert_ptr.p, A.sx_vert_ent.p, A.sx_outlet.p, A.dirichlet.p};
-    simplex_assemble(s, SM, A.sol_u, A.sol_p, (A.have_old && inv_dt != 0.0) ? A.old_u : nullptr, nu, inv_dt, p_out, stokes != 0,
-                     F.rowptr.p, F.col.p, F.val.p, h->ctx.slot(sl), inhomogeneous_bc ? A.bc.p : nullptr, h->rhs_b,
-                     h->rhs_b + h->n_u(), h->x_b, h->x_b + h->n_u());
+    simplex_assemble_blocks(s, SM, A.sol_u, nu, inv_dt, stokes != 0, F.val.p, h->ctx.slot(sl));
+    // the Dirichlet diagonal, as in the Q3/Q2 branch below: the rank owning global DoF 0 wrote it, the others 0
+    if (h->ctx.comm.nranks > 1) h->ctx.comm.allreduce_sum(h->ctx.slot(sl), 1, s);
+    if (A.x_is_result) {   // the rows below write the next initial guess over it: keep delta_owned for nsk_state_update
+      if (!A.sx_delta) A.sx_delta = h->pool_b.get(false);
+      vec_copy(s, h->N(), h->x_b, A.sx_delta);
+      A.sx_delta_valid = true;
+      A.x_is_result = false;
+    }
+    simplex_assemble_rows(s, SM, A.sol_u, A.sol_p, (A.have_old && inv_dt != 0.0) ? A.old_u : nullptr, nu, inv_dt, p_out,
+                          stokes != 0, F.rowptr.p, F.col.p, F.val.p, h->ctx.slot(sl), inhomogeneous_bc ? A.bc.p : nullptr,
+                          h->rhs_b, h->rhs_b + h->n_u(), h->x_b, h->x_b + h->n_u());
     ++F.values_version;
     F.refresh_blocked(s);
     h->ctx.norm2(h->N(), h->rhs_b, sl + 1);
@@ -439,18 +458,49 @@ int nsk_record_set_cells(nsk_handle h, int64_t n_cells, const int32_t *cells, in
   NSK_CATCH(h)
 }
 
+int nsk_record_set_points(nsk_handle h, int64_t n_points, const int32_t *u_node, const int32_t *p_dof) {
+  NSK_TRY_DEV(h)
+  auto &A = h->asmd;
+  if (!A.ready) throw Error(-69, "nsk_record_set_points: no cells on the handle (call nsk_assembly_set_simplex first)");
+  if (!A.simplex) throw Error(-71, "nsk_record_set_points: the handle holds Q3/Q2 cells (nsk_record_set_cells)");
+  if (n_points < 0 || (n_points > 0 && (!u_node || !p_dof)) || n_points > INT64_MAX / (4 * (int64_t)sizeof(double)))
+    throw Error(-60, "nsk_record_set_points: bad arguments");
+  // what the kernel indexes with: checked on the host before anything is launched.  The state is [owned | ghost]
+  const int64_t nun_all = (h->n_u() + h->sp[0].ng) / 2, np_all = (int64_t)h->n_p() + h->sp[1].ng;
+  for (int64_t k = 0; k < n_points; ++k) {
+    if (u_node[k] < 0 || u_node[k] >= nun_all) throw Error(-72, "nsk_record_set_points: velocity node id out of range");
+    if (p_dof[k] < 0 || p_dof[k] >= np_all) throw Error(-72, "nsk_record_set_points: pressure DoF id out of range");
+  }
+  hipStream_t s = h->s();
+  A.rec_points_set = false;
+  A.rec_unode.upload(u_node, (size_t)n_points, s);
+  A.rec_pdof.upload(p_dof, (size_t)n_points, s);
+  A.rec_out.alloc((size_t)std::max<int64_t>(1, n_points * 4));
+  h->ctx.sync();
+  A.rec_points = (long)n_points;
+  A.rec_points_set = true;
+  return 0;
+  NSK_CATCH(h)
+}
+
 int nsk_state_get_record(nsk_handle h, int64_t n_points, double *vel3, double *prs) {
   NSK_TRY_DEV(h)
   auto &A = h->asmd;
   if (!A.ready) throw Error(-69, "nsk_state_get_record: no cells on the handle");
   if (!A.simplex && !A.record_set) throw Error(-69, "nsk_state_get_record: no record list handed over (nsk_record_set_cells)");
   if (!A.state_set) throw Error(-73, "nsk_state_get_record: no state on the device");
-  const int64_t want = A.simplex ? (int64_t)h->n_p() : (int64_t)A.rec_cells * (A.rec_sub + 1) * (A.rec_sub + 1);
+  const bool listed = A.simplex && A.rec_points_set;
+  const int64_t want = listed ? (int64_t)A.rec_points
+                              : A.simplex ? (int64_t)h->n_p() : (int64_t)A.rec_cells * (A.rec_sub + 1) * (A.rec_sub + 1);
   if (n_points != want || (n_points > 0 && (!vel3 || !prs)))
     throw Error(-60, "nsk_state_get_record: bad arguments (n_points is not the record's number of points)");
   if (n_points == 0) return 0;
   hipStream_t s = h->s();
-  if (A.simplex) {
+  if (listed) {   // the listed points of a P2/P1 handle (nsk_record_set_points): one rank's piece, ghost vertices included
+    if (A.rec_out.n != (size_t)n_points * 4) A.rec_out.alloc((size_t)n_points * 4);
+    simplex_record_points(s, (long)n_points, A.rec_unode.p, A.rec_pdof.p, A.sol_u, A.sol_p, A.rec_out.p,
+                          A.rec_out.p + (size_t)n_points * 3);
+  } else if (A.simplex) {
     // the vertices are the first n_p velocity nodes (simplex.py's numbering); one rank: the state is [owned]
     if (h->ctx.comm.nranks > 1 || 2 * n_points > (int64_t)h->n_u())
       throw Error(-60, "nsk_state_get_record: the P2/P1 record covers one rank with the vertices numbered first");

@@ -281,6 +281,12 @@ struct nsk_handle_s {
     DBuf<int> sx_blk_ptr, sx_blk_ent, sx_node_ptr, sx_node_ent, sx_vert_ptr, sx_vert_ent;
     DBuf<long> sx_pos0, sx_pos1;
     DBuf<double> sx_grad, sx_area, sx_outlet;
+    // P2/P1: nsk_assemble writes the next solve's initial guess over the resident result of the last one (x_b), and the
+    // line search assembles between its steps: the result is copied here first, and nsk_state_update reads the copy
+    // (delta_owned of the reference outlives assemble_system()).  x_is_result: x_b holds a solve's result no assembly
+    // has overwritten yet (set by nsk_solve_resident, cleared by nsk_upload_system)
+    double *sx_delta = nullptr;   // pool_b vector [u_owned | p_owned | ...]
+    bool sx_delta_valid = false, x_is_result = false;
     double *old_u = nullptr;  // solution_old of the time loop (velocity part; the pressure is not used)
     bool have_old = false;
     double assemble_ms = 0;
@@ -302,6 +308,10 @@ struct nsk_handle_s {
     int rec_sub = 1;
     DBuf<int> rec_cell;
     DBuf<double> rec_wu, rec_wp, rec_out;   // (s+1)^2 x 16, (s+1)^2 x 9; 3 + 1 doubles per point (P2/P1: per vertex)
+    // P2/P1: the record's points as local ids (nsk_record_set_points): void with the cell data
+    bool rec_points_set = false;
+    long rec_points = 0;
+    DBuf<int> rec_unode, rec_pdof;          // per point: velocity node and pressure DoF, owned or ghost
   } asmd;
   int matrix_free_f = 0;        // NSK_OPT_INNER_MATRIX_FREE_F
   bool matfree_wanted = false;  // what the last set-up took of it (the option or NSK_INNER_MATRIX_FREE_F)

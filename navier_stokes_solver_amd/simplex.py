@@ -319,10 +319,18 @@ def write_vtu(path, sp_: SimplexSpace, u, p, cells=None):
     nv = sp_.n_p
     all_cells = sp_.cell_p
     sp_cells = all_cells if cells is None else all_cells[np.asarray(cells)]
+    write_vtu_points(path, sp_.mesh.nodes, sp_cells, u[0:2 * nv:2], u[1:2 * nv:2], p[:nv])
+
+
+def write_vtu_points(path, nodes, sp_cells, ux, uy, p):
+    """The same ASCII record from arrays: points `nodes` [n, 2], linear triangles `sp_cells` [m, 3] into them, the
+    velocity components and the pressure per point (one rank's compact piece, `record_points_rank`)."""
+    nv = len(nodes)
+    u = np.stack([np.asarray(ux, float), np.asarray(uy, float)], axis=1).reshape(-1)
     with open(path, "w") as f:
         f.write('<?xml version="1.0"?>\n<VTKFile type="UnstructuredGrid" version="0.1" byte_order="LittleEndian">\n<UnstructuredGrid>\n')
         f.write(f'<Piece NumberOfPoints="{nv}" NumberOfCells="{len(sp_cells)}">\n<Points>\n<DataArray type="Float64" NumberOfComponents="3" format="ascii">\n')
-        for x, y in sp_.mesh.nodes:
+        for x, y in nodes:
             f.write(f"{x:.16g} {y:.16g} 0\n")
         f.write('</DataArray>\n</Points>\n<Cells>\n<DataArray type="Int32" Name="connectivity" format="ascii">\n')
         for t in sp_cells:
@@ -467,3 +475,127 @@ def lift_drag_rank(sp_: SimplexSpace, lay: RankLayout, rank: int, u, p, nu):
     sub = SimplexSpace(sp_.mesh, sp_.cell_u, sp_.cell_p, sp_.xy_u, sp_.dirichlet, sp_.grad_lam, sp_.area, sp_.outlet,
                        tuple(np.asarray(c)[keep] for c in sp_.obstacle), sp_.n_un, sp_.n_p)
     return lift_drag(sub, u, p, nu)
+
+
+# ------------------------------------------------------------------ device assembly on several ranks
+def device_rank_handoff(sp_: SimplexSpace, lay: RankLayout, rank: int, q) -> dict:
+    """What `nsk_assembly_set_simplex` takes on rank `rank` of `lay`, in the rank's local numbering; `q` =
+    `local_problem(first, lay, rank)`.
+
+    Cells: every cell touching an owned velocity node or an owned pressure DoF, plus the rank's own cells, ascending by
+    global id (`cells`; `own`: the mask of the rank's own).  Local ids: owned first (new id minus the range's begin), then
+    the ghosts in the order of `q.ghost_u[0::2]` / `q.ghost_p`.  Every node and vertex of a local cell must be owned or
+    ghost (ValueError naming the cell otherwise: an own cell enclosed by lower ranks).  The lists are over owned rows,
+    nodes and DoFs, the cells inside each list ascending by global id: every sum is the one-rank sum term for term."""
+    u0, u1 = int(lay.u_ranges[rank]), int(lay.u_ranges[rank + 1])
+    p0, p1 = int(lay.p_ranges[rank]), int(lay.p_ranges[rank + 1])
+    n_own, np_own = (u1 - u0) // 2, p1 - p0
+    gh_u, gh_p = np.asarray(q.ghost_u, np.int64), np.asarray(q.ghost_p, np.int64)
+    if len(gh_u) % 2 or (gh_u[1::2] != gh_u[0::2] + 1).any():
+        raise ValueError("the ghost velocity DoFs are not whole nodes")
+
+    def localise(new, begin, n_owned, ghosts):
+        """local id of every old id (-1: neither owned nor ghost)"""
+        own = (new >= begin) & (new < begin + n_owned)
+        pos = np.searchsorted(ghosts, new)
+        hit = (pos < len(ghosts)) & (ghosts[np.minimum(pos, max(len(ghosts) - 1, 0))] == new) if len(ghosts) else np.zeros(len(new), bool)
+        return np.where(own, new - begin, np.where(hit, n_owned + pos, -1)), own
+
+    node_loc, node_own = localise(lay.node_new, u0 // 2, n_own, gh_u[0::2] // 2)
+    vert_loc, vert_own = localise(lay.vert_new, p0, np_own, gh_p)
+    is_own = lay.cell_rank == rank
+    keep = node_own[sp_.cell_u].any(axis=1) | vert_own[sp_.cell_p].any(axis=1) | is_own
+    cells = np.nonzero(keep)[0]
+    cu, cp = node_loc[sp_.cell_u[cells]], vert_loc[sp_.cell_p[cells]]
+    bad = np.nonzero((cu < 0).any(axis=1) | (cp < 0).any(axis=1))[0]
+    if len(bad):
+        raise ValueError(f"rank {rank}: cell {int(cells[bad[0]])} has nodes or vertices the rank neither owns nor holds as "
+                         f"ghosts (an own cell enclosed by lower ranks)")
+    T = len(cells)
+    # 2x2 node blocks of q.F: owned rows, owned and ghost columns (as device_handoff builds them)
+    rp, col = q.F.rowptr.astype(np.int64), q.F.col.astype(np.int64)
+    nblk_of = (rp[1::2] - rp[0:-1:2]) // 2
+    bstart = np.concatenate([[0], np.cumsum(nblk_of)])
+    nb = int(bstart[-1])
+    node_of_blk = np.repeat(np.arange(n_own), nblk_of)
+    j_of_blk = np.arange(nb) - bstart[node_of_blk]
+    pos0 = rp[2 * node_of_blk] + 2 * j_of_blk
+    pos1 = rp[2 * node_of_blk + 1] + 2 * j_of_blk
+    mcol = col[pos0] // 2
+    n_all = n_own + len(gh_u) // 2
+    lookup = sp.csr_matrix((np.arange(1, nb + 1), mcol, bstart), shape=(n_own, n_all))
+    n_idx = np.repeat(cu[:, :, None], 6, axis=2).ravel()
+    m_idx = np.repeat(cu[:, None, :], 6, axis=1).ravel()
+    code = (np.arange(T)[:, None] * 36 + np.arange(36)[None, :]).ravel()
+    rows = n_idx < n_own                                                    # the rows of ghost nodes are another rank's
+    n_idx, m_idx, code = n_idx[rows], m_idx[rows], code[rows]
+    bid = np.asarray(lookup[n_idx, m_idx]).ravel() - 1
+    if (bid < 0).any():
+        raise ValueError("a cell couples nodes that are not in the sparsity pattern of block (0,0)")
+    order = np.argsort(bid, kind="stable")
+    blk_ptr = np.concatenate([[0], np.cumsum(np.bincount(bid, minlength=nb))])
+
+    def per(ids, width, n):
+        c = (np.arange(T)[:, None] * width + np.arange(width)[None, :]).ravel()
+        i = ids.ravel()
+        c, i = c[i < n], i[i < n]
+        o = np.argsort(i, kind="stable")
+        return np.concatenate([[0], np.cumsum(np.bincount(i, minlength=n))]).astype(np.int32), c[o].astype(np.int32)
+    node_ptr, node_ent = per(cu, 6, n_own)
+    vert_ptr, vert_ent = per(cp, 3, np_own)
+    outlet_w = np.zeros(sp_.n_u)
+    a, m, b, nx_, ny_, ln = sp_.outlet[:6]
+    for node, w in ((a, 1 / 6), (m, 4 / 6), (b, 1 / 6)):
+        if len(node):
+            np.add.at(outlet_w, 2 * node.astype(int), w * ln * nx_)
+            np.add.at(outlet_w, 2 * node.astype(int) + 1, w * ln * ny_)
+    inv_n = np.empty(sp_.n_un, np.int64)
+    inv_n[lay.node_new] = np.arange(sp_.n_un)
+    inv_v = np.empty(sp_.n_p, np.int64)
+    inv_v[lay.vert_new] = np.arange(sp_.n_p)
+    own_nodes = inv_n[u0 // 2:u1 // 2]                                      # old ids of the owned nodes, in local order
+    ou = np.stack([2 * own_nodes, 2 * own_nodes + 1], axis=1).reshape(-1)
+    # the Dirichlet diagonal is |F[0, 0]| of the one-rank numbering: old DoF 0, wherever the layout put it
+    d0 = 2 * int(lay.node_new[0])
+    pos00 = -1
+    if u0 <= d0 < u1:
+        r = d0 - u0
+        pos00 = int(rp[r] + np.searchsorted(col[rp[r]:rp[r + 1]], r))
+    return dict(cell_u=cu.astype(np.int32), cell_p=cp.astype(np.int32),
+                grad_lam=np.ascontiguousarray(sp_.grad_lam[cells], float), area=np.ascontiguousarray(sp_.area[cells], float),
+                n_blocks=nb, blk_ptr=blk_ptr.astype(np.int32), blk_ent=code[order].astype(np.int32),
+                blk_pos0=pos0.astype(np.int64), blk_pos1=pos1.astype(np.int64), node_ptr=node_ptr, node_ent=node_ent,
+                vert_ptr=vert_ptr, vert_ent=vert_ent, outlet_w=np.ascontiguousarray(outlet_w[ou]), pos00=pos00,
+                cells=cells, own=is_own[cells],
+                node_ids=np.concatenate([own_nodes, inv_n[gh_u[0::2] // 2]]),          # old id of every local node / DoF
+                vert_ids=np.concatenate([inv_v[p0:p1], inv_v[gh_p]]))
+
+
+def force_edges_rank(sp_: SimplexSpace, lay: RankLayout, rank: int, handoff: dict):
+    """`force_edges` for one rank: the id-10 edges of its own cells (what `lift_drag_rank` integrates over), the cells as
+    indices into the rank's cell list (`handoff['cells']`)."""
+    ec, el, nl = force_edges(sp_)
+    keep = lay.cell_rank[ec] == rank if len(ec) else np.zeros(0, bool)
+    loc = np.searchsorted(handoff["cells"], ec[keep])
+    if len(loc) and not (handoff["cells"][loc] == ec[keep]).all():
+        raise ValueError("an own cell is missing from the rank's cell list")
+    return (np.ascontiguousarray(loc, np.int32), np.ascontiguousarray(el[keep], np.uint8), np.ascontiguousarray(nl[keep], np.float64))
+
+
+def record_points_rank(sp_: SimplexSpace, lay: RankLayout, rank: int, handoff: dict):
+    """One rank's piece of the VTU record: the vertices of its own cells in compact numbering (ascending by mesh vertex).
+    Returns (xy [n, 2], tris [own cells, 3] into the compact numbering, u_node [n], p_dof [n]): per point the local
+    velocity node and the local pressure DoF, owned or ghost (`nsk_record_set_points`)."""
+    own_cells = handoff["cells"][handoff["own"]]
+    tri = sp_.cell_p[own_cells]
+    verts = np.unique(tri)
+
+    def local(ids, n):
+        loc = np.full(n, -1, np.int64)
+        loc[ids] = np.arange(len(ids))
+        return loc[verts]                                                   # (a vertex is velocity node and pressure DoF of its id)
+    u_node, p_dof = local(handoff["node_ids"], sp_.n_un), local(handoff["vert_ids"], sp_.n_p)
+    if (u_node < 0).any() or (p_dof < 0).any():
+        raise ValueError("a vertex of an own cell is neither owned nor ghost")
+    return (np.ascontiguousarray(sp_.mesh.nodes[verts, :2], float), np.searchsorted(verts, tri).astype(np.int64),
+            u_node.astype(np.int32), p_dof.astype(np.int32))

@@ -62,7 +62,7 @@ EXPORTS = [
     "nsk_state_save", "nsk_state_save_old", "nsk_state_update", "nsk_assemble", "nsk_scale_values", "nsk_download_rhs", "nsk_time_assemble", "nsk_time_op", "nsk_profile_begin", "nsk_profile_read", "nsk_profile_end",
     "nsk_debug_spmv_form",
     "nsk_forces_set_faces", "nsk_forces_set_edges", "nsk_forces", "nsk_state_get_patches",
-    "nsk_record_set_cells", "nsk_state_get_record",
+    "nsk_record_set_cells", "nsk_state_get_record", "nsk_record_set_points",
 ]
 
 
@@ -145,6 +145,7 @@ def lib() -> C.CDLL:
         L.nsk_state_get_patches.argtypes = [vp, C.c_int64, i32p, f64p, f64p]
         L.nsk_record_set_cells.argtypes = [vp, C.c_int64, i32p, C.c_int, f64p, f64p]
         L.nsk_state_get_record.argtypes = [vp, C.c_int64, f64p, f64p]
+        L.nsk_record_set_points.argtypes = [vp, C.c_int64, i32p, i32p]
         L.nsk_download_rhs.argtypes = [vp, f64p, f64p]
         L.nsk_time_assemble.argtypes = [vp, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_double)]
         L.nsk_amg_info.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
@@ -574,6 +575,13 @@ class LinearSolver:
         ec, el, nl = SX.force_edges(space)
         self._ck(self.L.nsk_forces_set_edges(self.h, len(ec), ec.ctypes.data, el.ctypes.data, nl.ctypes.data))
 
+    def set_force_edges_rank(self, space, lay, rank, handoff):
+        """One rank of several: the id-10 edges of its own cells (simplex.force_edges_rank), after set_assembly with that
+        rank's hand-off (simplex.device_rank_handoff).  A rank without such edges hands over none."""
+        from . import simplex as SX
+        ec, el, nl = SX.force_edges_rank(space, lay, rank, handoff)
+        self._ck(self.L.nsk_forces_set_edges(self.h, len(ec), ec.ctypes.data, el.ctypes.data, nl.ctypes.data))
+
     def forces(self, nu, local=False):
         """(drag_force, lift_force) over the handed-over faces / edges from the resident state, summed over the ranks
         (collective); local=True: ((drag, lift), this rank's share)."""
@@ -600,6 +608,14 @@ class LinearSolver:
         wu, wp = (None, None) if tables is None else (_f64(tables[0]), _f64(tables[1]))
         self._ck(self.L.nsk_record_set_cells(self.h, len(c), c.ctypes.data, s, None if wu is None else wu.ctypes.data,
                                              None if wp is None else wp.ctypes.data))
+
+    def set_record_points(self, u_node, p_dof):
+        """The record's points of a P2/P1 handle as local ids (simplex.record_points_rank): per point the velocity node and
+        the pressure DoF, owned or ghost; after set_assembly with a simplex hand-off."""
+        un, pd = np.ascontiguousarray(u_node, np.int32), np.ascontiguousarray(p_dof, np.int32)
+        if un.shape != pd.shape or un.ndim != 1:
+            raise ValueError("set_record_points: one velocity node and one pressure DoF per point")
+        self._ck(self.L.nsk_record_set_points(self.h, len(un), un.ctypes.data, pd.ctypes.data))
 
     def state_record(self, n_points=None, vel3=None, prs=None):
         """(vel3 [n_points, 3], prs [n_points]): the `velocity` and `pressure` arrays of the record in file layout, from the
