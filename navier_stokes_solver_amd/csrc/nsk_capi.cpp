@@ -4,6 +4,7 @@
 
 #include <algorithm>
 #include <cstring>
+#include <initializer_list>
 
 #include "../../include/nsk_threads.h"
 #include <omp.h>
@@ -182,47 +183,40 @@ int nsk_update_values(nsk_handle h, int b, const double *val) {
   NSK_CATCH(h)
 }
 
+// "v must be one of these, else -61 with this text": the plain cases of nsk_set_option
+static int one_of(double v, std::initializer_list<double> allowed, const char *text) {
+  for (const double a : allowed)
+    if (v == a) return (int)v;
+  throw Error(-61, text);
+}
+
 int nsk_set_option(nsk_handle h, int opt, double v) {
   NSK_TRY(h)
+  SetupRequest &req = h->req;
   switch (opt) {
     case NSK_OPT_TRI_ORDERING: h->tri_ordering = v != 0.0 ? ORDER_MULTICOLOR : ORDER_NATURAL; break;
     case NSK_OPT_SUBDOMAINS: h->subdomains = std::max(1, (int)v); break;
     case NSK_OPT_FUSE_BLOCK_ROW: h->fuse_block_row = v != 0.0; break;
     case NSK_OPT_STREAM_KERNELS: h->use_stream = v != 0.0; break;
-    case NSK_OPT_TRI_SYNC_FREE:
-      if (v != 0.0 && v != 1.0 && v != 2.0) throw Error(-61, "NSK_OPT_TRI_SYNC_FREE: 0, 1 or 2");
-      h->sync_free_mode = (int)v;
-      break;
+    case NSK_OPT_TRI_SYNC_FREE: h->sync_free_mode = one_of(v, {0, 1, 2}, "NSK_OPT_TRI_SYNC_FREE: 0, 1 or 2"); break;
     case NSK_IOPT_FAULT_INJECT:
       h->fault_inject = (int)v;
       h->ctx.mgs_fault = (h->fault_inject & 4) != 0;
       break;
-    case NSK_OPT_TRI_LINE_GROUPS:
-      if (v != 0.0 && v != 1.0 && v != 2.0) throw Error(-61, "NSK_OPT_TRI_LINE_GROUPS: 0, 1 or 2");
-      h->line_groups = (int)v;
-      break;
-    case NSK_OPT_MASS_ORDERING:
-      if (v != -1.0 && v != 0.0 && v != 1.0) throw Error(-61, "NSK_OPT_MASS_ORDERING: -1, 0 or 1");
-      h->mp_ordering = (int)v;
-      break;
+    case NSK_OPT_TRI_LINE_GROUPS: h->line_groups = one_of(v, {0, 1, 2}, "NSK_OPT_TRI_LINE_GROUPS: 0, 1 or 2"); break;
+    case NSK_OPT_MASS_ORDERING: h->mp_ordering = one_of(v, {-1, 0, 1}, "NSK_OPT_MASS_ORDERING: -1, 0 or 1"); break;
     case NSK_IOPT_GROUP_U:
-    case NSK_IOPT_GROUP_P:
+    case NSK_IOPT_GROUP_P:   // (a range, not a list: 1.5 is taken as 1, as it always was)
       if (v < 1.0 || v > (double)kTriGroupMax) throw Error(-61, "line-group size: 1 .. 3");
       (opt == NSK_IOPT_GROUP_U ? h->group_u : h->group_p) = (int)v;
       break;
     case NSK_IOPT_FUSED_MGS: h->ctx.fused_mgs = v != 0.0; break;
-    case NSK_IOPT_GS_ONE_LAUNCH:
-      if (v != 0.0 && v != 1.0 && v != 2.0) throw Error(-61, "one-launch Gram-Schmidt sweeps: 0, 1 or 2");
-      h->ctx.gs_one_launch = (int)v;
-      break;
-    case NSK_IOPT_FGMRES_SKIP_UNUSED:
-      if (v != 0.0 && v != 1.0) throw Error(-61, "NSK_IOPT_FGMRES_SKIP_UNUSED: 0 or 1");
-      h->skip_unused = v != 0.0;
-      break;
+    case NSK_IOPT_GS_ONE_LAUNCH: h->ctx.gs_one_launch = one_of(v, {0, 1, 2}, "one-launch Gram-Schmidt sweeps: 0, 1 or 2"); break;
+    case NSK_IOPT_FGMRES_SKIP_UNUSED: h->skip_unused = one_of(v, {0, 1}, "NSK_IOPT_FGMRES_SKIP_UNUSED: 0 or 1") != 0; break;
     case NSK_IOPT_OVERLAP_HALO: h->overlap_halo = v != 0.0; break;
     case NSK_IOPT_TINY_BYTES: h->tF.tiny_bytes = h->tMp.tiny_bytes = h->tS.tiny_bytes = v; break;
     case NSK_OPT_BSR_VELOCITY: h->use_bsr = v != 0.0; break;
-    case NSK_OPT_VELOCITY_AMG: h->velocity_amg = v != 0.0; break;
+    case NSK_OPT_VELOCITY_AMG: req.velocity_amg = v != 0.0; break;
     case NSK_IOPT_TIMEOP_BETWEEN: h->timeop_between = (int)v; break;
     case NSK_IOPT_INDEX16:
       h->index16 = v != 0.0;
@@ -237,54 +231,23 @@ int nsk_set_option(nsk_handle h, int opt, double v) {
       h->tF_ok = h->tS_ok = h->tMp_ok = false;
       break;
     case NSK_OPT_BLAS1_PAIRS:
-      if (v != -1.0 && v != 0.0 && v != 1.0) throw Error(-61, "NSK_OPT_BLAS1_PAIRS: -1, 0 or 1");
-      h->blas1_pairs = (int)v;
+      h->blas1_pairs = one_of(v, {-1, 0, 1}, "NSK_OPT_BLAS1_PAIRS: -1, 0 or 1");
       h->ctx.ws.pairs = v < 0.0 ? (h->variant == 0) : (int)v;
       break;
-    case NSK_OPT_SCHUR_SIGN:
-      if (v != 1.0 && v != -1.0) throw Error(-61, "NSK_OPT_SCHUR_SIGN: +1 or -1");
-      h->schur_sign = (int)v;
-      break;
-    case NSK_OPT_FACTOR_PRECISION:
-      if (v != 64.0 && v != 32.0) throw Error(-61, "NSK_OPT_FACTOR_PRECISION: 64 or 32");
-      h->factor_precision = (int)v;
-      break;
-    case NSK_OPT_INNER_MATRIX_PRECISION:
-      if (v != 64.0 && v != 32.0) throw Error(-61, "NSK_OPT_INNER_MATRIX_PRECISION: 64 or 32");
-      h->inner_matrix_precision = (int)v;
-      break;
-    case NSK_OPT_INNER_BASIS_PRECISION:
-      if (v != 64.0 && v != 32.0) throw Error(-61, "NSK_OPT_INNER_BASIS_PRECISION: 64 or 32");
-      h->inner_basis_precision = (int)v;
-      break;
-    case NSK_OPT_AMG_PRECISION:
-      if (v != 64.0 && v != 32.0) throw Error(-61, "NSK_OPT_AMG_PRECISION: 64 or 32");
-      h->amg_precision = (int)v;
-      break;
-    case NSK_OPT_INNER_MATRIX_FREE_F:
-      if (v != 0.0 && v != 1.0) throw Error(-61, "NSK_OPT_INNER_MATRIX_FREE_F: 0 or 1");
-      h->matrix_free_f = (int)v;
-      break;
-    case NSK_OPT_SCHUR_AMG:
-      if (v != 0.0 && v != 1.0) throw Error(-61, "NSK_OPT_SCHUR_AMG: 0 or 1");
-      h->schur_amg = (int)v;
-      break;
-    case NSK_OPT_ASIMPLE_VELOCITY_AMG:
-      if (v != 0.0 && v != 1.0) throw Error(-61, "NSK_OPT_ASIMPLE_VELOCITY_AMG: 0 or 1");
-      h->asimple_velocity_amg = (int)v;
-      break;
-    case NSK_IOPT_AMG_FUSED_CHEBY:
-      if (v != -1.0 && v != 0.0 && v != 1.0) throw Error(-61, "NSK_IOPT_AMG_FUSED_CHEBY: -1, 0 or 1");
-      h->amg_fused_cheby = (int)v;
-      break;
+    case NSK_OPT_SCHUR_SIGN: h->schur_sign = one_of(v, {1, -1}, "NSK_OPT_SCHUR_SIGN: +1 or -1"); break;
+    case NSK_OPT_FACTOR_PRECISION: req.factor_precision = one_of(v, {64, 32}, "NSK_OPT_FACTOR_PRECISION: 64 or 32"); break;
+    case NSK_OPT_INNER_MATRIX_PRECISION: req.inner_matrix_precision = one_of(v, {64, 32}, "NSK_OPT_INNER_MATRIX_PRECISION: 64 or 32"); break;
+    case NSK_OPT_INNER_BASIS_PRECISION: req.inner_basis_precision = one_of(v, {64, 32}, "NSK_OPT_INNER_BASIS_PRECISION: 64 or 32"); break;
+    case NSK_OPT_AMG_PRECISION: req.amg_precision = one_of(v, {64, 32}, "NSK_OPT_AMG_PRECISION: 64 or 32"); break;
+    case NSK_OPT_INNER_MATRIX_FREE_F: req.matrix_free_f = one_of(v, {0, 1}, "NSK_OPT_INNER_MATRIX_FREE_F: 0 or 1"); break;
+    case NSK_OPT_SCHUR_AMG: req.schur_amg = one_of(v, {0, 1}, "NSK_OPT_SCHUR_AMG: 0 or 1"); break;
+    case NSK_OPT_ASIMPLE_VELOCITY_AMG: req.asimple_velocity_amg = one_of(v, {0, 1}, "NSK_OPT_ASIMPLE_VELOCITY_AMG: 0 or 1"); break;
+    case NSK_IOPT_AMG_FUSED_CHEBY: req.amg_fused_cheby = one_of(v, {-1, 0, 1}, "NSK_IOPT_AMG_FUSED_CHEBY: -1, 0 or 1"); break;
     case NSK_IOPT_TRI_X_LAYOUT:
       h->x_layout_mode = v == 0.0 ? 0 : 2;
       h->tF_ok = false;
       break;
-    case NSK_OPT_INNER_FUSED_GS:
-      if (v != 0.0 && v != 1.0 && v != 2.0) throw Error(-61, "NSK_OPT_INNER_FUSED_GS: 0, 1 or 2");
-      h->inner_fused_gs = (int)v;
-      break;
+    case NSK_OPT_INNER_FUSED_GS: h->inner_fused_gs = one_of(v, {0, 1, 2}, "NSK_OPT_INNER_FUSED_GS: 0, 1 or 2"); break;
     case NSK_OPT_OUTER_FUSED_GS: h->outer_fused_gs = v != 0.0; break;
     case NSK_OPT_CG_SINGLE_REDUCTION: h->cg_fused = v != 0.0; break;
     default: throw Error(-61, "nsk_set_option: unknown option");

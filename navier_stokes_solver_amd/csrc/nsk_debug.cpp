@@ -704,6 +704,20 @@ int nsk_debug_amg_spmv_form2(int blk_ok, int stream_ok, int amg32, int use_bsr, 
   return (int)amg_spmv_form(blk_ok != 0, stream_ok != 0, amg32 != 0, use_bsr != 0, mode, aligned16 != 0, blk_residual != 0);
 }
 
+int nsk_debug_env_parse(int kind, const char *text) {   // nsk_internal.h
+  return kind == 0 ? parse_env_precision(text) : kind == 1 ? parse_env_switch(text) : -2;
+}
+
+int nsk_debug_setup_plan(const int *req9, const int *env8, int type, int variant, int *out12) {   // nsk_internal.h
+  const SetupRequest req = {req9[0], req9[1], req9[2], req9[3], req9[4], req9[5], req9[6], req9[7], req9[8]};
+  const SetupEnv env = {env8[0], env8[1], env8[2], env8[3], env8[4], env8[5], env8[6], env8[7]};
+  const SetupPlan p = resolve_setup(req, env, type, variant);
+  const int out[12] = {p.factor32, p.amg_bits_F, p.want_amgF, p.fused_cheby, p.want_amgS, p.amg_bits_S,
+                       p.inner32,  p.matfree,    p.basis32,   p.kindF,       p.kindP,     p.velocity_amg_wanted};
+  std::copy(out, out + 12, out12);
+  return 12;
+}
+
 int nsk_debug_amg_fused(nsk_handle h, int64_t *out1) {   // nsk_internal.h
   *out1 = h->amg_active ? h->amgF.fused_launches : 0;
   return 0;

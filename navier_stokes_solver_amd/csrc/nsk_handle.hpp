@@ -1,5 +1,7 @@
 // nsk_handle.hpp — the handle behind include/nsk.h (struct nsk_handle_s), the timing helpers it uses and the macros every
-// entry point opens and closes with.  Included by the four files that implement the handle and the C ABI:
+// entry point opens and closes with; in front of the handle, what a set-up takes of its options: the one reader of their
+// environment overrides (setup_env) and the resolver (resolve_setup).  Included by the four files that implement the handle
+// and the C ABI:
 //   nsk_precond.cpp        the block preconditioners and the outer solve (H::setup, H::prec_vmult, H::solve_*)
 //   nsk_capi.cpp           the public ABI of include/nsk.h
 //   nsk_capi_assembly.cpp  its device-assembly group (nsk_assembly_*, nsk_state_*, nsk_assemble, nsk_forces*, nsk_record_*)
@@ -106,6 +108,81 @@ inline bool fused_row_plan(const Csr &F, const Csr &Bt, std::vector<int> &rb) {
   return build_rowblocks(F.h_rowptr.data(), Bt.h_rowptr.data(), F.n_rows, kStreamNnz, nullptr, rb);
 }
 
+// ================================================================== what a set-up takes of the options and the environment
+// The environment overrides of the set-up's options (A/B runs with unchanged callers): two parsers of the text alone.
+// Precision: atoi, 32 or 64 give that value, anything else — no text included — 0, "unset"
+inline int parse_env_precision(const char *e) {
+  const int v = e ? std::atoi(e) : 0;
+  return v == 32 || v == 64 ? v : 0;
+}
+// Switch: exactly "0" or "1"; anything else — no text included — -1, "unset"
+inline int parse_env_switch(const char *e) {
+  if (e && e[0] == '0' && !e[1]) return 0;
+  if (e && e[0] == '1' && !e[1]) return 1;
+  return -1;
+}
+struct SetupEnv {
+  int factor_precision, inner_matrix_precision, inner_basis_precision, amg_precision;   // 0 unset, 32, 64
+  int matrix_free_f, schur_amg, asimple_velocity_amg, amg_fused_cheby;                  // -1 unset, 0, 1
+};
+// The only reader of these eight variables: once per process (a function-local static: rank threads set up concurrently)
+inline const SetupEnv &setup_env() {
+  static const SetupEnv env = {parse_env_precision(std::getenv("NSK_FACTOR_PRECISION")),
+                               parse_env_precision(std::getenv("NSK_INNER_MATRIX_PRECISION")),
+                               parse_env_precision(std::getenv("NSK_INNER_BASIS_PRECISION")),
+                               parse_env_precision(std::getenv("NSK_AMG_PRECISION")),
+                               parse_env_switch(std::getenv("NSK_INNER_MATRIX_FREE_F")),
+                               parse_env_switch(std::getenv("NSK_SCHUR_AMG")),
+                               parse_env_switch(std::getenv("NSK_ASIMPLE_VELOCITY_AMG")),
+                               parse_env_switch(std::getenv("NSK_AMG_FUSED_CHEBY"))};
+  return env;
+}
+// What the caller asked for (nsk_set_option writes here); the first eight in SetupEnv's order
+struct SetupRequest {
+  int factor_precision = 64;         // NSK_OPT_FACTOR_PRECISION: 64, or 32 (single-precision off-diagonal values of the split halves)
+  int inner_matrix_precision = 64;   // NSK_OPT_INNER_MATRIX_PRECISION: 64, or 32 (fp32 values of F, S, M_p in the inner solves)
+  int inner_basis_precision = 64;    // NSK_OPT_INNER_BASIS_PRECISION: 64, or 32 (fp32 Krylov basis of the inner FGMRES on F)
+  int amg_precision = 64;            // NSK_OPT_AMG_PRECISION: 64, or 32 (fp32 values of the V-cycle's A, P, R on every level)
+  int matrix_free_f = 0;             // NSK_OPT_INNER_MATRIX_FREE_F
+  int schur_amg = 0;                 // NSK_OPT_SCHUR_AMG
+  int asimple_velocity_amg = 0;      // NSK_OPT_ASIMPLE_VELOCITY_AMG
+  int amg_fused_cheby = -1;          // NSK_IOPT_AMG_FUSED_CHEBY: -1 fused smoother steps where that hierarchy allows them, 0, 1
+  int velocity_amg = 1;              // NSK_OPT_VELOCITY_AMG
+};
+// What one set-up of (type, variant) takes of the two: an override that is set wins, one that is unset leaves the option
+struct SetupPlan {
+  bool factor32;              // fp32 off-diagonal values of the three factors
+  int amg_bits_F;             // 32 only where this set-up wants a hierarchy of F and the precision resolves to 32
+  bool want_amgF;             // the V-cycle on F in place of ILU(F): stationary aSIMPLE only
+  bool fused_cheby;           // its smoother steps in the residual products' epilogues (the option's -1 counts as on)
+  bool want_amgS;             // the V-cycle on S in place of ILU(S): stationary aSIMPLE only
+  int amg_bits_S;             // (one knob for "operators a V-cycle multiplies by": NSK_OPT_AMG_PRECISION governs S's too)
+  bool inner32;               // fp32 values of the inner solves' matrices
+  bool matfree;               // matrix-free F in the inner FGMRES
+  bool basis32;               // fp32 basis of the inner FGMRES on F
+  // kinds: blockDiagonal stationary = SSOR/SSOR, unsteady = ILU/ILU; blockTriangular = (AMG->ILU)/ILU; aSIMPLE = ILU/ILU
+  int kindF, kindP;
+  // PreconditionBlockTriangular, stationary: preconditioner_velocity is an AMG (NSSolverStationary.hpp:225,231)
+  bool velocity_amg_wanted;
+};
+inline SetupPlan resolve_setup(const SetupRequest &req, const SetupEnv &env, int type, int variant) {
+  const bool stationary_asimple = type == 2 && variant == 0;
+  const int amg_precision = env.amg_precision ? env.amg_precision : req.amg_precision;
+  SetupPlan p;
+  p.factor32 = (env.factor_precision ? env.factor_precision : req.factor_precision) == 32;
+  p.velocity_amg_wanted = type == 1 && variant == 0 && req.velocity_amg != 0;
+  p.want_amgF = stationary_asimple && (env.asimple_velocity_amg >= 0 ? env.asimple_velocity_amg : req.asimple_velocity_amg) == 1;
+  p.amg_bits_F = (p.velocity_amg_wanted || p.want_amgF) && amg_precision == 32 ? 32 : 64;
+  p.fused_cheby = p.want_amgF && (env.amg_fused_cheby >= 0 ? env.amg_fused_cheby : req.amg_fused_cheby) != 0;
+  p.want_amgS = stationary_asimple && (env.schur_amg >= 0 ? env.schur_amg : req.schur_amg) == 1;
+  p.amg_bits_S = p.want_amgS && amg_precision == 32 ? 32 : 64;
+  p.inner32 = (env.inner_matrix_precision ? env.inner_matrix_precision : req.inner_matrix_precision) == 32;
+  p.matfree = (env.matrix_free_f >= 0 ? env.matrix_free_f : req.matrix_free_f) == 1;
+  p.basis32 = (env.inner_basis_precision ? env.inner_basis_precision : req.inner_basis_precision) == 32;
+  p.kindF = p.kindP = (type == 0 && variant == 0) ? 1 : 0;
+  return p;
+}
+
 struct nsk_handle_s {
   Ctx ctx;
   EventSampler sampler;
@@ -153,13 +230,12 @@ struct nsk_handle_s {
   int prec_type = -1, variant = 0;
   double alpha = 0.5;
   TriSolve tF, tMp, tS;
+  SetupRequest req;         // the options a set-up resolves against the environment (resolve_setup)
   Amg amgF;                 // velocity AMG of the stationary block-triangular preconditioner
-  int velocity_amg = 1;     // NSK_OPT_VELOCITY_AMG
   // NSK_OPT_SCHUR_AMG: in the stationary aSIMPLE set-up one V-cycle of amgS, built from S at every set-up,
   // preconditions the inner CG on S instead of ILU(S).  schur_amg_active: the current set-up runs it — tS is then neither
   // analysed nor factorised and tP is null; every reader of tP asks schur_amg_active first
   Amg amgS;
-  int schur_amg = 0;
   bool schur_amg_active = false, schur_amg_warned = false;
   void pressure_apply_sampled(const double *b, double *x) {   // profile class 21: ILU(S) / ILU(M_p) / SGS, or the cycle on S
     if (!schur_amg_active) return tri_apply_sampled(*tP, 21, b, x);
@@ -170,8 +246,6 @@ struct nsk_handle_s {
   // preconditions the inner FGMRES on F instead of ILU(F).  asimple_amg_active: the current set-up runs it — amg_active is
   // then true as well (every reader of the velocity slot behaves as under the velocity AMG of blockTriangular) and tF is
   // neither analysed nor factorised nor held
-  int asimple_velocity_amg = 0;
-  int amg_fused_cheby = -1;   // NSK_IOPT_AMG_FUSED_CHEBY: -1 fused smoother steps where that hierarchy allows them, 0, 1
   bool asimple_amg_active = false, asimple_amg_warned = false;
   void velocity_apply_sampled(const double *b, double *x) {   // profile class 20 while asimple_amg_active: the cycle on F
     Sampled smp(sampler, 20, s());
@@ -191,12 +265,9 @@ struct nsk_handle_s {
   }
   int schur_sign = 1;       // NSK_OPT_SCHUR_SIGN: +1 the reference's S = B D^-1 Bt, -1 the negated (SIMPLE's) one
   int blas1_pairs = -1;     // NSK_OPT_BLAS1_PAIRS: -1 by variant (stationary on, unsteady off), 0, 1
-  int factor_precision = 64;   // NSK_OPT_FACTOR_PRECISION: 64, or 32 (single-precision off-diagonal values of the split halves)
-  int inner_matrix_precision = 64;   // NSK_OPT_INNER_MATRIX_PRECISION: 64, or 32 (fp32 values of F, S, M_p in the inner solves)
-  int amg_precision = 64;            // NSK_OPT_AMG_PRECISION: 64, or 32 (fp32 values of the V-cycle's A, P, R on every level)
-  int inner_basis_precision = 64;    // NSK_OPT_INNER_BASIS_PRECISION: 64, or 32 (fp32 Krylov basis of the inner FGMRES on F)
-  // what the last set-up took of it (the option or NSK_INNER_BASIS_PRECISION), and the fp32 vectors, kept from solve to
-  // solve.  Whether a solve reads them is SolverFGMRES::reads_f32_basis: the fused sweeps in their pair forms
+  // what the last set-up took of NSK_OPT_INNER_BASIS_PRECISION (the option or NSK_INNER_BASIS_PRECISION), and the fp32
+  // vectors, kept from solve to solve.  Whether a solve reads them is SolverFGMRES::reads_f32_basis: the fused sweeps in
+  // their pair forms
   bool basis32_wanted = false;
   BasisPool32 basis32_u;
   int inner_basis_width() const {
@@ -313,8 +384,7 @@ struct nsk_handle_s {
     long rec_points = 0;
     DBuf<int> rec_unode, rec_pdof;          // per point: velocity node and pressure DoF, owned or ghost
   } asmd;
-  int matrix_free_f = 0;        // NSK_OPT_INNER_MATRIX_FREE_F
-  bool matfree_wanted = false;  // what the last set-up took of it (the option or NSK_INNER_MATRIX_FREE_F)
+  bool matfree_wanted = false;  // what the last set-up took of NSK_OPT_INNER_MATRIX_FREE_F (the option or the environment)
   bool matfree_warned = false;
   // why a handle that wants the matrix-free product multiplies by the assembled block (nullptr: it does not)
   const char *matfree_obstacle() const {
@@ -539,7 +609,16 @@ struct nsk_handle_s {
     tF.use_stream = tMp.use_stream = tS.use_stream = use_stream != 0;
   }
   void schur_symbolic();
+  // the set-up and its steps, in the order they run (nsk_precond.cpp)
   void setup(int type, int variant_, double alpha_);
+  void setup_hierarchies(const SetupPlan &plan);
+  void setup_velocity_factor(const SetupPlan &plan, int key);
+  void analyse_S();
+  void setup_schur(const SetupPlan &plan, int key);
+  void setup_schur_hierarchy();
+  void setup_mass(const SetupPlan &plan, int key);
+  void setup_f32_copies(const SetupPlan &plan);
+  void check_f32_overflow();
   void prec_vmult(DVec &dst, const DVec &src);
   int solve_once(int solver, double tol, int max_iter, int *iters, double *final_res);
   int solve_resident(int solver, double tol, int max_iter, int *iters, double *final_res);

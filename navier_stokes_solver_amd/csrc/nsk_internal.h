@@ -322,6 +322,16 @@ int nsk_debug_schur_amg_forms(struct nsk_handle_s *h, int64_t *out5);
  * for every combination of the others; 1 gives 3 (blocked) exactly where amg32 = 0, mode = 2, blk_ok, use_bsr and aligned16
  * all hold, and that value everywhere else. */
 int nsk_debug_amg_spmv_form2(int blk_ok, int stream_ok, int amg32, int use_bsr, int mode, int aligned16, int blk_residual);
+/* The two parsers of the set-up's environment overrides (nsk_handle.hpp) on the caller's text, which may be null: no handle,
+ * no device, no environment read.  kind 0, a precision (NSK_FACTOR_PRECISION and its kin): 32 or 64, else 0 = unset;
+ * kind 1, a switch (NSK_SCHUR_AMG and its kin): 0 or 1, else -1 = unset.  Any other kind: -2. */
+int nsk_debug_env_parse(int kind, const char *text);
+/* What a set-up of (type, variant) takes of the options and the environment (resolve_setup, nsk_handle.hpp) on bare
+ * integers: no handle, no device, no environment read.  req9: factor_precision, inner_matrix_precision,
+ * inner_basis_precision, amg_precision, matrix_free_f, schur_amg, asimple_velocity_amg, amg_fused_cheby, velocity_amg as
+ * nsk_set_option stores them; env8: the first eight as the parsers return them.  out12: factor32, amg_bits_F, want_amgF,
+ * fused_cheby, want_amgS, amg_bits_S, inner32, matfree, basis32, kindF, kindP, velocity_amg_wanted.  Returns 12. */
+int nsk_debug_setup_plan(const int *req9, const int *env8, int type, int variant, int *out12);
 /* Fused smoother steps the V-cycles of the velocity hierarchy have launched since it was built; 0 without one. */
 int nsk_debug_amg_fused(struct nsk_handle_s *h, int64_t *out1);
 /* ONE fused Chebyshev step alone (nsk::spmv_blk22_cheby) on the caller's CSR matrix A (as nsk_debug_spmv takes

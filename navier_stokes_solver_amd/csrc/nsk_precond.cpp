@@ -110,14 +110,10 @@ void H::setup(int type, int variant_, double alpha_) {
   drop_pending();   // a fresh preconditioner object: the application the last solve left over fed the old one's state
   ctx.ws.pairs = blas1_pairs < 0 ? (variant_ == 0) : blas1_pairs;   // NSK_OPT_BLAS1_PAIRS
   push_tri_options();
-  // storage precision of the factors' off-diagonal values; NSK_FACTOR_PRECISION=32 / 64 overrides the option (A/B
-  // measurements with unchanged callers), any other value is ignored.  numeric() reallocates the halves when it changes.
-  static const int env_precision = [] {
-    const char *e = std::getenv("NSK_FACTOR_PRECISION");
-    const int v = e ? std::atoi(e) : 0;
-    return v == 32 || v == 64 ? v : 0;
-  }();
-  tF.want_f32 = tS.want_f32 = tMp.want_f32 = (env_precision ? env_precision : factor_precision) == 32;
+  // what this set-up takes of the options and their environment overrides (nsk_handle.hpp: resolve_setup)
+  const SetupPlan plan = resolve_setup(req, setup_env(), type, variant_);
+  // (numeric() reallocates the halves when the storage precision of the factors' off-diagonal values changes)
+  tF.want_f32 = tS.want_f32 = tMp.want_f32 = plan.factor32;
   // working-vector layout of the blocked velocity factor: colour-ordered whenever it runs single-launch (its
   // per-level kernels only know the caller's order).  The scalar factors always solve on colour-ordered vectors.
   const int f_layout = (x_layout_mode != 0 && sync_free_mode == 2) ? 1 : 0;
@@ -128,46 +124,36 @@ void H::setup(int type, int variant_, double alpha_) {
   alpha = alpha_;
   const int key = ((((tri_ordering * 1000 + subdomains) * 2 + (xy(0) ? 1 : 0)) * 2 + (xy(1) ? 1 : 0)) * 100 + group_u * 10 + group_p) * 2 +
                   mass_ordering(type, variant_);
+  setup_hierarchies(plan);
+  setup_velocity_factor(plan, key);
+  if (type == 2) setup_schur(plan, key);
+  else setup_mass(plan, key);
+  setup_f32_copies(plan);
+  check_f32_overflow();
+  // fp32 basis of the inner FGMRES on F: a set-up that does not want the vectors frees them
+  basis32_wanted = plan.basis32;
+  if (inner_basis_width() != 4) basis32_u.destroy();
+  setup_ms = wall_ms() - t0;
+}
+
+// A set-up the device kernels of a hierarchy cannot finish (-80..-85: a row of a product over their 512 columns and its
+// kin) leaves the ILU factor in charge; -48 and HIP errors are errors
+static bool amg_kernels_gave_up(const Error &e) { return e.code <= -80 && e.code >= -85; }
+
+// What the two hierarchies take of the plan; the one of F in stationary aSIMPLE is built here, with its fallback
+void H::setup_hierarchies(const SetupPlan &plan) {
   Csr &F = blk[NSK_BLK_F];
-  // kinds: blockDiagonal stationary = SSOR/SSOR, unsteady = ILU/ILU; blockTriangular = (AMG->ILU)/ILU; aSIMPLE = ILU/ILU
-  const int kindF = (type == 0 && variant == 0) ? 1 : 0;
-  const int kindP = (type == 0 && variant == 0) ? 1 : 0;
-  // PreconditionBlockTriangular, stationary: preconditioner_velocity is an AMG (NSSolverStationary.hpp:225,231)
-  amg_active = type == 1 && variant == 0 && velocity_amg != 0;
+  amg_active = plan.velocity_amg_wanted;
   amg_pending = false;
-  // fp32 storage of the V-cycle's operators; NSK_AMG_PRECISION=32 / 64 overrides the option (A/B measurements with
-  // unchanged callers), any other value is ignored.  The hierarchy converts when it is built (Amg::setup)
-  static const int env_amg = [] {
-    const char *e = std::getenv("NSK_AMG_PRECISION");
-    const int v = e ? std::atoi(e) : 0;
-    return v == 32 || v == 64 ? v : 0;
-  }();
-  // the V-cycle on F in place of ILU(F) in stationary aSIMPLE; NSK_ASIMPLE_VELOCITY_AMG=0 / 1 overrides the
-  // option (A/B runs with unchanged callers), any other value counts as unset.  Every other set-up ignores both
-  static const int env_asimple_amg = [] {
-    const char *e = std::getenv("NSK_ASIMPLE_VELOCITY_AMG");
-    if (e && e[0] == '0' && !e[1]) return 0;
-    if (e && e[0] == '1' && !e[1]) return 1;
-    return -1;
-  }();
-  // (NSK_AMG_FUSED_CHEBY=0 / 1: the same for NSK_IOPT_AMG_FUSED_CHEBY, so that the benchmark can run both)
-  static const int env_fused = [] {
-    const char *e = std::getenv("NSK_AMG_FUSED_CHEBY");
-    if (e && e[0] == '0' && !e[1]) return 0;
-    if (e && e[0] == '1' && !e[1]) return 1;
-    return -1;
-  }();
-  const bool want_amgF = type == 2 && variant == 0 && (env_asimple_amg >= 0 ? env_asimple_amg : asimple_velocity_amg) == 1;
   asimple_amg_active = false;
-  amgF.value_bits = (amg_active || want_amgF) && (env_amg ? env_amg : amg_precision) == 32 ? 32 : 64;
+  // (fp32 storage of the V-cycle's operators: the hierarchy converts when it is built, Amg::setup)
+  amgF.value_bits = plan.amg_bits_F;
   amgF.use_bsr = use_bsr != 0;
   // level 0 on F's node blocks, and the smoother steps in those products' epilogues: this hierarchy alone
-  amgF.blk_residual = want_amgF;
-  amgF.fused_cheby = want_amgF && (env_fused >= 0 ? env_fused : amg_fused_cheby) != 0;
-  if (want_amgF) {
-    // Built here and not on first use: it can fail, and ILU(F) must then still be possible.  A set-up the device kernels
-    // cannot finish (-80..-85: a row of a product over their 512 columns and its kin) leaves ILU(F) in charge, said once
-    // per handle; -48 and HIP errors are errors
+  amgF.blk_residual = plan.want_amgF;
+  amgF.fused_cheby = plan.fused_cheby;
+  if (plan.want_amgF) {
+    // Built here and not on first use: it can fail, and ILU(F) must then still be possible — said once per handle
     Phase ph("AMG hierarchy of F (device)");
     try {
       amgF.setup(&ctx, F, sub_offsets(0));
@@ -177,7 +163,7 @@ void H::setup(int type, int variant_, double alpha_) {
       F.amg32 = 0;
       amgF.blk_residual = amgF.fused_cheby = false;
       amgF.value_bits = 64;
-      if (e.code > -80 || e.code < -85) { prec_type = -1; throw; }
+      if (!amg_kernels_gave_up(e)) { prec_type = -1; throw; }
       if (!asimple_amg_warned) {
         asimple_amg_warned = true;
         fprintf(stderr, "[nsk] warning: NSK_OPT_ASIMPLE_VELOCITY_AMG = 1, but the hierarchy of F cannot be built (%s): ILU(F) preconditions the inner FGMRES on F\n",
@@ -186,176 +172,177 @@ void H::setup(int type, int variant_, double alpha_) {
     }
     if (asimple_amg_active) drop_velocity_factor();
   }
-  // the V-cycle on S in place of ILU(S); NSK_SCHUR_AMG=0 / 1 overrides the option (A/B runs with unchanged
-  // callers), any other value counts as unset.  Stationary aSIMPLE only: every other set-up ignores it
-  static const int env_schur_amg = [] {
-    const char *e = std::getenv("NSK_SCHUR_AMG");
-    if (e && e[0] == '0' && !e[1]) return 0;
-    if (e && e[0] == '1' && !e[1]) return 1;
-    return -1;
-  }();
-  const bool want_amgS = type == 2 && variant == 0 && (env_schur_amg >= 0 ? env_schur_amg : schur_amg) == 1;
+  // S's hierarchy is built where S is formed (setup_schur); a set-up that does not want it frees it here, before the
+  // velocity factor takes its storage
   schur_amg_active = false;
-  // (one knob for "operators a V-cycle multiplies by": NSK_OPT_AMG_PRECISION governs this hierarchy too)
-  amgS.value_bits = want_amgS && (env_amg ? env_amg : amg_precision) == 32 ? 32 : 64;
+  amgS.value_bits = plan.amg_bits_S;
   amgS.use_bsr = false;
   amgS.one_sign_diag = true;
-  if (!want_amgS) amgS.release();
-  if (asimple_amg_active) {
-    // (the hierarchy stands; no factor of F.  S's pattern and factor, where ILU(S) is wanted, are formed below on this
-    // thread: the side thread exists to overlap F's analysis, of which there is none)
-  } else if (amg_active) {
+  if (!plan.want_amgS) amgS.release();
+}
+
+// "Analyse a factor unless it is analysed under this key": true when `analyse` ran
+template <class Analyse>
+static bool analyse_unless_held(bool &ok, int &held, int key, Analyse analyse) {
+  if (ok && held == key) return false;
+  analyse();
+  ok = true;
+  held = key;
+  return true;
+}
+
+void H::analyse_S() { tS.analyze(&ctx, blk[NSK_BLK_S], 0, tri_ordering, sub_offsets(1), false, xy(1), group_p); }
+
+// The velocity slot: the hierarchy that stands, the one built on first use, or ILU(F) / SGS(F) analysed and factorised
+void H::setup_velocity_factor(const SetupPlan &plan, int key) {
+  // (asimple_amg_active: the hierarchy stands; no factor of F.  S's pattern and factor, where ILU(S) is wanted, are formed
+  // in setup_schur on this thread: the side thread exists to overlap F's analysis, of which there is none)
+  if (asimple_amg_active) return;
+  if (amg_active) {
     amgF.clear();
     amg_pending = true;
-  } else {
-    amgF.release();
-    // First aSIMPLE set-up of a pattern: the Schur pattern and the analysis of its factor need nothing of F's analysis —
-    // a second host thread does them meanwhile (both are host-side integer work with serial stretches: 1.7 s next to
-    // 3.3 s at 1200x400 instead of behind them)
-    std::thread side;
-    std::exception_ptr side_err;
-    bool side_done_s = false;
-    // (not under NSK_OPT_SCHUR_AMG: S's factor is not analysed then, and the pattern is formed below)
-    if (type == 2 && !want_amgS && (!tF_ok || tF_key != key) && (!tS_ok || tS_key != key)) {
-      side = std::thread([&] {
-        try {
-          (void)hipSetDevice(ctx.device);
-          if (!s_symbolic) {
-            Phase ph("Schur pattern (host, side thread)");
-            schur_symbolic();
-          }
-          Phase ph("analyse S factor (host, side thread)");
-          tS.analyze(&ctx, blk[NSK_BLK_S], 0, tri_ordering, sub_offsets(1), false, xy(1), group_p);
-          side_done_s = true;
-        } catch (...) {
-          side_err = std::current_exception();
-        }
-      });
-    }
-    struct Joiner {   // (F's analysis may throw: never leave the scope with the thread running)
-      std::thread &t;
-      ~Joiner() { if (t.joinable()) t.join(); }
-    } joiner{side};
-    if (!tF_ok || tF_key != key) {
-      Phase ph("analyse F factor (host)");
-      tF.analyze(&ctx, F, kindF, tri_ordering, sub_offsets(0), use_bsr && F.blk_ok && F.blk_R == 2 && F.blk_C == 2, xy(0),
-                 group_u);
-      tF_ok = true;
-      tF_key = key;
-    }
-    tF.kind = kindF;
-    if (side.joinable()) side.join();
-    if (side_err) std::rethrow_exception(side_err);
-    if (side_done_s) { tS_ok = true; tS_key = key; }
-    {
-      Phase ph("factorise F (device)");
-      tF.numeric(F.val.p);
-      if (verbose()) ctx.sync();
-    }
+    return;
   }
-  if (type == 2) {
-    if (!s_symbolic) {
-      Phase ph("Schur pattern (host)");
-      schur_symbolic();
-    }
-    if (!D) { D = pool_u.get(true); Dinv = pool_u.get(true); tmp_u = pool_u.get(true); }
-    if (!tmp_p) tmp_p = pool_p.get(true);
-    if (!delta_p) delta_p = pool_p.get(true);
-    if (!tmp_b) tmp_b = pool_b.get(true);
-    // D = diag(F), D^-1 (NSSolverStationary.hpp:259-264); ghosts of D^-1 feed the SpGEMM
-    extract_diag(s(), F.view(), D, Dinv);
-    halo(0, pool_u.view(Dinv));
-    Csr &S = blk[NSK_BLK_S], &B = blk[NSK_BLK_B], &Bt = blk[NSK_BLK_BT], &Btg = blk[NSK_BLK_BT_GHOST];
-    spgemm_bdbt_numeric(s(), B.view(), Dinv, Dinv + n_u(), Bt.view(), Btg.present ? Btg.view() : Bt.view(), S.rowptr.p,
-                        S.col.p, S.val.p, S.n_rows, std::max(1, s_max_row));
-    if (schur_sign < 0) vec_scale(s(), (int)S.nnz, sref(-1.0), S.val.p);   // opt-in deviation (nsk.h: NSK_OPT_SCHUR_SIGN)
-    ++S.values_version;
-    tP = nullptr;
-    if (want_amgS) {
-      // S changes with every set-up: the hierarchy is rebuilt every time, here and not on first use (the CG on S runs in
-      // every application).  A set-up the device kernels cannot finish — a row of a product over their 512 columns, a
-      // diagonal of S that is not of one sign — leaves ILU(S) in charge, said once per handle
-      Phase ph("AMG hierarchy of S (device)");
+  amgF.release();
+  Csr &F = blk[NSK_BLK_F];
+  // First aSIMPLE set-up of a pattern: the Schur pattern and the analysis of its factor need nothing of F's analysis —
+  // a second host thread does them meanwhile (both are host-side integer work with serial stretches: 1.7 s next to
+  // 3.3 s at 1200x400 instead of behind them)
+  std::thread side;
+  std::exception_ptr side_err;
+  bool side_done_s = false;
+  // (not under NSK_OPT_SCHUR_AMG: S's factor is not analysed then, and the pattern is formed in setup_schur)
+  if (prec_type == 2 && !plan.want_amgS && (!tF_ok || tF_key != key) && (!tS_ok || tS_key != key)) {
+    side = std::thread([&] {
       try {
-        amgS.setup(&ctx, S, sub_offsets(1));
-        schur_amg_active = true;
-      } catch (const Error &e) {
-        amgS.release();
-        S.amg32 = 0;
-        if (e.code > -80 || e.code < -85) throw;
-        if (!schur_amg_warned) {
-          schur_amg_warned = true;
-          fprintf(stderr, "[nsk] warning: NSK_OPT_SCHUR_AMG = 1, but the hierarchy of S cannot be built (%s): ILU(S) preconditions the inner CG on S\n",
-                  e.what());
+        (void)hipSetDevice(ctx.device);
+        if (!s_symbolic) {
+          Phase ph("Schur pattern (host, side thread)");
+          schur_symbolic();
         }
+        Phase ph("analyse S factor (host, side thread)");
+        analyse_S();
+        side_done_s = true;
+      } catch (...) {
+        side_err = std::current_exception();
       }
-    }
-    if (!schur_amg_active) {
-      if (!tS_ok || tS_key != key) {
-        Phase ph("analyse S factor (host)");
-        tS.analyze(&ctx, S, 0, tri_ordering, sub_offsets(1), false, xy(1), group_p);
-        tS_ok = true;
-        tS_key = key;
-      }
-      tS.kind = 0;
-      tS.numeric(S.val.p);
-      tP = &tS;
-    }
-    // delta_p.reinit(...) in initialize(): zero
-    vec_set(s(), n_p(), delta_p, 0.0);
-  } else {
-    Csr &Mp = blk[NSK_BLK_MP];
-    if (!Mp.present) throw Error(-45, "this preconditioner needs pressure_mass.block(1,1)");
-    if (!tMp_ok || tMp_key != key) {
-      tMp.analyze(&ctx, Mp, kindP, mass_ordering(type, variant), sub_offsets(1), false, xy(1), group_p);
-      tMp_ok = true;
-      tMp_key = key;
-      mp_factored_version = -1;
-    }
-    tMp.kind = kindP;
-    if (mp_factored_version != mp_values_version || mp_factored_kind != kindP || tMp.storage_stale()) {
-      Phase ph("factorise Mp (device)");
-      tMp.numeric(Mp.val.p);
-      mp_factored_version = mp_values_version;
-      mp_factored_kind = kindP;
-    }
-    tP = &tMp;
-    if (!tmp_p) tmp_p = pool_p.get(true);
+    });
   }
-  // fp32 values of the inner solves' matrices; NSK_INNER_MATRIX_PRECISION=32 / 64 overrides the option (A/B measurements
-  // with unchanged callers), any other value is ignored.  A block without an inner solve in this set-up, or whose SpMV
-  // would not take a stream kernel, keeps no copy (and 64 frees them all).
-  static const int env_inner = [] {
-    const char *e = std::getenv("NSK_INNER_MATRIX_PRECISION");
-    const int v = e ? std::atoi(e) : 0;
-    return v == 32 || v == 64 ? v : 0;
-  }();
-  const bool inner32 = (env_inner ? env_inner : inner_matrix_precision) == 32;
-  // matrix-free F in the inner FGMRES; NSK_INNER_MATRIX_FREE_F=0 / 1 overrides the option (A/B runs with
-  // unchanged callers), any other value counts as unset
-  static const int env_matfree = [] {
-    const char *e = std::getenv("NSK_INNER_MATRIX_FREE_F");
-    if (e && e[0] == '0' && !e[1]) return 0;
-    if (e && e[0] == '1' && !e[1]) return 1;
-    return -1;
-  }();
-  matfree_wanted = (env_matfree >= 0 ? env_matfree : matrix_free_f) == 1;
+  struct Joiner {   // (F's analysis may throw: never leave the scope with the thread running)
+    std::thread &t;
+    ~Joiner() { if (t.joinable()) t.join(); }
+  } joiner{side};
+  analyse_unless_held(tF_ok, tF_key, key, [&] {
+    Phase ph("analyse F factor (host)");
+    tF.analyze(&ctx, F, plan.kindF, tri_ordering, sub_offsets(0), use_bsr && F.blk_ok && F.blk_R == 2 && F.blk_C == 2, xy(0),
+               group_u);
+  });
+  tF.kind = plan.kindF;
+  if (side.joinable()) side.join();
+  if (side_err) std::rethrow_exception(side_err);
+  if (side_done_s) { tS_ok = true; tS_key = key; }   // (written here, on the calling thread, after the join)
+  Phase ph("factorise F (device)");
+  tF.numeric(F.val.p);
+  if (verbose()) ctx.sync();
+}
+
+// aSIMPLE: S = B D^-1 Bt formed, and its preconditioner — the V-cycle of amgS, or ILU(S)
+void H::setup_schur(const SetupPlan &plan, int key) {
+  Csr &F = blk[NSK_BLK_F], &S = blk[NSK_BLK_S], &B = blk[NSK_BLK_B], &Bt = blk[NSK_BLK_BT], &Btg = blk[NSK_BLK_BT_GHOST];
+  if (!s_symbolic) {
+    Phase ph("Schur pattern (host)");
+    schur_symbolic();
+  }
+  if (!D) { D = pool_u.get(true); Dinv = pool_u.get(true); tmp_u = pool_u.get(true); }
+  if (!tmp_p) tmp_p = pool_p.get(true);
+  if (!delta_p) delta_p = pool_p.get(true);
+  if (!tmp_b) tmp_b = pool_b.get(true);
+  // D = diag(F), D^-1 (NSSolverStationary.hpp:259-264); ghosts of D^-1 feed the SpGEMM
+  extract_diag(s(), F.view(), D, Dinv);
+  halo(0, pool_u.view(Dinv));
+  spgemm_bdbt_numeric(s(), B.view(), Dinv, Dinv + n_u(), Bt.view(), Btg.present ? Btg.view() : Bt.view(), S.rowptr.p,
+                      S.col.p, S.val.p, S.n_rows, std::max(1, s_max_row));
+  if (schur_sign < 0) vec_scale(s(), (int)S.nnz, sref(-1.0), S.val.p);   // opt-in deviation (nsk.h: NSK_OPT_SCHUR_SIGN)
+  ++S.values_version;
+  tP = nullptr;
+  if (plan.want_amgS) setup_schur_hierarchy();
+  if (!schur_amg_active) {
+    analyse_unless_held(tS_ok, tS_key, key, [&] {
+      Phase ph("analyse S factor (host)");
+      analyse_S();
+    });
+    tS.kind = 0;
+    tS.numeric(S.val.p);
+    tP = &tS;
+  }
+  // delta_p.reinit(...) in initialize(): zero
+  vec_set(s(), n_p(), delta_p, 0.0);
+}
+
+// S changes with every set-up: the hierarchy is rebuilt every time, in the set-up and not on first use (the CG on S runs
+// in every application).  A set-up the device kernels cannot finish — a row of a product over their 512 columns, a
+// diagonal of S that is not of one sign — leaves ILU(S) in charge, said once per handle
+void H::setup_schur_hierarchy() {
+  Csr &S = blk[NSK_BLK_S];
+  Phase ph("AMG hierarchy of S (device)");
+  try {
+    amgS.setup(&ctx, S, sub_offsets(1));
+    schur_amg_active = true;
+  } catch (const Error &e) {
+    amgS.release();
+    S.amg32 = 0;
+    if (!amg_kernels_gave_up(e)) throw;
+    if (!schur_amg_warned) {
+      schur_amg_warned = true;
+      fprintf(stderr, "[nsk] warning: NSK_OPT_SCHUR_AMG = 1, but the hierarchy of S cannot be built (%s): ILU(S) preconditions the inner CG on S\n",
+              e.what());
+    }
+  }
+}
+
+// The block preconditioners: the factor of M_p, kept while neither its values nor its analysis change
+void H::setup_mass(const SetupPlan &plan, int key) {
+  Csr &Mp = blk[NSK_BLK_MP];
+  if (!Mp.present) throw Error(-45, "this preconditioner needs pressure_mass.block(1,1)");
+  const bool analysed = analyse_unless_held(tMp_ok, tMp_key, key, [&] {
+    tMp.analyze(&ctx, Mp, plan.kindP, mass_ordering(prec_type, variant), sub_offsets(1), false, xy(1), group_p);
+  });
+  if (analysed) mp_factored_version = -1;
+  tMp.kind = plan.kindP;
+  if (mp_factored_version != mp_values_version || mp_factored_kind != plan.kindP || tMp.storage_stale()) {
+    Phase ph("factorise Mp (device)");
+    tMp.numeric(Mp.val.p);
+    mp_factored_version = mp_values_version;
+    mp_factored_kind = plan.kindP;
+  }
+  tP = &tMp;
+  if (!tmp_p) tmp_p = pool_p.get(true);
+}
+
+// fp32 values of the inner solves' matrices.  A block without an inner solve in this set-up, or whose SpMV would not take
+// a stream kernel, keeps no copy (and 64 frees them all).
+void H::setup_f32_copies(const SetupPlan &plan) {
+  matfree_wanted = plan.matfree;
   for (int b : {(int)NSK_BLK_F, (int)NSK_BLK_MP, (int)NSK_BLK_S}) {
     Csr &A = blk[b];
     // (F while its products are matrix-free: no stored value is read, so no copy is made)
-    const bool wanted = inner32 && A.present && inner_solve_on(b) && !(b == NSK_BLK_F && matfree_in_effect());
+    const bool wanted = plan.inner32 && A.present && inner_solve_on(b) && !(b == NSK_BLK_F && matfree_in_effect());
     // the copy this block would hold: F's 2 x 2 blocks (the only shape build_blocked gives F, and the only one of the
     // blocked fp32 kernel), else the scalar values — kept where the rule gives the inner product an _f32 form for it
     A.inner32 = !wanted ? 0 : b == NSK_BLK_F ? 1 : 2;
     if (!is_f32(form_of(A, 0, true))) A.inner32 = 0;
     // (F's copies may also serve the V-cycle, level 0 being F itself: Amg::setup names them in amg32 when the hierarchy is
     // built and this loop leaves them alone meanwhile; without an fp32 AMG in this set-up nothing of it remains)
-    // (S the same way under NSK_OPT_SCHUR_AMG, where amgS.setup above has named its copy already)
+    // (S the same way under NSK_OPT_SCHUR_AMG, where amgS.setup has named its copy already)
     if (!(b == NSK_BLK_F && amgF.value_bits == 32) && !(b == NSK_BLK_S && schur_amg_active && amgS.value_bits == 32)) A.amg32 = 0;
     if (!A.inner32 && !A.amg32) { A.release_f32(); continue; }
     if (A.inner32) A.refresh_f32(s(), true);
   }
   ctx.sync();
+}
+
+// A value outside the range of fp32 in a copy just made: error -48, and no preconditioner
+void H::check_f32_overflow() {
   for (int b : {(int)NSK_BLK_F, (int)NSK_BLK_MP, (int)NSK_BLK_S}) {
     Csr &A = blk[b];
     if (!A.inner32) continue;
@@ -374,16 +361,6 @@ void H::setup(int type, int variant_, double alpha_) {
                            names[b] + " are finite in fp64 but outside the range of fp32");
     }
   }
-  // fp32 basis of the inner FGMRES on F; NSK_INNER_BASIS_PRECISION=32 / 64 overrides the option (A/B measurements with
-  // unchanged callers), any other value is ignored.  A set-up that does not want the vectors frees them.
-  static const int env_basis = [] {
-    const char *e = std::getenv("NSK_INNER_BASIS_PRECISION");
-    const int v = e ? std::atoi(e) : 0;
-    return v == 32 || v == 64 ? v : 0;
-  }();
-  basis32_wanted = (env_basis ? env_basis : inner_basis_precision) == 32;
-  if (inner_basis_width() != 4) basis32_u.destroy();
-  setup_ms = wall_ms() - t0;
 }
 
 void H::prec_vmult(DVec &dst, const DVec &src) {

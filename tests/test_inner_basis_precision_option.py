@@ -34,19 +34,35 @@ def test_the_getter_is_declared_listed_and_wrapped():
 
 
 def test_the_environment_override_is_read_once_and_takes_32_or_64_only():
-    """The library's own parsing, as for the two other precision options: a function-local static (read once per
-    process), atoi, and every value but 32 and 64 counts as unset."""
+    """The library's own parsing, as for the other precision options: one function-local static (read once per process)
+    holds all eight overrides, atoi, and every value but 32 and 64 counts as unset."""
+    from tests import setup_plan_reference as R
     csrc = {n: _read("navier_stokes_solver_amd", "csrc", n)
             for n in ("nsk_handle.hpp", "nsk_precond.cpp", "nsk_capi.cpp", "nsk_capi_assembly.cpp", "nsk_debug.cpp")}
-    src = csrc["nsk_precond.cpp"]
-    m = re.search(r"static const int (\w+) = \[\] \{\s*const char \*e = std::getenv\(\"NSK_INNER_BASIS_PRECISION\"\);"
-                  r"\s*const int v = e \? std::atoi\(e\) : 0;\s*return v == 32 \|\| v == 64 \? v : 0;\s*\}\(\);", src)
-    assert m, "NSK_INNER_BASIS_PRECISION is not parsed the way NSK_INNER_MATRIX_PRECISION is"
-    name = m.group(1)
-    assert re.search(rf"\({name} \? {name} : inner_basis_precision\) == 32", src)
-    assert "\n".join(csrc.values()).count('getenv("NSK_INNER_BASIS_PRECISION")') == 1
-    # the option itself: 64 or 32, anything else is error -61
-    assert re.search(r"case NSK_OPT_INNER_BASIS_PRECISION:\s*if \(v != 64\.0 && v != 32\.0\) throw Error\(-61,", csrc["nsk_capi.cpp"])
+    # read once, in one place: one getenv per override across the handle files, all inside the one static
+    m = re.search(r"inline const SetupEnv &setup_env\(\) \{\s*static const SetupEnv env = \{(.*?)\};\s*return env;\s*\}",
+                  csrc["nsk_handle.hpp"], re.S)
+    assert m, "the overrides are not read by one function-local static behind one accessor"
+    for name in R.ENV_NAMES:
+        assert "\n".join(csrc.values()).count(f'getenv("{name}")') == 1, name
+        kind = "precision" if name.endswith("PRECISION") else "switch"
+        assert f'parse_env_{kind}(std::getenv("{name}"))' in m.group(1), name
+    # accepts only these values
+    for text, precision, _ in R.ENV_TEXTS:
+        assert R.env_parse(R.PRECISION, text) == precision, text
+    # the override wins over the option, and unset leaves the option: every pair, in every set-up
+    for opt in (64, 32):
+        for env in (0, 32, 64):
+            for t, v in R.SETUPS:
+                plan = R.library_plan(dict(R.DEFAULTS, inner_basis_precision=opt), dict(R.ENV_UNSET, inner_basis_precision=env), t, v)
+                assert plan["basis32"] == int((env if env else opt) == 32), (opt, env, t, v)
+    assert re.search(r"basis32_wanted = plan\.basis32;", csrc["nsk_precond.cpp"])
+    # the option itself: 64 or 32, anything else is error -61 (the helper of the plain cases throws it)
+    assert re.search(r"case NSK_OPT_INNER_BASIS_PRECISION:\s*req\.inner_basis_precision = one_of\(v, \{64, 32\}, "
+                     r"\"NSK_OPT_INNER_BASIS_PRECISION: 64 or 32\"\);", csrc["nsk_capi.cpp"])
+    assert re.search(r"static int one_of\(double v, std::initializer_list<double> allowed, const char \*text\) \{\s*"
+                     r"for \(const double a : allowed\)\s*if \(v == a\) return \(int\)v;\s*throw Error\(-61, text\);\s*\}",
+                     csrc["nsk_capi.cpp"])
 
 
 def test_both_drivers_print_the_line():

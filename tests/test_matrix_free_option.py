@@ -51,17 +51,32 @@ def test_the_entry_points_are_declared_listed_and_wrapped():
 
 
 def test_the_environment_override_is_read_once_and_takes_0_or_1_only():
-    """A function-local static (read once per process), as the three precision switches are read; exactly "0" or "1",
-    anything else counts as unset."""
+    """One function-local static (read once per process) holds all eight overrides, as the precision switches are read;
+    exactly "0" or "1", anything else counts as unset."""
+    from tests import setup_plan_reference as R
     src, capi, every = _csrc("nsk_precond.cpp"), _csrc("nsk_capi.cpp"), _csrc(*HANDLE_FILES)
-    m = re.search(r"static const int (\w+) = \[\] \{\s*const char \*e = std::getenv\(\"NSK_INNER_MATRIX_FREE_F\"\);"
-                  r"\s*if \(e && e\[0\] == '0' && !e\[1\]\) return 0;\s*if \(e && e\[0\] == '1' && !e\[1\]\) return 1;"
-                  r"\s*return -1;\s*\}\(\);", src)
-    assert m, "NSK_INNER_MATRIX_FREE_F is not parsed by a function-local static that takes 0 or 1 only"
-    name = m.group(1)
-    assert re.search(rf"matfree_wanted = \({name} >= 0 \? {name} : matrix_free_f\) == 1;", src)
-    assert every.count('getenv("NSK_INNER_MATRIX_FREE_F")') == 1
-    assert re.search(r"case NSK_OPT_INNER_MATRIX_FREE_F:\s*if \(v != 0\.0 && v != 1\.0\) throw Error\(-61,", capi)
+    # read once, in one place: one getenv per override across the handle files, all inside the one static
+    m = re.search(r"inline const SetupEnv &setup_env\(\) \{\s*static const SetupEnv env = \{(.*?)\};\s*return env;\s*\}",
+                  _csrc("nsk_handle.hpp"), re.S)
+    assert m, "the overrides are not read by one function-local static behind one accessor"
+    for name in R.ENV_NAMES:
+        assert every.count(f'getenv("{name}")') == 1, name
+    assert 'parse_env_switch(std::getenv("NSK_INNER_MATRIX_FREE_F"))' in m.group(1)
+    # accepts only these values
+    for text, _, switch in R.ENV_TEXTS:
+        assert R.env_parse(R.SWITCH, text) == switch, text
+    # the override wins over the option, and unset leaves the option: every pair, in every set-up
+    for opt in (0, 1):
+        for env in (-1, 0, 1):
+            for t, v in R.SETUPS:
+                plan = R.library_plan(dict(R.DEFAULTS, matrix_free_f=opt), dict(R.ENV_UNSET, matrix_free_f=env), t, v)
+                assert plan["matfree"] == int((opt if env < 0 else env) == 1), (opt, env, t, v)
+    assert re.search(r"matfree_wanted = plan\.matfree;", src)
+    # the option itself: 0 or 1, anything else is error -61 (the helper of the plain cases throws it)
+    assert re.search(r"case NSK_OPT_INNER_MATRIX_FREE_F:\s*req\.matrix_free_f = one_of\(v, \{0, 1\}, "
+                     r"\"NSK_OPT_INNER_MATRIX_FREE_F: 0 or 1\"\);", capi)
+    assert re.search(r"static int one_of\(double v, std::initializer_list<double> allowed, const char \*text\) \{\s*"
+                     r"for \(const double a : allowed\)\s*if \(v == a\) return \(int\)v;\s*throw Error\(-61, text\);\s*\}", capi)
     # the fallback announces itself, once per handle
     assert every.count("[nsk] warning: NSK_OPT_INNER_MATRIX_FREE_F = 1") == 1 and "matfree_warned = true;" in every
 
