@@ -147,7 +147,10 @@ enum {
                                  blockTriangular).  64 (default): double, as today.  32: they read copies of F, S and M_p
                                  rounded to float (F's 2x2 node-block copy, gathered from the double values; S and M_p
                                  scalar), made at every set-up and made again before use whenever the values change
-                                 (nsk_update_values, nsk_scale_values, nsk_assemble) without one; a set-up that finds a
+                                 (nsk_update_values, nsk_scale_values, nsk_assemble) without one.  nsk_set_block_csr of
+                                 F or M_p hands over a pattern and drops that block's copy: until the
+                                 next set-up the inner product of that block reads the double values
+                                 (nsk_inner_value_bytes: 8), and the next set-up converts again; a set-up that finds a
                                  value finite in fp64 but outside fp32's range returns -48.  What stays double: vectors,
                                  products, sums and the kernels' LDS partials (values are widened as they are loaded); the
                                  outer J x (fused F | Bt block row, or its per-block SpMVs); B and Bt inside the aSIMPLE

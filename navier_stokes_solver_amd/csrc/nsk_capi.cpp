@@ -215,7 +215,7 @@ int nsk_set_option(nsk_handle h, int opt, double v) {
     case NSK_IOPT_FGMRES_SKIP_UNUSED: h->skip_unused = one_of(v, {0, 1}, "NSK_IOPT_FGMRES_SKIP_UNUSED: 0 or 1") != 0; break;
     case NSK_IOPT_OVERLAP_HALO: h->overlap_halo = v != 0.0; break;
     case NSK_IOPT_TINY_BYTES: h->tF.tiny_bytes = h->tMp.tiny_bytes = h->tS.tiny_bytes = v; break;
-    case NSK_OPT_BSR_VELOCITY: h->use_bsr = v != 0.0; break;
+    case NSK_OPT_BSR_VELOCITY: h->use_bsr = v != 0.0; break;   // (part of the key of F's analysis: setup_velocity_factor)
     case NSK_OPT_VELOCITY_AMG: req.velocity_amg = v != 0.0; break;
     case NSK_IOPT_TIMEOP_BETWEEN: h->timeop_between = (int)v; break;
     case NSK_IOPT_INDEX16:
@@ -592,8 +592,10 @@ int nsk_get_stats(nsk_handle h, nsk_stats *o) {
   o->spmv_bytes = st.spmv_bytes;
   o->tri_bytes = st.tri_bytes;
   o->blas1_bytes = st.blas1_bytes;
-  o->n_colors_u = h->tF_ok ? h->tF.n_colors : 0;
-  o->n_levels_u = h->tF_ok ? h->tF.n_levels_L : 0;
+  // (a factor of F an earlier set-up left behind is not this set-up's while a hierarchy holds the velocity slot: DESIGN 5x)
+  const bool factor_u = h->tF_ok && !h->amg_active;
+  o->n_colors_u = factor_u ? h->tF.n_colors : 0;
+  o->n_levels_u = factor_u ? h->tF.n_levels_L : 0;
   o->n_colors_p = h->tP ? h->tP->n_colors : 0;
   o->n_levels_p = h->tP ? h->tP->n_levels_L : 0;
   o->nnz_s = h->blk[NSK_BLK_S].present ? h->blk[NSK_BLK_S].nnz : 0;

@@ -198,6 +198,8 @@ void H::setup_velocity_factor(const SetupPlan &plan, int key) {
   // (asimple_amg_active: the hierarchy stands; no factor of F.  S's pattern and factor, where ILU(S) is wanted, are formed
   // in setup_schur on this thread: the side thread exists to overlap F's analysis, of which there is none)
   if (asimple_amg_active) return;
+  // F's analysis is on 2 x 2 node blocks or scalar by NSK_OPT_BSR_VELOCITY: its key holds that bit as well
+  const int key_F = key * 2 + (use_bsr ? 1 : 0);
   if (amg_active) {
     amgF.clear();
     amg_pending = true;
@@ -212,7 +214,7 @@ void H::setup_velocity_factor(const SetupPlan &plan, int key) {
   std::exception_ptr side_err;
   bool side_done_s = false;
   // (not under NSK_OPT_SCHUR_AMG: S's factor is not analysed then, and the pattern is formed in setup_schur)
-  if (prec_type == 2 && !plan.want_amgS && (!tF_ok || tF_key != key) && (!tS_ok || tS_key != key)) {
+  if (prec_type == 2 && !plan.want_amgS && (!tF_ok || tF_key != key_F) && (!tS_ok || tS_key != key)) {
     side = std::thread([&] {
       try {
         (void)hipSetDevice(ctx.device);
@@ -232,7 +234,7 @@ void H::setup_velocity_factor(const SetupPlan &plan, int key) {
     std::thread &t;
     ~Joiner() { if (t.joinable()) t.join(); }
   } joiner{side};
-  analyse_unless_held(tF_ok, tF_key, key, [&] {
+  analyse_unless_held(tF_ok, tF_key, key_F, [&] {
     Phase ph("analyse F factor (host)");
     tF.analyze(&ctx, F, plan.kindF, tri_ordering, sub_offsets(0), use_bsr && F.blk_ok && F.blk_R == 2 && F.blk_C == 2, xy(0),
                group_u);
