@@ -33,7 +33,8 @@
  *   -50..-59 bad arguments of the hand-off calls           -60..-66 device assembly / Newton state
  *   -69, -71..-73 forces / output patches from the resident state (-69: no cells, or no faces / edges handed over; -71:
  *        faces or a record list on a P2/P1 handle, edges or patches on the other kind; -72: a cell index out of range;
- *        -73: no state); the record calls also -69 without a record list and -60 for subdivisions outside 1..4
+ *        -73: no state); the record calls also -69 without a record list and -60 for subdivisions outside 1..4; the
+ *        record's derived fields also -69 without gradient tables, -60 for another mask, -71 under a point list
  *   -70 single-launch triangular solve gave up waiting AND the per-colour retry failed too (see NSK_OPT_TRI_SYNC_FREE)
  *   -80..-85 AMG set-up (operator too large for 32-bit indices, rows too wide, rounds / estimates that do not end; -85:
  *        NSK_OPT_SCHUR_AMG, a level's diagonal with both signs or a zero — the set-up falls back to ILU(S), see there;
@@ -529,6 +530,29 @@ int nsk_record_set_cells(nsk_handle h, int64_t n_cells, const int32_t *cells, in
                          const double *w_u /* (s+1)^2 x 16 */, const double *w_p /* (s+1)^2 x 9 */);
 int nsk_record_set_points(nsk_handle h, int64_t n_points, const int32_t *u_node, const int32_t *p_dof);
 int nsk_state_get_record(nsk_handle h, int64_t n_points, double *vel3 /* 3 per point */, double *prs /* 1 per point */);
+/* Vorticity and divergence at the record's points, from the gradient of the element's own functions — the file
+ * shows the solution on bilinear quads (or linear triangles), from which no viewer can recover it.  A second launch beside
+ * nsk_state_get_record, whose results keep their bits.
+ * nsk_record_set_gradient (Q3/Q2 handles, after nsk_record_set_cells with the same s; needed for s = 1 too, a vertex
+ *   derivative reads all 16 nodes): D_x[pt][n] = L'_a(t_k) L_b(t_l) / hx and D_y[pt][n] = L_a(t_k) L'_b(t_l) / hy, laid
+ *   out like W_u (n = b*4 + a, pt = l (s+1) + k), each entry the double product of two 1-D values, then one division
+ *   (nsp_record_gradient_tables).  The tables stay on the device until nsk_assembly_set_cells, nsk_assembly_set_simplex or
+ *   a new nsk_record_set_cells void them.  -60: s differs from the record's; -69: no record list; -71: a P2/P1 handle.
+ * nsk_state_get_record_fields: fields is a mask of NSK_FIELD_VORTICITY (d_x u_y - d_y u_x) and NSK_FIELD_DIVERGENCE
+ *   (d_x u_x + d_y u_y); out receives n_points doubles per selected field, vorticity first, in the point order of
+ *   nsk_state_get_record — each block is the bytes of that array in the file.  Q3/Q2: g_cd = sum_n D_d[pt][n] u_c[n], n
+ *   increasing, one accumulator per sum, then g_10 - g_01 and g_00 + g_11; ghost nodes are read from the ghost tail.
+ *   P2/P1 (one rank, no tables, n_points = n_p): per vertex (sum_t area_t f_t(v)) / (sum_t area_t) over the vertex's cells
+ *   in the order of vert_ptr / vert_ent, f_t(v) the field of cell t's six P2 functions at that vertex; +0.0 at a vertex of
+ *   no cell.  No atomics: two calls give the same bits, and a mask of one field gives the bits it has in a mask of both.
+ *   -60: mask 0 or an unknown bit, n_points is not the record's; -69: no cells, no record list, or (Q3/Q2) no gradient
+ *   tables; -73: no state; -71: a P2/P1 handle with a point list of nsk_record_set_points in force (a rank's piece sees
+ *   only its own cells of a vertex on the cut). */
+#define NSK_FIELD_VORTICITY 1
+#define NSK_FIELD_DIVERGENCE 2
+int nsk_record_set_gradient(nsk_handle h, int subdivisions, const double *d_x /* (s+1)^2 x 16 */,
+                            const double *d_y /* (s+1)^2 x 16 */);
+int nsk_state_get_record_fields(nsk_handle h, int64_t n_points, int fields, double *out /* n_points per field */);
 /* values of a resident block times a factor: pressure_mass is assembled with 1/nu (:404, :450), block (1,0)
  * changes sign between the Stokes and the Newton phase (:397 against :444) */
 int nsk_scale_values(nsk_handle h, int blk, double factor);

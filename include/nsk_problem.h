@@ -133,6 +133,11 @@ void nsp_face_tables(const nsp_mesh *m, double *out672);
  * w_p[pt * 9 + b*3 + a] the same on {0, 1/2, 1}.  Rows at the vertices are exact unit vectors.  Returns 0, or -1 for
  * another s. */
 int nsp_record_tables(const nsp_mesh *m, int32_t subdivisions, double *w_u, double *w_p);
+/* Gradient tables of the record's vorticity and divergence (nsk_record_set_gradient), laid out like w_u for cells of
+ * hx x hy: d_x[pt * 16 + b*4 + a] = L'_a(t_k) L_b(t_l) / hx and d_y[...] = L_a(t_k) L'_b(t_l) / hy on the GLL nodes, each
+ * entry the double product of two 1-D values followed by one division.  Needed for s = 1 too.  Returns 0, or -1 for
+ * another s or a non-positive size. */
+int nsp_record_gradient_tables(const nsp_mesh *m, int32_t subdivisions, double hx, double hy, double *d_x, double *d_y);
 
 /* Support points of this rank's owned DoFs (what DoFTools::map_dofs_to_support_points gives the reference's caller):
  * out_xy[2 d], out_xy[2 d + 1] = (x, y) of owned DoF d of `space` (0: velocity, both components of a node share the

@@ -126,9 +126,39 @@ def vtu_switches(env, read_mesh=False):
     return fmt, int(sub)
 
 
+def vtu_fields(env, read_mesh=False):
+    """The derived arrays of the binary VTU record from NSK_VTU_FIELDS, a comma list of `vorticity` and `divergence`
+    (default: none), in file order.  ValueError, with the message the drivers exit on, for an unknown name and
+    for the combinations that do not exist: the fields are computed on the device from the resident state into the binary
+    record, and a rank's piece of a -M mesh sees only its own cells of a vertex on the cut."""
+    raw = env.get("NSK_VTU_FIELDS", "")
+    if raw == "":
+        return ()
+    from .postprocess import FIELDS
+    names = raw.split(",")
+    if any(n not in FIELDS for n in names):
+        raise ValueError(f"NSK_VTU_FIELDS={raw}: the names are vorticity and divergence, separated by commas")
+    several = env.get("NSK_RANKS", "1") not in ("", "0", "1") or int(env.get("WORLD_SIZE", "1") or "1") > 1
+    for bad, why in ((env.get("NSK_VTU_FORMAT", "ascii") != "binary", "needs NSK_VTU_FORMAT=binary"),
+                     (env.get("NSK_HOST_POSTPROCESS", "0") not in ("", "0"), "does not go with NSK_HOST_POSTPROCESS=1"),
+                     (bool(read_mesh) and several, "does not apply to -M (P2/P1 triangles) on several ranks"),
+                     (bool(read_mesh) and bool(env.get("NSK_HOST_ASSEMBLY")),
+                      "does not go with NSK_HOST_ASSEMBLY (the fields come from the resident state)")):
+        if bad:
+            raise ValueError(f"NSK_VTU_FIELDS={raw} {why}")
+    return tuple(f for f in FIELDS if f in names)
+
+
+def _fill_fields(ls, record):
+    """The record's derived arrays in place inside the file image: one `nsk_state_get_record_fields` per array."""
+    from . import postprocess as PP
+    for f in record.fields:
+        ls.record_fields(record.n_points, PP.field_mask((f,)), out=record.field[f])
+
+
 def _make_record(ls, pr, cfg, rank=0):
     """NSK_VTU_FORMAT=binary: the record list on the handle (`nsk_record_set_cells`) and the file image of this rank's
-    strip, once per run and rank; None for the ASCII record."""
+    strip, once per run and rank; None for the ASCII record.  NSK_VTU_FIELDS: the gradient tables too."""
     if cfg.get("vtu_format", "ascii") != "binary":
         return None
     import numpy as np
@@ -137,7 +167,10 @@ def _make_record(ls, pr, cfg, rank=0):
     own = np.nonzero(pr.cell_in_strip)[0]
     s = cfg.get("vtu_subdivisions", 1)
     ls.set_record(own, s)
-    return PP.VtuRecord.quads(pr.cell_ij[own], PP.LX / pr.info["nx"], PP.LY / pr.info["ny"], s, rank)
+    hx, hy, fields = PP.LX / pr.info["nx"], PP.LY / pr.info["ny"], cfg.get("vtu_fields", ())
+    if fields:
+        ls.set_record_gradient(s, hx, hy)
+    return PP.VtuRecord.quads(pr.cell_ij[own], hx, hy, s, rank, fields=fields)
 
 
 def _device_report(ls, pr, nu, name, counter, n_digits, rank=0, nranks=1, record=None):
@@ -150,6 +183,7 @@ def _device_report(ls, pr, nu, name, counter, n_digits, rank=0, nranks=1, record
     from . import postprocess as PP
     if record is not None:
         ls.state_record(vel3=record.vel3, prs=record.prs)
+        _fill_fields(ls, record)
         PP.write_vtu_record(record, os.environ.get("NSK_OUTPUT_DIR", "./"), name, counter, n_digits=n_digits, rank=rank,
                             nranks=nranks)
         return ls.forces(nu)
@@ -229,10 +263,12 @@ def run_gmsh(cfg, unsteady: bool) -> int:
             return
         if r not in records:
             records[r] = PP.VtuRecord.triangles(space.mesh.nodes, space.cell_p if r is None else
-                                                space.cell_p[backend.layout.cell_rank == r])
+                                                space.cell_p[backend.layout.cell_rank == r],
+                                                fields=cfg.get("vtu_fields", ()))
         rec = records[r]
         if u is None:                       # one rank, device assembly: the vertices' values from the resident state
             ls.state_record(vel3=rec.vel3, prs=rec.prs)
+            _fill_fields(ls, rec)
         else:
             rec.vel3[:, 0], rec.vel3[:, 1], rec.prs[:] = u[0:2 * space.n_p:2], u[1:2 * space.n_p:2], p[:space.n_p]
         rec.write(path)
@@ -641,6 +677,9 @@ def run(cfg, unsteady: bool) -> int:
                                      or bool(os.environ.get("NSK_HOST_ASSEMBLY")))
         print("[nsk] NSK_VTU_FORMAT=binary: the VTU record as raw appended data" + ("" if host else ", packed on the device")
               + (f", {s} x {s} patches per cell" if s > 1 else ""))
+    if cfg.get("vtu_fields"):
+        print(f"[nsk] NSK_VTU_FIELDS={','.join(cfg['vtu_fields'])}: derived arrays in the VTU record, from the gradient of "
+              "the element's own functions on the device")
     if cfg["read_mesh"]:
         return run_gmsh(cfg, unsteady)
     if cfg["prec"] not in PRECS:
@@ -718,6 +757,7 @@ def main(argv=None) -> int:
         return rc
     try:
         cfg["vtu_format"], cfg["vtu_subdivisions"] = vtu_switches(os.environ, cfg["read_mesh"])
+        cfg["vtu_fields"] = vtu_fields(os.environ, cfg["read_mesh"])
     except ValueError as e:
         sys.stderr.write(f"Error: {e}\n")
         return 1

@@ -18,6 +18,7 @@
 // Built twice from this file: -DNSK_UNSTEADY=0 -> StationaryNSSolver, -DNSK_UNSTEADY=1 -> NSSolver.
 #include <getopt.h>
 
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -61,6 +62,8 @@ static void check(nsk_handle h, int rc, const char *what) {
 struct VtuSwitches {
   bool binary = false;
   int subdivisions = 1;
+  unsigned fields = 0;       // NSK_VTU_FIELDS: mask of vtu::field_name's arrays
+  std::string fields_text;   // the names in file order, separated by commas
 };
 static std::string vtu_switches(VtuSwitches &out) {
   const char *f = std::getenv("NSK_VTU_FORMAT"), *s = std::getenv("NSK_VTU_SUBDIVISIONS"), *hp = std::getenv("NSK_HOST_POSTPROCESS");
@@ -73,6 +76,28 @@ static std::string vtu_switches(VtuSwitches &out) {
   if (out.subdivisions > 1 && !out.binary) return "NSK_VTU_SUBDIVISIONS=" + sub + " needs NSK_VTU_FORMAT=binary";
   if (out.subdivisions > 1 && host) return "NSK_VTU_SUBDIVISIONS=" + sub + " does not go with NSK_HOST_POSTPROCESS=1";
   if (out.binary && host) return "NSK_VTU_FORMAT=binary does not go with NSK_HOST_POSTPROCESS=1";
+  return "";
+}
+
+// NSK_VTU_FIELDS: a comma list of vorticity and divergence (default: none); after vtu_switches.  Returns the
+// message to exit on, or an empty string.
+static std::string vtu_fields(VtuSwitches &out) {
+  const char *e = std::getenv("NSK_VTU_FIELDS"), *hp = std::getenv("NSK_HOST_POSTPROCESS");
+  const std::string raw = e ? e : "";
+  if (raw.empty()) return "";
+  for (size_t a = 0; a <= raw.size();) {
+    const size_t b = std::min(raw.find(',', a), raw.size());
+    const std::string name = raw.substr(a, b - a);
+    int k = 0;
+    while (k < vtu::kFields && name != vtu::field_name(k)) ++k;
+    if (k == vtu::kFields) return "NSK_VTU_FIELDS=" + raw + ": the names are vorticity and divergence, separated by commas";
+    out.fields |= 1u << k;
+    a = b + 1;
+  }
+  if (!out.binary) return "NSK_VTU_FIELDS=" + raw + " needs NSK_VTU_FORMAT=binary";
+  if (hp && *hp && std::string(hp) != "0") return "NSK_VTU_FIELDS=" + raw + " does not go with NSK_HOST_POSTPROCESS=1";
+  for (int k = 0; k < vtu::kFields; ++k)
+    if (out.fields >> k & 1u) out.fields_text += (out.fields_text.empty() ? "" : ",") + std::string(vtu::field_name(k));
   return "";
 }
 
@@ -100,7 +125,13 @@ struct Report {
       std::vector<double> wu((size_t)(s + 1) * (s + 1) * 16), wp((size_t)(s + 1) * (s + 1) * 9);
       if (nsp_record_tables(mesh, s, wu.data(), wp.data()) != 0) throw std::runtime_error("nsp_record_tables failed");
       check(h, nsk_record_set_cells(h, (int64_t)cells.size(), cells.data(), s, wu.data(), wp.data()), "nsk_record_set_cells");
-      record = vtu::quad_record((int64_t)cells.size(), ij.data(), hx, hy, s, 0);
+      if (sw.fields) {
+        std::vector<double> dx((size_t)(s + 1) * (s + 1) * 16), dy(dx.size());
+        if (nsp_record_gradient_tables(mesh, s, hx, hy, dx.data(), dy.data()) != 0)
+          throw std::runtime_error("nsp_record_gradient_tables failed");
+        check(h, nsk_record_set_gradient(h, s, dx.data(), dy.data()), "nsk_record_set_gradient");
+      }
+      record = vtu::quad_record((int64_t)cells.size(), ij.data(), hx, hy, s, 0, sw.fields);
     }
   }
   void operator()(const char *name, unsigned counter, int n_digits) {
@@ -108,6 +139,9 @@ struct Report {
     const char *dir = std::getenv("NSK_OUTPUT_DIR");
     if (record) {   // the two arrays of the file, filled in place, and one write
       check(h, nsk_state_get_record(h, record->n_points(), record->vel3(), record->prs()), "nsk_state_get_record");
+      for (int k = 0; k < vtu::kFields; ++k)   // the derived arrays, each in place
+        if (record->field(k))
+          check(h, nsk_state_get_record_fields(h, record->n_points(), 1 << k, record->field(k)), "nsk_state_get_record_fields");
       record->write(dir ? dir : "./", name, vtu::counter_text(counter, n_digits), 0, 1);
     } else {
       check(h, nsk_state_get_patches(h, (int64_t)cells.size(), cells.data(), vel.data(), prs.data()), "nsk_state_get_patches");
@@ -379,6 +413,7 @@ int main(int argc, char *argv[]) {
     std::string msg = vtu_switches(vtu_sw);
     if (msg.empty() && vtu_sw.subdivisions > 1 && read_mesh_from_file)
       msg = "NSK_VTU_SUBDIVISIONS=" + std::to_string(vtu_sw.subdivisions) + " does not apply to -M (P2/P1 triangles)";
+    if (msg.empty()) msg = vtu_fields(vtu_sw);
     if (!msg.empty()) { std::cerr << "Error: " << msg << "\n"; return 1; }
   }
 
@@ -403,6 +438,9 @@ int main(int argc, char *argv[]) {
     if (vtu_sw.subdivisions > 1) std::printf(", %d x %d patches per cell", vtu_sw.subdivisions, vtu_sw.subdivisions);
     std::printf("\n");
   }
+  if (vtu_sw.fields)
+    std::printf("[nsk] NSK_VTU_FIELDS=%s: derived arrays in the VTU record, from the gradient of the element's own functions "
+                "on the device\n", vtu_sw.fields_text.c_str());
   nsk_handle h = nullptr;
   nsp_mesh *mesh = nullptr;
   try {

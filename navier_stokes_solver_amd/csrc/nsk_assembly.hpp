@@ -55,6 +55,11 @@ void state_patches(hipStream_t s, const AsmMesh &M, long n, const int *cells, co
 // cell's 16 nodes / 9 DoFs with wu[(s+1)^2][16], wp[(s+1)^2][9], n increasing, one accumulator.  One launch, no atomics.
 void state_record(hipStream_t s, const AsmMesh &M, long n_cells, int subdivisions, const int *cells, const double *wu,
                   const double *wp, const double *su, const double *sp, double *vel3, double *prs);
+// Vorticity d_x u_y - d_y u_x and divergence d_x u_x + d_y u_y at the same points: four sums over the cell's 16
+// nodes with dx[(s+1)^2][16], dy[(s+1)^2][16], n increasing, one accumulator each.  vort / div: n_cells (s+1)^2 doubles, or
+// null for a field that is not wanted.  One launch, no atomics.
+void record_fields(hipStream_t s, const AsmMesh &M, long n_cells, int subdivisions, const int *cells, const double *dx,
+                   const double *dy, const double *su, double *vort, double *div);
 
 // ---- P2/P1 on triangles (general cells; the reference's -M path) ----
 struct SimplexMesh {  // device pointers
@@ -89,6 +94,9 @@ void forces_edges(hipStream_t s, const SimplexMesh &M, long n_edges, const int *
                   const double *edge_nl, const double *su, const double *sp, double nu, double *slots, double *out2);
 // the record of the mesh's vertices: the first n_points velocity nodes and pressure DoFs, (u_x, u_y, +0.0) and p
 void simplex_record(hipStream_t s, long n_points, const double *su, const double *sp, double *vel3, double *prs);
+// vorticity and divergence at those vertices: the area-weighted average over the vertex's cells (vert_ptr / vert_ent, list
+// order) of the cell's own value at the vertex; vort / div may be null.  One launch, one thread per vertex
+void simplex_record_fields(hipStream_t s, const SimplexMesh &M, long n_points, const double *su, double *vort, double *div);
 // the record of listed points (nsk_record_set_points): per point a velocity node and a pressure DoF of the state
 // [owned | ghost]; the bits of the state.  One launch, one thread per point
 void simplex_record_points(hipStream_t s, long n_points, const int *u_node, const int *p_dof, const double *su, const double *sp,

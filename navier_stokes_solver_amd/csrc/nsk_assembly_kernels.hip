@@ -409,6 +409,44 @@ __global__ __launch_bounds__(BLK) void state_record_kernel(long n_points, int pp
   prs[t] = p;
 }
 
+// Vorticity and divergence at the record's points: g_cd = sum_n D_d[pt][n] u_c[n] over the cell's 16 nodes with
+// the tables dx[pt][16], dy[pt][16] (postprocess.record_gradient_tables), n increasing, one accumulator per sum; then
+// vort = g_10 - g_01 and div = g_00 + g_11.  A workgroup takes cpg = BLK / ppc consecutive cells of the record: it stages the
+// two tables and its cells' 16 (u_x, u_y) pairs — gathered through cell_u with one 16-byte load per node, owned or ghost —
+// in LDS, so the state is read from memory once per cell; thread lc * ppc + pt then forms its point's four sums from LDS.
+// vort / div: either may be null (the field was not asked for).  No atomics: two calls give the same bits.
+constexpr int RF_MAX_PPC = 25, RF_MAX_CELLS = BLK / 4;
+__global__ __launch_bounds__(BLK) void record_fields_kernel(long n_cells, int ppc, int cpg, const int *__restrict__ cells,
+                                                            const int *__restrict__ cell_u, const double *__restrict__ dx,
+                                                            const double *__restrict__ dy, const double *__restrict__ su,
+                                                            double *__restrict__ vort, double *__restrict__ div) {
+  __shared__ double sdx[RF_MAX_PPC * 16], sdy[RF_MAX_PPC * 16];
+  __shared__ double2 suv[RF_MAX_CELLS * 16];
+  const long cell0 = (long)blockIdx.x * cpg;
+  const long left = n_cells - cell0;
+  const int nc = left < cpg ? (int)left : cpg;
+  for (int i = threadIdx.x; i < ppc * 16; i += BLK) { sdx[i] = dx[i]; sdy[i] = dy[i]; }
+  for (int i = threadIdx.x; i < nc * 16; i += BLK) {
+    const long cell = cells[cell0 + (i >> 4)];
+    const int node = cell_u[cell * 16 + (i & 15)];
+    suv[i] = *reinterpret_cast<const double2 *>(su + 2 * (size_t)node);
+  }
+  __syncthreads();
+  const int lc = (int)threadIdx.x / ppc, pt = (int)threadIdx.x - lc * ppc;
+  if (lc >= nc) return;
+  const double *X = sdx + pt * 16, *Y = sdy + pt * 16;
+  const double2 *U = suv + lc * 16;
+  double g00 = 0.0, g01 = 0.0, g10 = 0.0, g11 = 0.0;
+  for (int n = 0; n < 16; ++n) {
+    const double2 uv = U[n];
+    g00 += X[n] * uv.x; g01 += Y[n] * uv.x;
+    g10 += X[n] * uv.y; g11 += Y[n] * uv.y;
+  }
+  const long t = (cell0 + lc) * ppc + pt;
+  if (vort) vort[t] = g10 - g01;
+  if (div) div[t] = g00 + g11;
+}
+
 }  // namespace
 
 static void forces_sum(hipStream_t s, long n_slots, const double *slots, double *out2) {
@@ -478,6 +516,14 @@ void state_record(hipStream_t s, const AsmMesh &M, long n_cells, int subdivision
   else
     hipLaunchKernelGGL(state_record_kernel, grid, dim3(BLK), 0, s, n_points, ppc, cells, M.cell_u, M.cell_p, wu, wp, su, sp,
                        vel3, prs);
+}
+
+void record_fields(hipStream_t s, const AsmMesh &M, long n_cells, int subdivisions, const int *cells, const double *dx,
+                   const double *dy, const double *su, double *vort, double *div) {
+  const int ppc = (subdivisions + 1) * (subdivisions + 1), cpg = BLK / ppc;
+  if (n_cells <= 0 || ppc > RF_MAX_PPC || cpg > RF_MAX_CELLS) return;
+  hipLaunchKernelGGL(record_fields_kernel, dim3((unsigned)((n_cells + cpg - 1) / cpg)), dim3(BLK), 0, s, n_cells, ppc, cpg, cells,
+                     M.cell_u, dx, dy, su, vort, div);
 }
 
 }  // namespace nsk
@@ -733,7 +779,50 @@ __global__ __launch_bounds__(256) void simplex_record_points_kernel(long n_point
   prs[t] = spv[p_dof[t]];
 }
 
+// Vorticity and divergence at the vertices of a P2/P1 mesh: the gradient of a P2 field jumps from cell to
+// cell, so vertex v gets (sum_t area_t f_t(v)) / (sum_t area_t) over the cells of vert_ptr / vert_ent in list order, f_t(v)
+// the field from the gradients of the cell's six P2 functions at lambda = e_lv (p2_grad, as forces_edges_kernel forms them),
+// n increasing, one accumulator per sum.  One thread per vertex, no atomics: two calls give the same bits.  A vertex of no
+// cell gets +0.0.  vort / div: either may be null.
+__global__ __launch_bounds__(256) void simplex_record_fields_kernel(long n_points, const int *__restrict__ cell_u,
+                                                                    const double *__restrict__ grad_lam,
+                                                                    const double *__restrict__ area,
+                                                                    const int *__restrict__ vert_ptr,
+                                                                    const int *__restrict__ vert_ent,
+                                                                    const double *__restrict__ su, double *__restrict__ vort,
+                                                                    double *__restrict__ div) {
+  const long v = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= n_points) return;
+  double sw = 0.0, sd = 0.0, sa = 0.0;
+  for (int e = vert_ptr[v]; e < vert_ptr[v + 1]; ++e) {
+    const int code = vert_ent[e], t = code / 3, lv = code % 3;
+    const double lam[3] = {lv == 0 ? 1.0 : 0.0, lv == 1 ? 1.0 : 0.0, lv == 2 ? 1.0 : 0.0};
+    const int *cu = cell_u + 6 * (size_t)t;
+    const double *gl = grad_lam + 6 * (size_t)t;
+    double g00 = 0, g01 = 0, g10 = 0, g11 = 0;
+    for (int n = 0; n < 6; ++n) {
+      double val, gx, gy;
+      p2_grad(n, lam, gl, val, gx, gy);
+      const double ux = su[2 * (size_t)cu[n]], uy = su[2 * (size_t)cu[n] + 1];
+      g00 += ux * gx; g01 += ux * gy;
+      g10 += uy * gx; g11 += uy * gy;
+    }
+    const double a = area[t];
+    sw += a * (g10 - g01);
+    sd += a * (g00 + g11);
+    sa += a;
+  }
+  if (vort) vort[v] = sa > 0.0 ? sw / sa : 0.0;
+  if (div) div[v] = sa > 0.0 ? sd / sa : 0.0;
+}
+
 }  // namespace
+
+void simplex_record_fields(hipStream_t s, const SimplexMesh &M, long n_points, const double *su, double *vort, double *div) {
+  if (n_points > 0)
+    hipLaunchKernelGGL(simplex_record_fields_kernel, dim3((unsigned)((n_points + 255) / 256)), dim3(256), 0, s, n_points, M.cell_u,
+                       M.grad_lam, M.area, M.vert_ptr, M.vert_ent, su, vort, div);
+}
 
 void simplex_record(hipStream_t s, long n_points, const double *su, const double *sp, double *vel3, double *prs) {
   if (n_points > 0)

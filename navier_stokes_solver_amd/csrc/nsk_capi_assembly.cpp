@@ -97,6 +97,7 @@ int nsk_assembly_set_cells(nsk_handle h, int64_t n_cells, const int32_t *cell_u_
   A.mf_valid = false;   // (cq of another mesh)
   A.forces_set = false;   // (faces index the cells of another mesh)
   A.record_set = false;   // (so does the record's list)
+  A.rec_grad_set = false;
   A.rec_points_set = false;
   if (!A.sol_u) {
     A.sol_u = h->pool_u.get(true); A.eval_u = h->pool_u.get(true); A.old_u = h->pool_u.get(true);
@@ -252,6 +253,7 @@ int nsk_assembly_set_simplex(nsk_handle h, int64_t n_cells, const int32_t *cell_
   A.mf_valid = false;
   A.forces_set = false;   // (edges index the cells of another mesh)
   A.record_set = false;
+  A.rec_grad_set = false;
   A.rec_points_set = false;   // (the points name nodes of another numbering)
   A.sx_delta_valid = false;
   A.rec_out.release();
@@ -441,6 +443,7 @@ int nsk_record_set_cells(nsk_handle h, int64_t n_cells, const int32_t *cells, in
     if (cells[c] < 0 || cells[c] >= A.n_cells) throw Error(-72, "nsk_record_set_cells: cell index out of range");
   hipStream_t s = h->s();
   A.record_set = false;
+  A.rec_grad_set = false;   // (tables of another list's subdivisions)
   A.rec_cell.upload(cells, (size_t)n_cells, s);
   if (subdivisions > 1) {
     A.rec_wu.upload(w_u, (size_t)ppc * 16, s);
@@ -512,6 +515,65 @@ int nsk_state_get_record(nsk_handle h, int64_t n_points, double *vel3, double *p
   }
   NSK_HIP(hipMemcpyAsync(vel3, A.rec_out.p, sizeof(double) * (size_t)n_points * 3, hipMemcpyDeviceToHost, s));
   NSK_HIP(hipMemcpyAsync(prs, A.rec_out.p + (size_t)n_points * 3, sizeof(double) * (size_t)n_points, hipMemcpyDeviceToHost, s));
+  h->ctx.sync();
+  return 0;
+  NSK_CATCH(h)
+}
+
+int nsk_record_set_gradient(nsk_handle h, int subdivisions, const double *d_x, const double *d_y) {
+  NSK_TRY_DEV(h)
+  auto &A = h->asmd;
+  if (!A.ready) throw Error(-69, "nsk_record_set_gradient: no cells on the handle (call nsk_assembly_set_cells first)");
+  if (A.simplex) throw Error(-71, "nsk_record_set_gradient: the handle holds P2/P1 triangles (their fields need no tables)");
+  if (!A.record_set) throw Error(-69, "nsk_record_set_gradient: no record list handed over (nsk_record_set_cells)");
+  if (subdivisions != A.rec_sub) throw Error(-60, "nsk_record_set_gradient: subdivisions differ from the record's");
+  if (!d_x || !d_y) throw Error(-60, "nsk_record_set_gradient: bad arguments");
+  const size_t ppc = (size_t)(subdivisions + 1) * (subdivisions + 1);
+  hipStream_t s = h->s();
+  A.rec_grad_set = false;
+  A.rec_dx.upload(d_x, ppc * 16, s);
+  A.rec_dy.upload(d_y, ppc * 16, s);
+  A.rec_fout.alloc(std::max<size_t>(1, (size_t)A.rec_cells * ppc * 2));
+  h->ctx.sync();
+  A.rec_grad_set = true;
+  return 0;
+  NSK_CATCH(h)
+}
+
+int nsk_state_get_record_fields(nsk_handle h, int64_t n_points, int fields, double *out) {
+  NSK_TRY_DEV(h)
+  auto &A = h->asmd;
+  if (fields <= 0 || (fields & ~(NSK_FIELD_VORTICITY | NSK_FIELD_DIVERGENCE)))
+    throw Error(-60, "nsk_state_get_record_fields: fields must be a non-empty mask of vorticity (1) and divergence (2)");
+  if (!A.ready) throw Error(-69, "nsk_state_get_record_fields: no cells on the handle");
+  if (!A.simplex && !A.record_set)
+    throw Error(-69, "nsk_state_get_record_fields: no record list handed over (nsk_record_set_cells)");
+  if (!A.state_set) throw Error(-73, "nsk_state_get_record_fields: no state on the device");
+  if (A.simplex && A.rec_points_set)
+    throw Error(-71, "nsk_state_get_record_fields: a point list is in force (a rank's piece sees only its own cells of a vertex)");
+  const int64_t want = A.simplex ? (int64_t)h->n_p() : (int64_t)A.rec_cells * (A.rec_sub + 1) * (A.rec_sub + 1);
+  if (n_points != want || (n_points > 0 && !out))
+    throw Error(-60, "nsk_state_get_record_fields: bad arguments (n_points is not the record's number of points)");
+  if (!A.simplex && !A.rec_grad_set)
+    throw Error(-69, "nsk_state_get_record_fields: no gradient tables handed over (nsk_record_set_gradient)");
+  if (A.simplex && (h->ctx.comm.nranks > 1 || 2 * n_points > (int64_t)h->n_u()))
+    throw Error(-60, "nsk_state_get_record_fields: the P2/P1 record covers one rank with the vertices numbered first");
+  if (n_points == 0) return 0;
+  hipStream_t s = h->s();
+  const bool wv = fields & NSK_FIELD_VORTICITY, wd = fields & NSK_FIELD_DIVERGENCE;
+  if (A.simplex && A.rec_fout.n != (size_t)n_points * 2) A.rec_fout.alloc((size_t)n_points * 2);
+  double *dv = wv ? A.rec_fout.p : nullptr, *dd = wd ? A.rec_fout.p + (size_t)n_points : nullptr;
+  if (A.simplex) {
+    const SimplexMesh SM{A.n_cells, A.sx_blocks, h->n_u() / 2, h->n_p(), A.sx_pos00, A.cell_u.p, A.cell_p.p, A.sx_grad.p,
+                         A.sx_area.p, A.sx_blk_ptr.p, A.sx_blk_ent.p, A.sx_pos0.p, A.sx_pos1.p, A.sx_node_ptr.p,
+                         A.sx_node_ent.p, A.sx_vert_ptr.p, A.sx_vert_ent.p, A.sx_outlet.p, A.dirichlet.p};
+    simplex_record_fields(s, SM, (long)n_points, A.sol_u, dv, dd);
+  } else {
+    record_fields(s, h->asm_view(), A.rec_cells, A.rec_sub, A.rec_cell.p, A.rec_dx.p, A.rec_dy.p, A.sol_u, dv, dd);
+  }
+  double *o = out;   // vorticity first
+  if (wv) { NSK_HIP(hipMemcpyAsync(o, dv, sizeof(double) * (size_t)n_points, hipMemcpyDeviceToHost, s)); o += n_points; }
+  if (wd) NSK_HIP(hipMemcpyAsync(o, dd, sizeof(double) * (size_t)n_points, hipMemcpyDeviceToHost, s));
   h->ctx.sync();
   return 0;
   NSK_CATCH(h)

@@ -379,6 +379,9 @@ struct nsk_handle_s {
     int rec_sub = 1;
     DBuf<int> rec_cell;
     DBuf<double> rec_wu, rec_wp, rec_out;   // (s+1)^2 x 16, (s+1)^2 x 9; 3 + 1 doubles per point (P2/P1: per vertex)
+    // the gradient tables of nsk_record_set_gradient: void with the record's list
+    bool rec_grad_set = false;
+    DBuf<double> rec_dx, rec_dy, rec_fout;  // (s+1)^2 x 16 each; vorticity | divergence, one double per point each
     // P2/P1: the record's points as local ids (nsk_record_set_points): void with the cell data
     bool rec_points_set = false;
     long rec_points = 0;

@@ -927,6 +927,24 @@ int nsp_record_tables(const nsp_mesh *m, int32_t s, double *w_u, double *w_p) {
   return 0;
 }
 
+// Gradient tables of the record's vorticity and divergence (nsk_record_set_gradient): each entry the double product of two
+// 1-D values, then one division (postprocess.record_gradient_tables gives the same bits).
+int nsp_record_gradient_tables(const nsp_mesh *m, int32_t s, double hx, double hy, double *d_x, double *d_y) {
+  if (!m || s < 1 || s > 4 || !d_x || !d_y || !(hx > 0.0) || !(hy > 0.0)) return -1;
+  double l3[5][4], d3[5][4];
+  for (int k = 0; k <= s; ++k) lagrange(m->T.gll, 4, (double)k / (double)s, l3[k], d3[k]);
+  for (int l = 0; l <= s; ++l)
+    for (int k = 0; k <= s; ++k) {
+      const int pt = l * (s + 1) + k;
+      for (int b = 0; b < 4; ++b)
+        for (int a = 0; a < 4; ++a) {
+          d_x[pt * 16 + b * 4 + a] = d3[k][a] * l3[l][b] / hx;
+          d_y[pt * 16 + b * 4 + a] = l3[k][a] * d3[l][b] / hy;
+        }
+    }
+  return 0;
+}
+
 // Support points of this rank's owned DoFs (DoFTools::map_dofs_to_support_points): out_xy[2 d], out_xy[2 d + 1] for
 // owned DoF d of the space (0 velocity: both components of a node share the point; 1 pressure).
 void nsp_support_points(const nsp_mesh *m, int space, double *out_xy) {

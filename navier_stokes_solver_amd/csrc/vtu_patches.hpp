@@ -25,16 +25,23 @@ inline std::string counter_text(unsigned counter, int n_digits) {
   return buf;
 }
 
-// the record <name>_<cnt>.pvtu naming the pieces of all ranks
-inline void write_pvtu(const std::filesystem::path &dir, const std::string &name, const std::string &cnt, int nranks) {
+// the derived arrays of the binary record, in file order; bit k of nsk_state_get_record_fields' mask
+constexpr int kFields = 2;
+inline const char *field_name(int k) { return k == 0 ? "vorticity" : "divergence"; }
+
+// the record <name>_<cnt>.pvtu naming the pieces of all ranks; fields: the mask of the pieces' derived arrays
+inline void write_pvtu(const std::filesystem::path &dir, const std::string &name, const std::string &cnt, int nranks,
+                       unsigned fields = 0) {
   const std::string record = (dir / (name + "_" + cnt + ".pvtu")).string();
   std::FILE *f = std::fopen(record.c_str(), "w");
   if (!f) throw std::runtime_error("cannot write " + record);
   std::fprintf(f, "<?xml version=\"1.0\"?>\n<VTKFile type=\"PUnstructuredGrid\" version=\"0.1\" byte_order=\"LittleEndian\">\n"
                   "<PUnstructuredGrid GhostLevel=\"0\">\n<PPointData Scalars=\"scalars\">\n"
                   "<PDataArray type=\"Float64\" Name=\"velocity\" NumberOfComponents=\"3\" format=\"ascii\"/>\n"
-                  "<PDataArray type=\"Float64\" Name=\"pressure\" format=\"ascii\"/>\n"
-                  "<PDataArray type=\"Float64\" Name=\"partitioning\" format=\"ascii\"/>\n</PPointData>\n<PPoints>\n"
+                  "<PDataArray type=\"Float64\" Name=\"pressure\" format=\"ascii\"/>\n");
+  for (int k = 0; k < kFields; ++k)
+    if (fields >> k & 1u) std::fprintf(f, "<PDataArray type=\"Float64\" Name=\"%s\" format=\"ascii\"/>\n", field_name(k));
+  std::fprintf(f, "<PDataArray type=\"Float64\" Name=\"partitioning\" format=\"ascii\"/>\n</PPointData>\n<PPoints>\n"
                   "<PDataArray type=\"Float64\" NumberOfComponents=\"3\"/>\n</PPoints>\n");
   for (int r = 0; r < nranks; ++r)
     std::fprintf(f, "%s<Piece Source=\"%s_%s.%d.vtu\"/>", r ? "\n" : "", name.c_str(), cnt.c_str(), r);
@@ -82,25 +89,30 @@ inline std::string write_patches(const std::string &directory, const std::string
 
 // The piece as VTK XML with raw appended data (postprocess.VtuRecord writes the same bytes from the same
 // arrays): the XML header, then after <AppendedData encoding="raw"> and `_` the blocks — a UInt64 byte count and that many
-// bytes each — points, velocity, pressure, [partitioning,] connectivity, offsets, types.  The header is padded with blanks
-// so that the first block starts at a multiple of 8 in the file.  Built once per run and rank with everything but velocity
-// and pressure filled in; a report fills vel3() / prs() (nsk_state_get_record) and writes the image with one write.
+// bytes each — points, velocity, pressure, [vorticity,] [divergence,] [partitioning,] connectivity, offsets, types.  The
+// header is padded with blanks so that the first block starts at a multiple of 8 in the file.  Built once per run and rank
+// with everything but velocity, pressure and the derived arrays filled in; a report fills vel3() / prs()
+// (nsk_state_get_record) and field(k) (nsk_state_get_record_fields) and writes the image with one write.
 class Record {
  public:
-  // points: 3 doubles per point; rank < 0: no partitioning array
+  // points: 3 doubles per point; rank < 0: no partitioning array; fields: mask of the derived arrays (0: the image without them)
   Record(int64_t n_points, const double *points, const std::vector<int32_t> &conn, const std::vector<int32_t> &offsets,
          const std::vector<uint8_t> &types, int rank, const char *declaration = "<?xml version=\"1.0\" ?>",
-         const char *point_data = "Scalars=\"scalars\"")
-      : n_points_(n_points) {
+         const char *point_data = "Scalars=\"scalars\"", unsigned fields = 0)
+      : n_points_(n_points), fields_(fields) {
     const size_t n = (size_t)n_points, m = offsets.size();
     if (types.size() != m) throw std::runtime_error("vtu::Record: offsets and types do not match");
+    if (fields >> kFields) throw std::runtime_error("vtu::Record: unknown field");
     const bool part = rank >= 0;
-    // byte counts in block order
-    const size_t bytes[7] = {24 * n, 24 * n, 8 * n, part ? 8 * n : 0, 4 * conn.size(), 4 * m, m};
-    size_t at[7], pos = 0;
-    for (int b = 0; b < 7; ++b) {
+    // blocks in file order: 0 points, 1 velocity, 2 pressure, 3 partitioning, 4 connectivity, 5 offsets, 6 types, 7 + k field k
+    constexpr int NB = 7 + kFields;
+    const int order[NB] = {0, 1, 2, 7, 8, 3, 4, 5, 6};
+    const size_t bytes[NB] = {24 * n, 24 * n, 8 * n, 8 * n, 4 * conn.size(), 4 * m, m, 8 * n, 8 * n};
+    const bool present[NB] = {true, true, true, part, true, true, true, (fields & 1u) != 0, (fields & 2u) != 0};
+    size_t at[NB], pos = 0;
+    for (int b : order) {
       at[b] = pos;
-      if (b != 3 || part) pos += 8 + bytes[b];
+      if (present[b]) pos += 8 + bytes[b];
     }
     auto arr = [&](const char *type, const char *name, const char *extra, int b) {
       return std::string("<DataArray type=\"") + type + "\"" + (name ? std::string(" Name=\"") + name + "\"" : std::string()) +
@@ -114,6 +126,8 @@ class Record {
                        arr("Int32", "connectivity", "", 4) + arr("Int32", "offsets", "", 5) + arr("UInt8", "types", "", 6) +
                        "</Cells>\n<PointData " + point_data + ">\n" +
                        arr("Float64", "velocity", " NumberOfComponents=\"3\"", 1) + arr("Float64", "pressure", "", 2) +
+                       (present[7] ? arr("Float64", field_name(0), "", 7) : std::string()) +
+                       (present[8] ? arr("Float64", field_name(1), "", 8) : std::string()) +
                        (part ? arr("Float64", "partitioning", "", 3) : std::string()) +
                        "</PointData>\n</Piece>\n</UnstructuredGrid>\n";
     const std::string opening = "<AppendedData encoding=\"raw\">\n_", closing = "\n</AppendedData>\n</VTKFile>\n";
@@ -126,15 +140,16 @@ class Record {
     std::memcpy(im, head.data(), start);
     std::memcpy(im + start + pos, closing.data(), closing.size());
     const std::vector<double> partv(part ? n : 0, (double)rank);
-    const void *src[7] = {points, nullptr, nullptr, partv.data(), conn.data(), offsets.data(), types.data()};
-    for (int b = 0; b < 7; ++b) {
-      if (b == 3 && !part) continue;
+    const void *src[NB] = {points, nullptr, nullptr, partv.data(), conn.data(), offsets.data(), types.data(), nullptr, nullptr};
+    for (int b = 0; b < NB; ++b) {
+      if (!present[b]) continue;
       const uint64_t count = bytes[b];
       std::memcpy(im + start + at[b], &count, 8);
       if (src[b] && count) std::memcpy(im + start + at[b] + 8, src[b], count);
     }
     vel3_ = reinterpret_cast<double *>(im + start + at[1] + 8);
     prs_ = reinterpret_cast<double *>(im + start + at[2] + 8);
+    for (int k = 0; k < kFields; ++k) field_[k] = present[7 + k] ? reinterpret_cast<double *>(im + start + at[7 + k] + 8) : nullptr;
   }
   Record(const Record &) = delete;
   Record &operator=(const Record &) = delete;
@@ -142,6 +157,8 @@ class Record {
   int64_t n_points() const { return n_points_; }
   double *vel3() { return vel3_; }   // 3 per point: the file's velocity array
   double *prs() { return prs_; }     // 1 per point: the file's pressure array
+  unsigned fields() const { return fields_; }
+  double *field(int k) { return field_[k]; }   // 1 per point: the file's array field_name(k), or null
   const char *data() const { return reinterpret_cast<const char *>(image_.data()); }
   size_t size() const { return size_; }
 
@@ -158,12 +175,14 @@ class Record {
     fs::create_directories(dir);
     const std::string piece = (dir / (name + "_" + cnt + "." + std::to_string(rank) + ".vtu")).string();
     write(piece);
-    if (rank == 0) write_pvtu(dir, name, cnt, nranks);
+    if (rank == 0) write_pvtu(dir, name, cnt, nranks, fields_);
     return piece;
   }
 
  private:
   int64_t n_points_;
+  unsigned fields_ = 0;
+  double *field_[kFields] = {nullptr, nullptr};
   size_t size_ = 0;
   std::vector<uint64_t> image_;
   double *vel3_ = nullptr, *prs_ = nullptr;
@@ -172,7 +191,8 @@ class Record {
 // The piece of the generated mesh's cells ij in file order with s = subdivisions in 1..4: per cell (s+1)^2 points
 // ((i + k/s) hx, (j + l/s) hy, 0), pt = l (s+1) + k, and s^2 VTK_QUADs base + l (s+1) + k, +1, +(s+1)+1, +(s+1) — for s = 1
 // the points and the `0 1 3 2` of write_patches.
-inline std::unique_ptr<Record> quad_record(int64_t n_cells, const int32_t *ij, double hx, double hy, int s, int rank) {
+inline std::unique_ptr<Record> quad_record(int64_t n_cells, const int32_t *ij, double hx, double hy, int s, int rank,
+                                           unsigned fields = 0) {
   if (s < 1 || s > 4) throw std::runtime_error("vtu::quad_record: subdivisions outside 1..4");
   const int64_t ppc = (int64_t)(s + 1) * (s + 1), n_points = n_cells * ppc, n_quads = n_cells * s * s;
   std::vector<double> pts(3 * (size_t)n_points, 0.0);
@@ -192,7 +212,8 @@ inline std::unique_ptr<Record> quad_record(int64_t n_cells, const int32_t *ij, d
       }
   }
   for (int64_t q = 0; q < n_quads; ++q) offs[(size_t)q] = (int32_t)(4 * (q + 1));
-  return std::make_unique<Record>(n_points, pts.data(), conn, offs, std::vector<uint8_t>((size_t)n_quads, 9), rank);
+  return std::make_unique<Record>(n_points, pts.data(), conn, offs, std::vector<uint8_t>((size_t)n_quads, 9), rank,
+                                  "<?xml version=\"1.0\" ?>", "Scalars=\"scalars\"", fields);
 }
 
 }  // namespace vtu

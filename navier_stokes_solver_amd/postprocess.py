@@ -250,16 +250,18 @@ def _join_rows(a):
     return "\n".join(out.tolist())
 
 
-def _write_pvtu(directory, name, cnt, nranks):
-    """The record `<name>_<cnt>.pvtu` naming the pieces of all ranks, as `write_vtu` writes it."""
+def _write_pvtu(directory, name, cnt, nranks, fields=()):
+    """The record `<name>_<cnt>.pvtu` naming the pieces of all ranks, as `write_vtu` writes it; `fields`: the derived arrays
+    of the pieces, listed after `pressure`."""
     pieces = "\n".join(f'<Piece Source="{name}_{cnt}.{r}.vtu"/>' for r in range(nranks))
+    extra = "".join(f'<PDataArray type="Float64" Name="{f}" format="ascii"/>\n' for f in fields)
     pvtu = f"""<?xml version="1.0"?>
 <VTKFile type="PUnstructuredGrid" version="0.1" byte_order="LittleEndian">
 <PUnstructuredGrid GhostLevel="0">
 <PPointData Scalars="scalars">
 <PDataArray type="Float64" Name="velocity" NumberOfComponents="3" format="ascii"/>
 <PDataArray type="Float64" Name="pressure" format="ascii"/>
-<PDataArray type="Float64" Name="partitioning" format="ascii"/>
+{extra}<PDataArray type="Float64" Name="partitioning" format="ascii"/>
 </PPointData>
 <PPoints>
 <PDataArray type="Float64" NumberOfComponents="3"/>
@@ -355,16 +357,48 @@ def record_tables(s):
     return out[0], out[1]
 
 
+FIELDS = ("vorticity", "divergence")        # the derived arrays of the record, in file order; bit k of the library's mask
+
+
+def record_gradient_tables(s, hx, hy):
+    """(d_x, d_y) [(s+1)^2, 16] of `nsk_record_set_gradient`, laid out like `record_tables`' w_u:
+    d_x[pt, b*4 + a] = L'_a(t_k) L_b(t_l) / hx and d_y[pt, b*4 + a] = L_a(t_k) L'_b(t_l) / hy on the GLL nodes, each entry the
+    double product of two `_lagrange` values followed by one division (csrc/problem_gen.cpp::nsp_record_gradient_tables gives
+    the same bits)."""
+    if s not in (1, 2, 3, 4):
+        raise ValueError("subdivisions must be 1, 2, 3 or 4")
+    if not (hx > 0.0 and hy > 0.0):
+        raise ValueError("cell sizes must be positive")
+    val, der = _lagrange(_GLL, np.arange(s + 1) / s)
+    v, d = val.T, der.T                                                # [point, basis]
+    dx = (d[None, :, None, :] * v[:, None, :, None]).reshape((s + 1) ** 2, 16) / float(hx)       # [l, k, b, a]
+    dy = (v[None, :, None, :] * d[:, None, :, None]).reshape((s + 1) ** 2, 16) / float(hy)
+    return dx, dy
+
+
+def field_mask(fields):
+    """The mask of `nsk_state_get_record_fields` for a tuple of names out of `FIELDS`."""
+    m = 0
+    for f in fields:
+        if f not in FIELDS:
+            raise ValueError(f"unknown record field {f!r}")
+        m |= 1 << FIELDS.index(f)
+    return m
+
+
 class VtuRecord:
     """The image of one `.vtu` piece in VTK's XML format with raw appended data, built once per run and rank: the XML
     header, then after `<AppendedData encoding="raw">` and `_` the blocks — a UInt64 byte count and that many bytes each —
-    points, `velocity`, `pressure`, [`partitioning`,] `connectivity`, `offsets`, `types`.  The header is padded with blanks
-    so that the first block starts at a multiple of 8 in the file.  Everything but `velocity` and `pressure` is filled in
-    here; `vel3` [n, 3] and `prs` [n] are views of the image at those two blocks — a report fills them
-    (`LinearSolver.state_record(vel3=..., prs=...)`) and writes the image with one write."""
+    points, `velocity`, `pressure`, [`vorticity`,] [`divergence`,] [`partitioning`,] `connectivity`, `offsets`, `types`.  The
+    header is padded with blanks so that the first block starts at a multiple of 8 in the file.  Everything but `velocity`,
+    `pressure` and the derived arrays is filled in here; `vel3` [n, 3] and `prs` [n] are views of the image at those two
+    blocks — a report fills them (`LinearSolver.state_record(vel3=..., prs=...)`) and writes the image with one write.
+    `fields`: names out of `FIELDS`; each becomes one Float64 array of one component after `pressure`, in the
+    order of `FIELDS`, and `field[name]` [n] is the view a report fills (`LinearSolver.record_fields`).  With no fields the
+    image is the one without them, byte for byte."""
 
     def __init__(self, points, connectivity, offsets, types, partitioning=None, declaration='<?xml version="1.0" ?>',
-                 point_data='Scalars="scalars"'):
+                 point_data='Scalars="scalars"', fields=()):
         pts = np.ascontiguousarray(points, np.float64).reshape(-1, 3)
         conn = np.ascontiguousarray(connectivity, np.int32).reshape(-1)
         offs = np.ascontiguousarray(offsets, np.int32).reshape(-1)
@@ -372,7 +406,9 @@ class VtuRecord:
         n, m = len(pts), len(offs)
         if len(typ) != m:
             raise ValueError("offsets and types do not match")
-        blocks = [("points", pts), ("velocity", 24 * n), ("pressure", 8 * n)]
+        field_mask(fields)
+        self.fields = tuple(f for f in FIELDS if f in fields)
+        blocks = [("points", pts), ("velocity", 24 * n), ("pressure", 8 * n)] + [(f, 8 * n) for f in self.fields]
         if partitioning is not None:
             blocks.append(("partitioning", np.full(n, float(partitioning))))
         blocks += [("connectivity", conn), ("offsets", offs), ("types", typ)]
@@ -387,6 +423,7 @@ class VtuRecord:
                 + arr("Float64", "points", ' NumberOfComponents="3"') + "</Points>\n<Cells>\n" + arr("Int32", "connectivity")
                 + arr("Int32", "offsets") + arr("UInt8", "types") + f"</Cells>\n<PointData {point_data}>\n"
                 + arr("Float64", "velocity", ' NumberOfComponents="3"') + arr("Float64", "pressure")
+                + "".join(arr("Float64", f) for f in self.fields)
                 + (arr("Float64", "partitioning") if partitioning is not None else "")
                 + "</PointData>\n</Piece>\n</UnstructuredGrid>\n")
         opening = '<AppendedData encoding="raw">\n_'
@@ -405,9 +442,10 @@ class VtuRecord:
         self.n_points, self.n_cells = n, m
         self.vel3 = self.image[start + at["velocity"] + 8:start + at["velocity"] + 8 + 24 * n].view(np.float64).reshape(n, 3)
         self.prs = self.image[start + at["pressure"] + 8:start + at["pressure"] + 8 + 8 * n].view(np.float64)
+        self.field = {f: self.image[start + at[f] + 8:start + at[f] + 8 + 8 * n].view(np.float64) for f in self.fields}
 
     @classmethod
-    def quads(cls, ij, hx, hy, subdivisions=1, rank=0):
+    def quads(cls, ij, hx, hy, subdivisions=1, rank=0, fields=()):
         """The piece of the generated mesh's cells `ij` [n, 2] in file order: per cell (s+1)^2 points ((i + k/s) hx,
         (j + l/s) hy, 0), pt = l (s+1) + k, and s^2 VTK_QUADs base + l (s+1) + k, +1, +(s+1)+1, +(s+1) — for s = 1 the
         points and the `0 1 3 2` of `write_vtu_patches`."""
@@ -424,20 +462,21 @@ class VtuRecord:
         first = (l * (s + 1) + k)[:, None] + np.array([0, 1, s + 2, s + 1])        # VTK_QUAD ordering
         conn = ppc * np.arange(n_cells)[:, None, None] + first[None]
         n_quads = n_cells * s * s
-        return cls(pts.reshape(-1, 3), conn, 4 * np.arange(1, n_quads + 1), np.full(n_quads, 9), partitioning=rank)
+        return cls(pts.reshape(-1, 3), conn, 4 * np.arange(1, n_quads + 1), np.full(n_quads, 9), partitioning=rank,
+                   fields=fields)
 
     @classmethod
-    def triangles(cls, nodes, cells):
+    def triangles(cls, nodes, cells, fields=()):
         """The piece `simplex.write_vtu` writes: all vertices `nodes` [n, 2], the piece's linear triangles `cells` [m, 3]."""
         nodes = np.asarray(nodes, float).reshape(-1, 2)
         cells = np.asarray(cells).reshape(-1, 3)
         pts = np.concatenate([nodes, np.zeros((len(nodes), 1))], axis=1)
         return cls(pts, cells, 3 * np.arange(1, len(cells) + 1), np.full(len(cells), 5), declaration='<?xml version="1.0"?>',
-                   point_data='Vectors="velocity" Scalars="pressure"')
+                   point_data='Vectors="velocity" Scalars="pressure"', fields=fields)
 
     def write(self, path):
         """The image as it stands, with one write."""
-        if not (np.isfinite(self.vel3).all() and np.isfinite(self.prs).all()):
+        if not (np.isfinite(self.vel3).all() and np.isfinite(self.prs).all() and all(np.isfinite(a).all() for a in self.field.values())):
             raise ValueError("VTU output touched an entry this rank does not hold (owned + ghost DoFs)")
         with open(path, "wb") as f:
             f.write(self.image)
@@ -451,5 +490,5 @@ def write_vtu_record(record, directory, name, counter, n_digits=None, rank=0, nr
     os.makedirs(directory, exist_ok=True)
     piece = record.write(os.path.join(directory, f"{name}_{cnt}.{rank}.vtu"))
     if rank == 0:
-        _write_pvtu(directory, name, cnt, nranks)
+        _write_pvtu(directory, name, cnt, nranks, record.fields)
     return piece

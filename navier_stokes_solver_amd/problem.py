@@ -75,6 +75,8 @@ def lib() -> C.CDLL:
         L.nsp_face_tables.argtypes = [C.c_void_p, C.c_void_p]
         L.nsp_record_tables.restype = C.c_int
         L.nsp_record_tables.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+        L.nsp_record_gradient_tables.restype = C.c_int
+        L.nsp_record_gradient_tables.argtypes = [C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_void_p, C.c_void_p]
         _LIB = L
     return _LIB
 

@@ -63,6 +63,7 @@ EXPORTS = [
     "nsk_debug_spmv_form",
     "nsk_forces_set_faces", "nsk_forces_set_edges", "nsk_forces", "nsk_state_get_patches",
     "nsk_record_set_cells", "nsk_state_get_record", "nsk_record_set_points",
+    "nsk_record_set_gradient", "nsk_state_get_record_fields",
 ]
 
 
@@ -146,6 +147,8 @@ def lib() -> C.CDLL:
         L.nsk_record_set_cells.argtypes = [vp, C.c_int64, i32p, C.c_int, f64p, f64p]
         L.nsk_state_get_record.argtypes = [vp, C.c_int64, f64p, f64p]
         L.nsk_record_set_points.argtypes = [vp, C.c_int64, i32p, i32p]
+        L.nsk_record_set_gradient.argtypes = [vp, C.c_int, f64p, f64p]
+        L.nsk_state_get_record_fields.argtypes = [vp, C.c_int64, C.c_int, f64p]
         L.nsk_download_rhs.argtypes = [vp, f64p, f64p]
         L.nsk_time_assemble.argtypes = [vp, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_double)]
         L.nsk_amg_info.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
@@ -628,6 +631,28 @@ class LinearSolver:
         self._ck(self.L.nsk_state_get_record(self.h, prs.size, vel3.ctypes.data,
                                              prs.ctypes.data))
         return vel3, prs
+
+    def set_record_gradient(self, s, hx, hy, tables=None):
+        """The gradient tables of the record's vorticity and divergence for cells of hx x hy; after set_record
+        with the same s on a Q3/Q2 handle.  `tables`: (d_x, d_y) to hand over instead of `postprocess.record_gradient_tables`."""
+        if tables is None:
+            from . import postprocess as PP
+            tables = PP.record_gradient_tables(int(s), hx, hy)
+        dx, dy = _f64(tables[0]), _f64(tables[1])
+        self._ck(self.L.nsk_record_set_gradient(self.h, int(s), dx.ctypes.data, dy.ctypes.data))
+
+    def record_fields(self, n_points, fields, out=None):
+        """[k, n_points]: the arrays selected by the mask `fields` (1: vorticity, 2: divergence; vorticity first) at the points
+        of `state_record`, from the resident state.  `out`: a contiguous float64 array of that size to fill instead (one
+        field: its position inside a file image)."""
+        fields, n = int(fields), int(n_points)
+        k = bin(fields & 3).count("1") if fields > 0 else 0
+        if out is None:
+            out = np.empty((max(k, 1), n))
+        elif out.dtype != np.float64 or not out.flags.c_contiguous or out.size != max(k, 1) * n:
+            raise ValueError("record_fields: out must be a contiguous float64 array of n_points per selected field")
+        self._ck(self.L.nsk_state_get_record_fields(self.h, n, fields, out.ctypes.data))
+        return out
 
     def scale_values(self, blk, factor):
         self._ck(self.L.nsk_scale_values(self.h, blk, float(factor)))
